@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X hot path: batched Env2DAirfoil steps on the ys930 mesh.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: set-up, W untimed steps, K timed steps, the result line (metric, value, unit,
+ms_per_step = milliseconds of one timed batched step, ...).  `--dump-outputs DIR` writes what the timed path computed in
+its last step (`DIR/<name>.npy`, float32 / float64; inputs are seeded, so two builds can be compared output for output).
+`--full` adds everything else described below (timed repeats, CPU baseline, S1 / S2 / learning loop, BASELINE configs,
+roofline and per-kernel figures, the detail file).
 
 `value`: a "step" is one batched ENVIRONMENT step of unit-of-work S3 (the north-star step): every
 one of the `--envs` (default 128, BASELINE.json configs[1]) environments of a rank removes a vertex and restores the
@@ -10,13 +16,14 @@ snapshots and evaluates the ten force integrals (Env2DAirfoil.py:547-602, :380-4
 (:244-290), runs ONE IPCS time step on the coarsened mesh (flow_solver.py:362-396, warm start = interpolated last
 snapshot) and the Q-network forward (airfoilgcnn.py:85-145); actions follow `default_rng(1370 + ...)` streams with
 epsilon = 0.5, so the meshes of the batch diverge; terminated environments are reset in place.  Everything is resident
-in HBM before the timed region.  K steps are timed `--repeats` (5) times, each between a barrier + synchronize pair;
-value = (ranks x envs x K) / median-over-repeats of the max-over-ranks time (min / max are reported as well).
+in HBM before the timed region.  K steps are timed `--repeats` times (1 in a plain run, 5 with `--full`), each between a
+barrier + synchronize pair; value = (ranks x envs x K) / median-over-repeats of the max-over-ranks time (min / max are
+reported as well).
 
 For N > 1 launch with torchrun (one rank per GPU); environments are independent so they are sharded across ranks
 with no data-path collective (weak scaling).
 
-Top-level extras: s1_env_steps_per_s (the reference-semantics step without the flow re-solve), s2_ipcs_env_steps_per_s
+Top-level extras (`--full`): s1_env_steps_per_s (the reference-semantics step without the flow re-solve), s2_ipcs_env_steps_per_s
 (one FlowSolver.evolve per env on 128 identical, developed-flow meshes), s3_env_steps_per_s (= value),
 training_env_steps_per_s (S1 rollout + replay + optimiser step, RCCL all-reduce for N > 1).
   roofline      dominant kernel of an S3 step (smooth_kernel): algorithmic bytes per launch / launch duration measured
@@ -279,12 +286,13 @@ def _timed(dist, dev, fn):
 
 
 def measure_env_steps(args, dev, dist, world, flow_steps=0, steps=None, warmup=8, repeats=1, mesh=None, keep=None, envs=None,
-                      flow_pressure="cg"):
+                      flow_pressure="cg", outputs=None):
     """Units of work S1 / S3 for every env of the batch, all on the GPU: vertex removal + Delaunay
     restoration (mdq_remesh), smooth(50) (mdq_smooth), topology / N-closest / state graph (mdq_env_topology), snapshot
     interpolation + 10 force integrals + node features, fused Q-network forward + epsilon-greedy action; with
     flow_steps > 0 (S3) also the matrix-free IPCS set-up and `flow_steps` IPCS steps on every coarsened mesh.
-    `steps` batched steps are timed `repeats` times.  Returns env-steps/s over all ranks (median) and the details."""
+    `steps` batched steps are timed `repeats` times.  Returns env-steps/s over all ranks (median) and the details; a dict
+    `outputs` receives what the last timed step computed (`step_outputs`)."""
     import torch
     from meshdqn_amd.airfoilgcnn import NodeRemovalNet
     from meshdqn_amd.env import Env2DAirfoil
@@ -338,18 +346,22 @@ def measure_env_steps(args, dev, dist, world, flow_steps=0, steps=None, warmup=8
             ra.append(np.array([p_[1] for p_ in pairs]))
         return ex, ra
 
+    last = [None]           # what the last rollout returned to its caller
     if args.host_step:      # state -> host -> action -> host -> step: two host round trips per batched step
-        run = lambda k: groups.rollout(act, k)                      # noqa: E731
+        def run(k):
+            last[0] = groups.rollout(act, k)
     else:                   # device-resident: action selection / decoding / reward / reset logic as kernels
         def run(k):
             ex, ra = draw(k)
-            groups.rollout_device(fused, k, ex, ra)
+            last[0] = groups.rollout_device(fused, k, ex, ra)
     run(warmup)
     if keep is not None and not args.host_step:     # HIP events around every smoothing launch of the timed rollouts
         for e in groups.envs:
             e.smooth_events = []
     times = [_timed(dist, dev, lambda: run(steps)) for _ in range(repeats)]
     el = float(np.median(times))
+    if outputs is not None:
+        outputs.update(step_outputs(groups, last[0], args.host_step))
     venv = groups.envs[0]
     rate = world * B * steps / el
     out = dict(value=rate, unit="env steps/s", ms_per_batched_step=el / steps * 1e3, batched_steps=steps, repeats=repeats,
@@ -386,6 +398,54 @@ def measure_env_steps(args, dev, dist, world, flow_steps=0, steps=None, warmup=8
         for e in groups.envs:
             e.smooth_events = None
     return out
+
+
+def step_outputs(groups, last, host_step=False):
+    """What a caller of the timed path holds after its last batched step, one row per environment (groups in order):
+    the step's rewards / dones / actions / codes / vertex counts (the rollout's return), the probe drag / lift of the
+    coarsened meshes, the drag / lift of the IPCS leg (overlap mode: the leg launched in that step), the meshes the next
+    step starts from (vertex counts, coordinates with the slots past the count zeroed; an environment the step terminated
+    is reset already) and the state the next Q-forward reads."""
+    import torch
+    out = {}
+    if host_step:
+        out["rewards"] = np.concatenate([r for r, _ in last]).astype(np.float64)
+        out["dones"] = np.concatenate([d for _, d in last]).astype(np.float64)
+    else:
+        for k in ("rewards", "dones", "actions", "codes", "nv"):
+            out[k] = np.concatenate([r[k][-1] for r in last]).astype(np.float64)
+    per = {}
+    for g, env in enumerate(groups.envs):
+        with torch.cuda.stream(groups.streams[g]):
+            flow = env.flow_wait()
+            dt = env.dtopo
+            slots = torch.arange(dt.coords.shape[1], device=dt.coords.device)[None, :] < dt.nv[:, None].long()
+            parts = dict(drag=np.asarray(env.new_drags, np.float64), lift=np.asarray(env.new_lifts, np.float64),
+                         coords=(dt.coords * slots[..., None]).cpu().numpy().astype(np.float64), mesh_nv=dt.nv.cpu().numpy(),
+                         state_x=env.get_state()["x"].cpu().numpy().astype(np.float32))
+            if flow is not None:
+                parts.update(flow_drag=np.asarray(flow[0], np.float64), flow_lift=np.asarray(flow[1], np.float64))
+            groups.streams[g].synchronize()
+        for k, v in parts.items():
+            per.setdefault(k, []).append(v)
+    out.update({k: np.concatenate(v) for k, v in per.items()})
+    return out
+
+
+OUTPUTS_LIMIT = 64 << 20        # bytes of all files --dump-outputs writes
+
+
+def write_outputs(path, outputs):
+    """`outputs` (name -> array) as `path/<name>.npy`, float32 arrays as they are and everything else as float64."""
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+            for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > OUTPUTS_LIMIT:
+        raise ValueError(f"--dump-outputs: {total} bytes of outputs, more than the {OUTPUTS_LIMIT} allowed")
+    os.makedirs(path, exist_ok=True)
+    for k, a in sorted(arrs.items()):
+        np.save(os.path.join(path, f"{k}.npy"), a)
+    return sorted(arrs)
 
 
 def measure_smooth_kernel(dev, groups, reps=20):
@@ -695,14 +755,17 @@ def _short(v, n=120):
 
 def compact_line(res, detail_path):
     """The contract line from the full result: contract keys only, one NUMBER per side rate, no prose (strings <= 120
-    characters), <= LINE_LIMIT bytes.  Everything else is in the detail file."""
-    cfg, roof, cpu = res["config"], res["roofline"], res.get("cpu_baseline")
+    characters), <= LINE_LIMIT bytes.  Everything else is in the detail file (`detail_path`; None: a plain run, which has
+    the headline keys only and writes no detail file)."""
+    cfg, roof, cpu = res["config"], res.get("roofline"), res.get("cpu_baseline")
     line = {k: _num(res[k]) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "steady_state_ms_per_step",
                                        "repeats", "value_min", "value_max", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
     line["config"] = {"workload": cfg["workload_short"], "mesh": cfg["mesh"], "envs_per_gpu": cfg["envs_per_gpu"],
                       "rtol": cfg["rtol"], "dt": cfg["dt"], "mu": cfg["mu"], "rho": cfg["rho"],
                       "krylov_iters_per_ipcs_step": {k: _num(v, 4) for k, v in cfg["krylov_iters_per_ipcs_step"].items()},
                       "parallelism": cfg["parallelism"], "collective_backend": cfg["collective_backend"]}
+    if roof is None:
+        return line
     line["roofline"] = {k: _num(roof.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
     line["roofline"].update(kernel="smooth_linear_kernel", traffic_source=_short(roof.get("traffic_source_short")),
                             **{k: _num(roof.get(k)) for k in ("launch_ms", "launches_timed", "launch_ms_alone", "algorithmic_bytes_per_launch",
@@ -789,7 +852,7 @@ def launch_ranks(args, argv):
         return 2
     env = dict(os.environ)
     cpu_file = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             txt = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-child", "--cpu-budget",
                                   str(args.cpu_budget)], check=True, capture_output=True, text=True).stdout
@@ -812,13 +875,78 @@ def launch_ranks(args, argv):
     return 0
 
 
+def headline_result(args, s3, world, rccl, nv, nt):
+    """The keys of the headline (S3 rollouts of `measure_env_steps`): the result a plain run reports; `--full` adds to it."""
+    B = args.envs
+    return {
+        "metric": "env steps/sec (ys930 ~2k-tri)",
+        "value": s3["value"],
+        "unit": "env steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": s3["ms_per_batched_step"],
+        # period of a batched step inside the rollouts (HIP events; ms_per_step also pays the fill and the drain of the
+        # two-stream pipeline and the one read-back per rollout: K = --steps batched steps per rollout)
+        "steady_state_ms_per_step": s3.get("steady_state_ms_per_step"),
+        "repeats": args.repeats,
+        "value_min": s3["value_min"],
+        "value_max": s3["value_max"],
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "s3_env_steps_per_s": s3["value"],
+        "collective_backend": rccl,          # backend, RCCL version, ranks (None for a single rank)
+        "stream_setup": _stream_log(),       # rank 0: how the main / flow / optimiser streams were chosen
+        "config": {
+            "workload_short": f"{args.mesh} ({nv} vertices / {nt} triangles), {B} envs per GPU, S3 env step (remesh+smooth+interp+"
+                              f"forces+state+1 IPCS step+Q-fwd)",
+            "mesh": args.mesh,
+            "workload": f"{args.mesh} ({nv} vertices / {nt} triangles), {B} batched envs per GPU, step = S3 (north-star env "
+                        f"step): remove vertex + Delaunay restoration + smooth(50) + 5-snapshot interpolation + 10 force "
+                        f"integrals + state graph + ONE IPCS step on every coarsened mesh (matrix-free, Jacobi-BiCGStab / "
+                        f"CG, rtol {args.rtol:g}, warm start = interpolated last snapshot"
+                        + ("" if args.no_flow_overlap else "; it runs on a second stream beside the NEXT step's removal / "
+                           "smoothing / topology kernels, its drag / lift are delivered one step later")
+                        + ") + fused Q-network forward"
+                        + ("" if args.host_step else "; action selection / decoding, reward / terminal logic and in-place "
+                           "resets are kernels too (rollout_device: no host round trip inside a step)") + "; "
+                        f"epsilon = 0.5 actions from default_rng(1370 + ...), meshes diverge (vertices "
+                        f"{s3['vertices_min_max'][0]}..{s3['vertices_min_max'][1]} at the end), terminated envs reset in place",
+            "envs_per_gpu": B, "rtol": args.rtol, "dt": 1e-3, "mu": 1e-3, "rho": 1.0,
+            "numerics": {
+                "ipcs": "mode 3: operator results accumulated with LDS fp64 atomics => reproducible to round-off only; run-to-run "
+                        "spread of drag / lift after 5000 steps 1e-8 .. 1.6e-6 relative (tools/traj_spread.py), inside the 1e-4 "
+                        "contract (5000-step values within 1e-5 of the FEniCS CSV rows, tests/test_golden_gpu.py); the correction "
+                        "solve starts fused on 15 of 16 steps and takes the |b| of its stopping test from the last exact start",
+                "bitwise_reproducible": "vertex removal / Delaunay restoration, smoothing, topology / N-closest / state graph, "
+                                        "fused Q-forward, learning-step gradient (per-graph slices reduced in graph order)"},
+            "krylov_iters_per_ipcs_step": s3["krylov_iters_per_ipcs_step"],
+            "parallelism": f"dp{world} (independent envs sharded, no data-path collective)",
+            "collective_backend": rccl,
+            "reference_published": "45.8 IPCS steps/s for 1 env (FEniCS, unknown hardware; BASELINE.md) - context only",
+        },
+    }
+
+
+def _finish(dist, rank, line, real_stdout):
+    """Every rank meets at the last barrier; rank 0 prints the result line as the last thing on stdout."""
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:               # the LAST thing this process writes to stdout
+        print(line, file=real_stdout, flush=True)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50, help="K: batched S3 env steps per timed repeat")
     ap.add_argument("--warmup", type=int, default=10, help="W: untimed batched S3 env steps in front")
-    ap.add_argument("--repeats", type=int, default=5, help="timed repeats of the K steps (median reported)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed repeats of the K steps (median reported; default 1, 5 with --full)")
     ap.add_argument("--envs", type=int, default=128, help="environments per GPU")
     ap.add_argument("--spinup", type=int, default=300, help="S2: untimed IPCS steps from rest before warmup")
     ap.add_argument("--s2-steps", type=int, default=200)
@@ -840,7 +968,13 @@ def main(argv=None):
                     help="S1 / S3: the step() path with its two host round trips per batched step instead of rollout_device")
     ap.add_argument("--no-flow-overlap", action="store_true",
                     help="S3: run the IPCS step of an env step in line instead of beside the next step's mesh kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeats, CPU baseline, side measurements, roofline / per-kernel figures, detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if args.cpu_baseline_child:                      # child interpreter: CPU legs only, JSON on stdout
         print(json.dumps(cpu_baseline(args.cpu_budget)), flush=True)
@@ -861,7 +995,7 @@ def main(argv=None):
             cpu = json.load(open(os.environ["MDQ_BENCH_CPU_JSON"]))
         except Exception as exc:  # noqa: BLE001
             sys.stderr.write(f"[bench] cannot read the parent's cpu baseline ({exc!r})\n")
-    elif int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline:
+    elif int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.full and not args.no_cpu_baseline:
         # in a child interpreter (started before this process touches the GPU): whatever the numpy / scipy / Qhull
         # heavy oracle run leaves behind in the process state was measured to slow the later learning loop by 30 %
         import subprocess
@@ -952,13 +1086,24 @@ def main(argv=None):
     gc.collect()
     gc.disable()            # no collector pause inside the timed regions
     keep = []
-    s3 = measure_env_steps(args, dev, dist, world, 1, steps=args.steps, warmup=args.warmup, repeats=args.repeats, keep=keep)
-    smk = measure_smooth_kernel(dev, keep[0])
+    outputs = {} if args.dump_outputs and rank == 0 else None
+    s3 = measure_env_steps(args, dev, dist, world, 1, steps=args.steps, warmup=args.warmup, repeats=args.repeats, keep=keep,
+                           outputs=outputs)
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
+    smk = measure_smooth_kernel(dev, keep[0]) if args.full else None
     del keep
     gc.enable()
+    z = np.load(os.path.join(ROOT, "tests", "golden", f"{args.mesh}.npz"))
+    if not args.full:           # a plain run: the headline only
+        line = None
+        if rank == 0:
+            res = headline_result(args, s3, world, rccl, z["coords"].shape[0], z["cells"].shape[0])
+            sys.stderr.write(_detail_digest(res) + "\n")
+            line = json.dumps(compact_line(res, None))
+        return _finish(dist, rank, line, real_stdout)
 
     # ---------------- S2 on the BASELINE configuration (128 identical meshes, developed flow)
-    z = np.load(os.path.join(ROOT, "tests", "golden", f"{args.mesh}.npz"))
     topo = MeshTopology(z["coords"], z["cells"])
     x = smooth_coords(topo, 50)
     B = args.envs
@@ -1115,6 +1260,7 @@ def main(argv=None):
         except Exception as exc:  # noqa: BLE001
             cfgs["C5_s2_refined_mesh"] = _err(exc)
 
+    line = None
     if rank == 0:
         def prof(name, key):
             fp = os.path.join(ROOT, "profiles", name)
@@ -1132,59 +1278,11 @@ def main(argv=None):
         s3_gbs = s3_step_bytes / (s3["ms_per_batched_step"] * 1e-3) / 1e9
         vel_gbs = vel_bytes / (k_vel * 1e-3) / 1e9
         vel_traffic = prof("traffic.json", "velocity_kernel_hbm_bytes_per_launch")
-        res = {
-            "metric": "env steps/sec (ys930 ~2k-tri)",
-            "value": s3["value"],
-            "unit": "env steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": s3["ms_per_batched_step"],
-            # period of a batched step inside the rollouts (HIP events; ms_per_step also pays the fill and the drain of the
-            # two-stream pipeline and the one read-back per rollout: K = --steps batched steps per rollout)
-            "steady_state_ms_per_step": s3.get("steady_state_ms_per_step"),
-            "repeats": args.repeats,
-            "value_min": s3["value_min"],
-            "value_max": s3["value_max"],
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "s3_env_steps_per_s": s3["value"],
+        res = headline_result(args, s3, world, rccl, nv, nt)
+        res.update({
             "s1_env_steps_per_s": None if s1 is None else s1["value"],
             "s2_ipcs_env_steps_per_s": s2["value"],
             "training_env_steps_per_s": None if tr is None else tr["value"],
-            "collective_backend": rccl,          # backend, RCCL version, ranks (None for a single rank)
-            "stream_setup": _stream_log(),       # rank 0: how the main / flow / optimiser streams were chosen
-            "config": {
-                "workload_short": f"{args.mesh} ({nv} vertices / {nt} triangles), {B} envs per GPU, S3 env step (remesh+smooth+interp+"
-                                  f"forces+state+1 IPCS step+Q-fwd)",
-                "mesh": args.mesh,
-                "workload": f"{args.mesh} ({nv} vertices / {nt} triangles), {B} batched envs per GPU, step = S3 (north-star env "
-                            f"step): remove vertex + Delaunay restoration + smooth(50) + 5-snapshot interpolation + 10 force "
-                            f"integrals + state graph + ONE IPCS step on every coarsened mesh (matrix-free, Jacobi-BiCGStab / "
-                            f"CG, rtol {args.rtol:g}, warm start = interpolated last snapshot"
-                            + ("" if args.no_flow_overlap else "; it runs on a second stream beside the NEXT step's removal / "
-                               "smoothing / topology kernels, its drag / lift are delivered one step later")
-                            + ") + fused Q-network forward"
-                            + ("" if args.host_step else "; action selection / decoding, reward / terminal logic and in-place "
-                               "resets are kernels too (rollout_device: no host round trip inside a step)") + "; "
-                            f"epsilon = 0.5 actions from default_rng(1370 + ...), meshes diverge (vertices "
-                            f"{s3['vertices_min_max'][0]}..{s3['vertices_min_max'][1]} at the end), terminated envs reset in place",
-                "envs_per_gpu": B, "rtol": args.rtol, "dt": 1e-3, "mu": 1e-3, "rho": 1.0,
-                "numerics": {
-                    "ipcs": "mode 3: operator results accumulated with LDS fp64 atomics => reproducible to round-off only; run-to-run "
-                            "spread of drag / lift after 5000 steps 1e-8 .. 1.6e-6 relative (tools/traj_spread.py), inside the 1e-4 "
-                            "contract (5000-step values within 1e-5 of the FEniCS CSV rows, tests/test_golden_gpu.py); the correction "
-                            "solve starts fused on 15 of 16 steps and takes the |b| of its stopping test from the last exact start",
-                    "bitwise_reproducible": "vertex removal / Delaunay restoration, smoothing, topology / N-closest / state graph, "
-                                            "fused Q-forward, learning-step gradient (per-graph slices reduced in graph order)"},
-                "krylov_iters_per_ipcs_step": s3["krylov_iters_per_ipcs_step"],
-                "parallelism": f"dp{world} (independent envs sharded, no data-path collective)",
-                "collective_backend": rccl,
-                "reference_published": "45.8 IPCS steps/s for 1 env (FEniCS, unknown hardware; BASELINE.md) - context only",
-            },
             "roofline": {"bound": "hbm", "achieved": sm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": sm_gbs / HBM_PEAK_GBS,
                          "traffic": sm_traffic,
                          "kernel": "smooth_linear_kernel (DOLFIN smooth(50) as blocked triangular solves: 32-row block inverses built "
@@ -1229,7 +1327,7 @@ def main(argv=None):
                               "frac": vel_flops / (k_vel * 1e-3) / 1e12 / (78.6 * min(B, 256) / 256.0)},
                 "note": "matrix-free: operators are re-derived per triangle from 64 B of metadata, Krylov vectors live in "
                         "LDS/registers; one workgroup (one CU) per environment: 128 of 256 CUs at the BASELINE configuration"},
-        }
+        })
         res["kernel_scratch"] = _kernel_scratch()
         res["rates"] = {"S3_north_star_step": s3, "S1_reference_step": s1, "S2_ipcs_step": s2, "S2_full_chip": full,
                         "training_loop": tr, **cfgs}
@@ -1244,11 +1342,7 @@ def main(argv=None):
         sys.stderr.write(_detail_digest(res) + "\n")
         line = json.dumps(compact_line(res, detail_path))
         assert len(line) <= LINE_LIMIT, len(line)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:               # the LAST thing this process writes to stdout
-        print(line, file=real_stdout, flush=True)
+    return _finish(dist, rank, line, real_stdout)
 
 
 if __name__ == "__main__":

@@ -2,7 +2,8 @@
 the rank processes) and by torchrun (the driver's form).  The two-rank cases share cuda:0 between the ranks
 (MDQ_SHARE_GPU=1) over gloo, because RCCL refuses two ranks on one device: they exercise the multi-rank control flow
 (rank-0 build, barriers, max-over-ranks timing, sharded envs, the gradient all-reduce and the record all-gather of the
-learning loop), not RCCL itself."""
+learning loop), not RCCL itself.  These runs take `--full` (side measurements, roofline, CPU baseline, detail file); the last
+test checks a plain run (the headline only) and `--dump-outputs`."""
 import json
 import os
 import subprocess
@@ -12,7 +13,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "6", "--warmup", "2", "--repeats", "3", "--spinup", "60", "--s2-steps", "20", "--envs", "16",
+SMALL = ["--full", "--steps", "6", "--warmup", "2", "--repeats", "3", "--spinup", "60", "--s2-steps", "20", "--envs", "16",
          "--s1-steps", "4", "--s1-warmup", "3", "--train-steps", "3", "--s1-solver-steps", "200"]
 LINE_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
              "vs_baseline", "dtype", "data", "config", "roofline", "rates", "repeats", "value_min", "value_max",
@@ -149,7 +150,7 @@ def test_bench_one_rank_through_rccl(lib_built):
     assert res["value"] > 0 and abs(res["value"] - 16 * 6 / (res["ms_per_step"] * 6e-3)) < 1e-6 * res["value"]
 
 
-TINY = ["--steps", "3", "--warmup", "1", "--repeats", "2", "--spinup", "20", "--s2-steps", "10", "--envs", "4",
+TINY = ["--full", "--steps", "3", "--warmup", "1", "--repeats", "2", "--spinup", "20", "--s2-steps", "10", "--envs", "4",
         "--s1-steps", "0", "--train-steps", "0", "--s1-solver-steps", "100", "--no-cpu-baseline"]
 
 
@@ -190,3 +191,32 @@ def test_bench_launcher_tears_down_when_a_rank_dies(lib_built, tmp_path):
     assert out.returncode == 1 and took < 150, (out.returncode, took, out.stderr[-2000:])   # (8 x `import torch` on a cold box)
     assert "rank 3 of 8 exited with code 3" in out.stderr and "failure injected by the test" in out.stderr
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_outputs(lib_built, tmp_path):
+    """A plain run (no --full): exactly --steps timed steps, the headline keys only (no side measurement, no detail file), and
+    --dump-outputs writes what the last timed step computed, one row per environment."""
+    import numpy as np
+    out_dir, detail = tmp_path / "outputs", tmp_path / "detail.json"
+    cmd = [sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--envs", "16", "--s1-warmup", "3", "--s1-solver-steps", "200",
+           "--dump-outputs", str(out_dir)]
+    out = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, MDQ_BENCH_DETAIL=str(detail)), capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and out.stdout.rstrip("\n").endswith(lines[0]), out.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"} <= set(line)
+    assert not {"roofline", "rates", "cpu_baseline", "detail"} & set(line) and not detail.exists()
+    assert line["steps"] == 6 and line["warmup"] == 2 and line["repeats"] == 1 and line["higher_is_better"] is True
+    assert line["unit"] == "env steps/s" and line["dtype"] == "f64" and line["n_gpus"] == 1
+    assert line["value"] > 0 and abs(line["value"] - 16 * 6 / (line["ms_per_step"] * 6e-3)) < 1e-5 * line["value"]
+    names = {"rewards", "dones", "actions", "codes", "nv", "drag", "lift", "flow_drag", "flow_lift", "mesh_nv", "coords", "state_x"}
+    assert {p.name for p in out_dir.iterdir()} == {n + ".npy" for n in names}
+    arrs = {n: np.load(out_dir / f"{n}.npy") for n in names}
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    for n, a in arrs.items():
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == 16 and np.isfinite(a).all(), n
+    nv, mesh_nv = arrs["nv"].astype(int), arrs["mesh_nv"].astype(int)
+    assert ((nv > 0) & (nv <= arrs["coords"].shape[1])).all() and (arrs["actions"] >= 0).all() and (arrs["actions"] <= 180).all()
+    assert ((mesh_nv > 0) & (mesh_nv <= arrs["coords"].shape[1])).all()
+    assert all(not arrs["coords"][b, mesh_nv[b]:].any() and arrs["coords"][b, :mesh_nv[b]].any() for b in range(16))

@@ -74,3 +74,36 @@ def test_resource_table_is_tied_to_the_library(tmp_path):
     other.write_bytes(b"not the library")
     with pytest.raises(RuntimeError, match="does not describe"):
         b.library_resources(str(other))
+
+
+def test_plain_run_line_is_the_headline():
+    """A plain run (no --full) reports the headline keys only and writes no detail file."""
+    res = _full_result()
+    for k in ("roofline", "rates", "cpu_baseline"):
+        res.pop(k)
+    line = bench.compact_line(res, None)
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"} <= set(line)
+    assert not {"roofline", "rates", "cpu_baseline", "detail"} & set(line)
+    assert line["value"] == float(f"{res['value']:.6g}") and line["ms_per_step"] == float(f"{res['ms_per_step']:.6g}")
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 kept, everything else float64, at most 64 MB in all."""
+    import numpy as np
+    import pytest
+    out = {"actions": np.arange(4, dtype=np.int32), "state_x": np.ones((2, 3), np.float32), "rewards": np.linspace(0, 1, 3)}
+    assert bench.write_outputs(str(tmp_path / "d"), out) == ["actions", "rewards", "state_x"]
+    got = {k: np.load(tmp_path / "d" / f"{k}.npy") for k in out}
+    assert got["actions"].dtype == np.float64 and got["rewards"].dtype == np.float64 and got["state_x"].dtype == np.float32
+    assert all(np.array_equal(got[k], out[k]) for k in out)
+    with pytest.raises(ValueError, match="more than"):
+        bench.write_outputs(str(tmp_path / "e"), {"big": np.zeros(bench.OUTPUTS_LIMIT // 8 + 1)})
+    assert not (tmp_path / "e").exists()
+
+
+def test_full_and_dump_outputs_options(capsys):
+    import pytest
+    with pytest.raises(SystemExit):
+        bench.main(["--help"])
+    txt = capsys.readouterr().out
+    assert "--full" in txt and "--dump-outputs" in txt

@@ -2,11 +2,12 @@
 # HBM traffic of evolve_kernel from PMC counters (separate passes, no tracing domains), on the GPU box:
 #   tools/pmc_traffic.sh <outdir-under-gpurun_out> [bench args...]
 set -u
+R=$(cd "$(dirname "$0")/.." && pwd)    # the repository
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1; shift
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --output-format csv -d $OUT/$C -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline "$@" > $OUT/$C.log 2>&1
+  rocprofv3 --pmc $C --output-format csv -d $OUT/$C -- python3 $R/bench.py --full --no-cpu-baseline "$@" > $OUT/$C.log 2>&1
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, json

@@ -6,10 +6,10 @@ TAG=${1:-fin}
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
-cd $R && python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+cd $R && python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s2 -- python3 $R/bench.py --no-cpu-baseline --s1-steps 0 > $OUT/s2.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/full -- python3 $R/bench.py --no-cpu-baseline > $OUT/full.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s2 -- python3 $R/bench.py --full --no-cpu-baseline --s1-steps 0 > $OUT/s2.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/full -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/full.log 2>&1
 cd $R
 bash tools/pmc_traffic.sh $TAG/pmc --s1-steps 0 > $OUT/pmc.log 2>&1
 bash tools/pmc_sq.sh $TAG/sq > $OUT/sq.log 2>&1

@@ -6,13 +6,13 @@ TAG=${1:-r02}
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
-cd $R && python3 bench.py > $OUT/r02_bench.json 2> $OUT/bench.err
+cd $R && python3 bench.py --full > $OUT/r02_bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 ARGS="--no-cpu-baseline --train-steps 0 --no-configs"
 # (the kernel trace includes the learning loops: gcn_train_kernel, replay / Adam kernels)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $R/bench.py --no-cpu-baseline --no-configs > $OUT/r02_bench_profiled.json 2> $OUT/kt.log
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $R/bench.py --full --no-cpu-baseline --no-configs > $OUT/r02_bench_profiled.json 2> $OUT/kt.log
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/$C -- python3 $R/bench.py $ARGS --s1-steps 0 --s2-steps 20 --spinup 20 --repeats 2 > $OUT/$C.log 2>&1
+  timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/$C -- python3 $R/bench.py --full $ARGS --s1-steps 0 --s2-steps 20 --spinup 20 --repeats 2 > $OUT/$C.log 2>&1
 done
 cd $R
 python3 - "$OUT" <<'PY'

@@ -9,15 +9,15 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 if [ -z "$QUICK" ]; then
-  cd $R && python3 bench.py > $OUT/r05_bench.json 2> $OUT/bench.err
+  cd $R && python3 bench.py --full > $OUT/r05_bench.json 2> $OUT/bench.err
 fi
 cd /tmp && export TMPDIR=/tmp
 # kernel trace of the bench command (headline S3 rollouts + S1 + learning loops; C2 / C3 / C5 / deploy side measurements too)
-timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $R/bench.py --no-cpu-baseline > $OUT/r05_bench_profiled.json 2> $OUT/kt.log
+timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/r05_bench_profiled.json 2> $OUT/kt.log
 if [ -z "$QUICK" ]; then
   # HBM traffic of the dominant kernels (separate --pmc passes, kernel trace off): the S3 rollout only, then C5 only
   for C in FETCH_SIZE WRITE_SIZE; do
-    timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/$C -- python3 $R/bench.py --no-cpu-baseline --train-steps 0 --no-configs --s1-steps 0 --s2-steps 20 --spinup 20 --repeats 2 > $OUT/$C.log 2>&1
+    timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/$C -- python3 $R/bench.py --full --no-cpu-baseline --train-steps 0 --no-configs --s1-steps 0 --s2-steps 20 --spinup 20 --repeats 2 > $OUT/$C.log 2>&1
     timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/C5_$C -- python3 $R/tools/time_c5.py pmc > $OUT/C5_$C.log 2>&1
   done
 fi

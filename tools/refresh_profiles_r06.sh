@@ -10,16 +10,16 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 if [ -z "$QUICK" ]; then
   # (the stdout line is the contract line; the full result - prose, side tables, per-repeat times - is the detail file)
-  cd $R && MDQ_BENCH_DETAIL=$OUT/r06_bench_detail.json python3 bench.py > $OUT/r06_bench.json 2> $OUT/bench.err
+  cd $R && MDQ_BENCH_DETAIL=$OUT/r06_bench_detail.json python3 bench.py --full > $OUT/r06_bench.json 2> $OUT/bench.err
 fi
 cd /tmp && export TMPDIR=/tmp
 export MDQ_BENCH_DETAIL=$OUT/scratch_detail.json      # (the profiled runs' detail files are not kept)
 # kernel trace of the bench command (headline S3 rollouts + S1 + learning loops; C2 / C3 / C5 / deploy side measurements too)
-timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $R/bench.py --no-cpu-baseline > $OUT/r06_bench_profiled.json 2> $OUT/kt.log
+timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/r06_bench_profiled.json 2> $OUT/kt.log
 if [ -z "$QUICK" ]; then
   # HBM traffic of the dominant kernels (separate --pmc passes, kernel trace off): the S3 rollout only, then C5 only
   for C in FETCH_SIZE WRITE_SIZE; do
-    timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/$C -- python3 $R/bench.py --no-cpu-baseline --train-steps 0 --no-configs --s1-steps 0 --s2-steps 20 --spinup 20 --repeats 2 > $OUT/$C.log 2>&1
+    timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/$C -- python3 $R/bench.py --full --no-cpu-baseline --train-steps 0 --no-configs --s1-steps 0 --s2-steps 20 --spinup 20 --repeats 2 > $OUT/$C.log 2>&1
     timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/C5_$C -- python3 $R/tools/time_c5.py pmc > $OUT/C5_$C.log 2>&1
   done
 fi
