@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define MDQ_ABI_VERSION 7
+#define MDQ_ABI_VERSION 8
 
 /* The library is built with -fvisibility=hidden: the entry points below are its ONLY exported symbols. */
 #if defined(__GNUC__)
@@ -485,6 +485,23 @@ MDQ_API int mdq_stream_create_cu_mask(const uint32_t* mask, int32_t nwords, void
 MDQ_API int mdq_stream_destroy(void* stream);
 
 /* ---- snapshot interpolation onto coarsened meshes (Env2DAirfoil.py:556-593, :515-522) ---- */
+/* ABI 8: one source (original mesh + its snapshots + its location grid) of a batch that mixes several airfoils - the
+ * source fields of mdq_interp_desc in one record; a DEVICE array of these is mdq_interp_desc.srcs. */
+typedef struct mdq_interp_src {
+  int32_t src_nv, src_nt, src_n2;
+  int32_t gnx, gny;
+  int32_t _pad;
+  double x0, y0, inv_hx, inv_hy;
+  const double* src_coords;     /* [src_nv][2]       (device, as in mdq_interp_desc) */
+  const int32_t* src_cell_dofs; /* [6][src_nt]                                     */
+  const double* src_geom;       /* [5][src_nt]                                     */
+  const int32_t* bin_ptr;       /* [gnx*gny+1]                                     */
+  const int32_t* bin_cells;
+  const double* src_u;          /* [S][src_n2][2]                                  */
+  const double* src_p;          /* [S][src_nv]                                     */
+  const double* src_cellrec;    /* [src_nt][6] or NULL                             */
+} mdq_interp_src;
+
 typedef struct mdq_interp_desc {
   int32_t B, S;            /* target meshes (environments), snapshots                         */
   int32_t NP, NP1;         /* capacities: target P2 points (vertices then edge midpoints), P1 points (vertices) */
@@ -525,6 +542,12 @@ typedef struct mdq_interp_desc {
   const int32_t* cell_dofs;     /* device [B][6][NT] dof ids of the target meshes              */
   int32_t NT, NAF;
   int32_t sparse, _pad2;
+  /* optional (ABI 8): per-environment sources of a batch over n_src airfoils.  srcs (device [n_src]) and src_of_env
+   * (device [B], values in [0, n_src)) both set: environment b is interpolated from srcs[src_of_env[b]] and the source
+   * fields above (src_nv .. src_p, src_cellrec, the grid) are ignored; both NULL: the one shared source above. */
+  int32_t n_src, _pad3;
+  const int32_t* src_of_env;
+  const mdq_interp_src* srcs;
 } mdq_interp_desc;
 
 /*
@@ -669,6 +692,13 @@ typedef struct {
                                   left at zero by every launch: the rows among dst[] that ARE nv / nsel - inputs of the
                                   terminal decision every workgroup of the environment takes - are restored by the last
                                   workgroup to have read them.  NULL: one workgroup per environment */
+  /* optional (ABI 8), a batch over several airfoils: src_of_env (device [B]) = the airfoil a of environment b.  Set, it
+   * switches the fields of the one shared source to per-airfoil tables: gt_drag is [A][S], x_init [A][N][2 + 3 S],
+   * nv0_of (device [A], required) replaces nv0, and the cached initial row of row array t for environment b is
+   * src[t] + a * src_stride[t] bytes (0: one row shared by every airfoil).  NULL: everything as above. */
+  const int32_t* src_of_env;
+  const int32_t* nv0_of;
+  int64_t src_stride[MDQ_FINISH_MAX_ROWS];
 } mdq_env_finish_desc;
 MDQ_API int mdq_env_finish(const mdq_env_finish_desc* d, void* stream);
 
@@ -693,6 +723,18 @@ MDQ_API int mdq_edge_ptr(int32_t B, const int32_t* nedges, int32_t* edge_ptr, vo
  */
 MDQ_API int mdq_restore_rows(int32_t n, void* const* dst, const void* const* src, const int64_t* row_bytes, int32_t n_idx,
                      const int32_t* idx, void* stream);
+
+/*
+ * ABI 8: mdq_restore_rows / mdq_restore_rows_masked with one cached initial row PER AIRFOIL: row b of dst[t] is
+ * overwritten with src[t] + src_of_env[b] * src_stride[t] bytes (src_stride: host array, multiples of 4; 0 = one row shared
+ * by every airfoil); src_of_env: device [B] (B = rows of the destination tensors).
+ */
+MDQ_API int mdq_restore_rows_src(int32_t n, void* const* dst, const void* const* src, const int64_t* src_stride,
+                                 const int64_t* row_bytes, int32_t n_idx, const int32_t* idx, const int32_t* src_of_env,
+                                 void* stream);
+MDQ_API int mdq_restore_rows_masked_src(int32_t n, void* const* dst, const void* const* src, const int64_t* src_stride,
+                                        const int64_t* row_bytes, int32_t B, const uint8_t* mask, const int32_t* src_of_env,
+                                        void* stream);
 
 /*
  * DOLFIN `Mesh.smooth(n)` (flow_solver.py:65-67 and 236-237 after every remesh) for B meshes on the GPU: Gauss-Seidel
@@ -824,13 +866,20 @@ typedef struct mdq_env_topo_desc {
   void* workspace;          /* device, 16-byte aligned, >= mdq_env_topology_workspace_bytes(d) bytes: the tables of the
                                large-mesh kernel instance (NULL / 0 for meshes of up to 1024 vertices and for the host engine) */
   int64_t workspace_bytes;
+  /* optional (ABI 8), a batch over several airfoils: `polygon` holds the A polygons one after the other, poly_ptr [A+1]
+   * their first points, src_of_env [B] the airfoil of every environment (environment b measures its distances to points
+   * poly_ptr[a] .. poly_ptr[a+1] - 1, a = src_of_env[b]); npoly is then the largest of the A polygons.  Both NULL: the one
+   * polygon [npoly][2].  Device pointers for mdq_env_topology, host pointers for mdq_env_topology_host. */
+  const int32_t* poly_ptr;
+  const int32_t* src_of_env;
 } mdq_env_topo_desc;
 
 /*
  * Per environment: unique edges / P2 dof map / dof coordinates, boundary + airfoil facets, `removable`
  * (flow_solver.py:75-78 quirk), polygon distances + argsort + N-closest window (Env2DAirfoil.py:220-241,
  * 293-315) and the state graph edges (:258-280).  status[b] = 0 ok, <0 capacity exceeded
- * (-1 NP, -2 NAF, -3 EMAX, -4 more than 2 outflow rows per row-owner thread, -5 NBO/NBE, -6 NSE1).
+ * (-1 NP, -2 NAF, -3 EMAX, -4 more than 2 outflow rows per row-owner thread, -5 NBO/NBE, -6 NSE1, -7 the environment's
+ * polygon (poly_ptr) is empty or larger than npoly).
  */
 MDQ_API int mdq_env_topology_host(const mdq_env_topo_desc* d, int32_t nthreads, int32_t* status);
 

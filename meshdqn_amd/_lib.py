@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # (MDQ_LIB_PATH: a differently built copy of the library, e.g. an experiment of tools/: development knob)
 LIB_PATH = os.environ.get("MDQ_LIB_PATH") or os.path.join(HERE, "libmeshdqn_hip.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class MeshDQNHipError(RuntimeError):
@@ -69,6 +69,19 @@ class InterpDesc(C.Structure):
         ("npts_extra", C.c_void_p),
         ("af_facets", C.c_void_p), ("naf", C.c_void_p), ("cell_dofs", C.c_void_p),
         ("NT", C.c_int32), ("NAF", C.c_int32), ("sparse", C.c_int32), ("_pad2", C.c_int32),
+        ("n_src", C.c_int32), ("_pad3", C.c_int32), ("src_of_env", C.c_void_p), ("srcs", C.c_void_p),
+    ]
+
+
+class InterpSrc(C.Structure):
+    """Mirror of `mdq_interp_src` (ABI 8: one airfoil's source of a mixed batch)."""
+    _fields_ = [
+        ("src_nv", C.c_int32), ("src_nt", C.c_int32), ("src_n2", C.c_int32),
+        ("gnx", C.c_int32), ("gny", C.c_int32), ("_pad", C.c_int32),
+        ("x0", C.c_double), ("y0", C.c_double), ("inv_hx", C.c_double), ("inv_hy", C.c_double),
+        ("src_coords", C.c_void_p), ("src_cell_dofs", C.c_void_p), ("src_geom", C.c_void_p),
+        ("bin_ptr", C.c_void_p), ("bin_cells", C.c_void_p), ("src_u", C.c_void_p), ("src_p", C.c_void_p),
+        ("src_cellrec", C.c_void_p),
     ]
 
 
@@ -77,7 +90,8 @@ class EnvTopoDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "NV", "NT", "NP", "NAF", "N", "EMAX", "npoly")] + [
         (n, C.c_void_p) for n in ("coords", "cells", "nv", "nt", "offset", "polygon", "ne", "cell_dofs", "points", "naf",
                                   "af_facets", "nremovable", "nsel", "n_closest", "coord_map", "nedges", "edge_src",
-                                  "edge_dst", "edge_len", "ipcs", "handover", "workspace")] + [("workspace_bytes", C.c_int64)]
+                                  "edge_dst", "edge_len", "ipcs", "handover", "workspace")] + [("workspace_bytes", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("poly_ptr", "src_of_env")]
 
 
 class TopoHandover(C.Structure):
@@ -105,7 +119,8 @@ class EnvFinishDesc(C.Structure):
         ("dst", C.c_void_p * FINISH_MAX_ROWS), ("src", C.c_void_p * FINISH_MAX_ROWS),
         ("row_bytes", C.c_int64 * FINISH_MAX_ROWS), ("handover_dst", C.c_void_p * FINISH_MAX_ROWS),
         ("handover_off", C.c_int64 * FINISH_MAX_ROWS), ("handover_bytes", C.c_int64 * FINISH_MAX_ROWS)] + [
-        (n, C.c_void_p) for n in ("coords", "u", "p", "n_closest", "x_init", "x", "arrive")]
+        (n, C.c_void_p) for n in ("coords", "u", "p", "n_closest", "x_init", "x", "arrive")] + [
+        (n, C.c_void_p) for n in ("src_of_env", "nv0_of")] + [("src_stride", C.c_int64 * FINISH_MAX_ROWS)]
 
 
 # every symbol include/meshdqn_hip.h declares: name -> (restype, argtypes)
@@ -149,6 +164,10 @@ SYMBOLS = {
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32,
                                  C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mdq_restore_rows_masked": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mdq_restore_rows_src": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "mdq_restore_rows_masked_src": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
     "mdq_env_finish": (C.c_int, [C.POINTER(EnvFinishDesc), C.c_void_p]),
     "mdq_remesh_act": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
                        + [C.c_void_p] * 11 + [C.c_int64, C.c_void_p]),

@@ -725,8 +725,13 @@ static int topology_one(const mdq_env_topo_desc& D, int b) {
   D.nremovable[b] = nrem;
   // ---- N closest removable vertices to the airfoil polygon (argsort of the distances, window by offset)
   std::vector<double> dist(nrem);
-  const PolyAux aux(D.polygon, D.npoly);
-  for (int r = 0; r < nrem; ++r) dist[r] = polygon_distance(D.polygon, D.npoly, aux, x + 2 * removable[r]);
+  // (a batch over several airfoils: this environment's own polygon out of the concatenated ones)
+  const int p0 = D.poly_ptr ? D.poly_ptr[D.src_of_env[b]] : 0;
+  const int npoly = D.poly_ptr ? D.poly_ptr[D.src_of_env[b] + 1] - p0 : D.npoly;
+  const double* polyg = D.polygon + 2 * (size_t)p0;
+  if (npoly < 1 || npoly > D.npoly) return -7;
+  const PolyAux aux(polyg, npoly);
+  for (int r = 0; r < nrem; ++r) dist[r] = polygon_distance(polyg, npoly, aux, x + 2 * removable[r]);
   std::vector<int32_t> order(nrem);
   for (int r = 0; r < nrem; ++r) order[r] = r;
   std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return dist[a] < dist[c]; });
@@ -772,6 +777,8 @@ static int topology_one(const mdq_env_topo_desc& D, int b) {
 
 extern "C" int mdq_env_topology_host(const mdq_env_topo_desc* d, int32_t nthreads, int32_t* status) {
   if (!d || d->B <= 0 || !status) return mdq_set_error("mdq_env_topology_host: bad arguments");
+  if ((d->poly_ptr == nullptr) != (d->src_of_env == nullptr))
+    return mdq_set_error("mdq_env_topology_host: poly_ptr and src_of_env go together");
   const mdq_env_topo_desc D = *d;
   int T = nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency();
   if (T < 1) T = 1;

@@ -14,6 +14,30 @@ namespace mdq_mesh {
 // snapshots with the P2 / P1 bases of that cell.
 __global__ __launch_bounds__(256) void interpolate_kernel(mdq_interp_desc d) {
   const int b = blockIdx.y;
+  // the source of this environment (workgroup-uniform): the descriptor's own fields, or - a batch over several airfoils -
+  // the record of its airfoil
+  mdq_interp_src src;
+  if (d.srcs) {
+    src = d.srcs[__builtin_amdgcn_readfirstlane(d.src_of_env[b])];
+  } else {
+    src.src_nv = d.src_nv;
+    src.src_nt = d.src_nt;
+    src.src_n2 = d.src_n2;
+    src.gnx = d.gnx;
+    src.gny = d.gny;
+    src.x0 = d.x0;
+    src.y0 = d.y0;
+    src.inv_hx = d.inv_hx;
+    src.inv_hy = d.inv_hy;
+    src.src_coords = d.src_coords;
+    src.src_cell_dofs = d.src_cell_dofs;
+    src.src_geom = d.src_geom;
+    src.bin_ptr = d.bin_ptr;
+    src.bin_cells = d.bin_cells;
+    src.src_u = d.src_u;
+    src.src_p = d.src_p;
+    src.src_cellrec = d.src_cellrec;
+  }
   const int npts = d.npts[b] + (d.npts_extra ? d.npts_extra[b] : 0);
   const int np1 = d.np1[b];
   const int64_t B = b;
@@ -38,27 +62,27 @@ __global__ __launch_bounds__(256) void interpolate_kernel(mdq_interp_desc d) {
       s_lo = d.S - 1;
     }
     const double px = pts[2 * k], py = pts[2 * k + 1];
-    int gx = (int)floor((px - d.x0) * d.inv_hx), gy = (int)floor((py - d.y0) * d.inv_hy);
-    gx = gx < 0 ? 0 : (gx >= d.gnx ? d.gnx - 1 : gx);
-    gy = gy < 0 ? 0 : (gy >= d.gny ? d.gny - 1 : gy);
-    const int bin = gy * d.gnx + gx;
+    int gx = (int)floor((px - src.x0) * src.inv_hx), gy = (int)floor((py - src.y0) * src.inv_hy);
+    gx = gx < 0 ? 0 : (gx >= src.gnx ? src.gnx - 1 : gx);
+    gy = gy < 0 ? 0 : (gy >= src.gny ? src.gny - 1 : gy);
+    const int bin = gy * src.gnx + gx;
     int best = -1;
     double bxi = 0.0, beta = 0.0, bviol = -1e300;
-    if (d.src_cellrec) {
+    if (src.src_cellrec) {
       // candidates in batches of CB: their ids in one round trip, their records (vertex 0 + Jinv, 48 bytes) in a second
       // one, then the same tests in the same order.  (Cell by cell - id, then its dofs, then the vertex - a point paid
       // three dependent L2 round trips per candidate: the whole kernel was the latency of its longest candidate list.)
       constexpr int CB = 6;
-      const int s0 = d.bin_ptr[bin], s1 = d.bin_ptr[bin + 1];
+      const int s0 = src.bin_ptr[bin], s1 = src.bin_ptr[bin + 1];
       bool found = false;
       for (int sb = s0; sb < s1 && !found; sb += CB) {
         int cid[CB];
 #pragma unroll
-        for (int q = 0; q < CB; ++q) cid[q] = d.bin_cells[min(sb + q, s1 - 1)];
+        for (int q = 0; q < CB; ++q) cid[q] = src.bin_cells[min(sb + q, s1 - 1)];
         double2 r0[CB], r1[CB], r2[CB];
 #pragma unroll
         for (int q = 0; q < CB; ++q) {
-          const double2* rp = reinterpret_cast<const double2*>(d.src_cellrec + (int64_t)cid[q] * 6);
+          const double2* rp = reinterpret_cast<const double2*>(src.src_cellrec + (int64_t)cid[q] * 6);
           r0[q] = rp[0];
           r1[q] = rp[1];
           r2[q] = rp[2];
@@ -82,12 +106,12 @@ __global__ __launch_bounds__(256) void interpolate_kernel(mdq_interp_desc d) {
         }
       }
     } else
-    for (int s = d.bin_ptr[bin]; s < d.bin_ptr[bin + 1]; ++s) {
-      const int c = d.bin_cells[s];
-      const int v0 = d.src_cell_dofs[0 * d.src_nt + c];
-      const double dx = px - d.src_coords[2 * v0], dy = py - d.src_coords[2 * v0 + 1];
-      const double j00 = d.src_geom[0 * d.src_nt + c], j01 = d.src_geom[1 * d.src_nt + c];
-      const double j10 = d.src_geom[2 * d.src_nt + c], j11 = d.src_geom[3 * d.src_nt + c];
+    for (int s = src.bin_ptr[bin]; s < src.bin_ptr[bin + 1]; ++s) {
+      const int c = src.bin_cells[s];
+      const int v0 = src.src_cell_dofs[0 * src.src_nt + c];
+      const double dx = px - src.src_coords[2 * v0], dy = py - src.src_coords[2 * v0 + 1];
+      const double j00 = src.src_geom[0 * src.src_nt + c], j01 = src.src_geom[1 * src.src_nt + c];
+      const double j10 = src.src_geom[2 * src.src_nt + c], j11 = src.src_geom[3 * src.src_nt + c];
       // reference coordinates: [xi, eta] = J^-1 (x - x0); geom stores Jinv[c][a] (reference row, physical col)
       const double xi = j00 * dx + j01 * dy, eta = j10 * dx + j11 * dy;
       const double l0 = 1.0 - xi - eta;
@@ -111,9 +135,9 @@ __global__ __launch_bounds__(256) void interpolate_kernel(mdq_interp_desc d) {
     phi[5] = 4.0 * l0 * l1;
     int dof[6];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) dof[i] = d.src_cell_dofs[i * d.src_nt + best];
+    for (int i = 0; i < 6; ++i) dof[i] = src.src_cell_dofs[i * src.src_nt + best];
     for (int s = s_lo; s < s_hi; ++s) {
-      const double* us = d.src_u + (int64_t)s * d.src_n2 * 2;
+      const double* us = src.src_u + (int64_t)s * src.src_n2 * 2;
       double ux = 0.0, uy = 0.0;
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
@@ -124,7 +148,7 @@ __global__ __launch_bounds__(256) void interpolate_kernel(mdq_interp_desc d) {
       uo[0] = ux;
       uo[1] = uy;
       if (k < np1) {
-        const double* ps = d.src_p + (int64_t)s * d.src_nv;
+        const double* ps = src.src_p + (int64_t)s * src.src_nv;
         d.out_p[(B * d.S + s) * d.NP1 + k] = ps[dof[0]] * l0 + ps[dof[1]] * l1 + ps[dof[2]] * l2;
       }
     }
@@ -142,6 +166,8 @@ extern "C" int mdq_interpolate_snapshots(const mdq_interp_desc* d, void* stream)
       return mdq_set_error("mdq_interpolate_snapshots: sparse mode needs af_facets, naf, cell_dofs, NT, NAF");
     bx += (3 * d->NAF + 255) / 256;
   }
+  if ((d->srcs == nullptr) != (d->src_of_env == nullptr) || (d->srcs && d->n_src <= 0))
+    return mdq_set_error("mdq_interpolate_snapshots: srcs and src_of_env go together (n_src > 0)");
   hipLaunchKernelGGL(mdq_mesh::interpolate_kernel, dim3(bx, d->B), dim3(256), 0, (hipStream_t)stream, *d);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mdq_set_error(hipGetErrorString(e));
@@ -233,6 +259,88 @@ extern "C" int mdq_restore_rows(int32_t n, void* const* dst, const void* const* 
   const int chunks = (int)((wmax + mdq_mesh::RESTORE_CHUNK - 1) / mdq_mesh::RESTORE_CHUNK);
   hipLaunchKernelGGL(mdq_mesh::restore_rows_kernel, dim3(n_idx, n, chunks), dim3(256), 0, (hipStream_t)stream, a, idx);
   if (hipGetLastError() != hipSuccess) return mdq_set_error("restore_rows_kernel launch failed");
+  return 0;
+}
+
+namespace mdq_mesh {
+// ABI 8: the restores with one cached row per airfoil - row b's source is src[t] + src_of_env[b] * stride[t] words
+struct RestoreSrc {
+  int64_t stride[RESTORE_MAX];   // words
+  const int32_t* src_of_env;
+};
+__device__ __forceinline__ void restore_one_row(const RestoreArgs& a, const RestoreSrc& r, int t, int64_t row) {
+  const int64_t n = a.words[t];
+  const int64_t w0 = (int64_t)blockIdx.z * RESTORE_CHUNK;
+  if (w0 >= n) return;
+  const int64_t w1 = w0 + RESTORE_CHUNK < n ? w0 + RESTORE_CHUNK : n;
+  uint32_t* d = a.dst[t] + row * n;
+  const uint32_t* s = a.src[t] + (int64_t)__builtin_amdgcn_readfirstlane(r.src_of_env[row]) * r.stride[t];
+  if ((n & 3) == 0 && ((reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(s)) & 15) == 0) {
+    uint4* d4 = reinterpret_cast<uint4*>(d);
+    const uint4* s4 = reinterpret_cast<const uint4*>(s);
+    for (int64_t i = (w0 >> 2) + threadIdx.x; i < (w1 >> 2); i += 256) d4[i] = s4[i];
+  } else {
+    for (int64_t i = w0 + threadIdx.x; i < w1; i += 256) d[i] = s[i];
+  }
+}
+__global__ __launch_bounds__(256) void restore_rows_src_kernel(RestoreArgs a, RestoreSrc r, const int32_t* idx) {
+  restore_one_row(a, r, blockIdx.y, idx[blockIdx.x]);
+}
+__global__ __launch_bounds__(256) void restore_rows_masked_src_kernel(RestoreArgs a, RestoreSrc r, const uint8_t* mask) {
+  if (!mask[blockIdx.x]) return;
+  restore_one_row(a, r, blockIdx.y, blockIdx.x);
+}
+
+// host side of both: the argument checks of mdq_restore_rows + the strides
+static int restore_src_args(const char* what, int32_t n, void* const* dst, const void* const* src, const int64_t* src_stride,
+                            const int64_t* row_bytes, const int32_t* src_of_env, RestoreArgs& a, RestoreSrc& r, int& chunks) {
+  if (n <= 0 || n > RESTORE_MAX || !dst || !src || !src_stride || !row_bytes || !src_of_env)
+    return mdq_set_error(what);
+  int64_t wmax = 0;
+  for (int t = 0; t < n; ++t) {
+    if (!dst[t] || !src[t] || row_bytes[t] <= 0 || (row_bytes[t] & 3) || ((uintptr_t)dst[t] & 3) || ((uintptr_t)src[t] & 3) ||
+        src_stride[t] < 0 || (src_stride[t] & 3))
+      return mdq_set_error(what);
+    a.dst[t] = static_cast<uint32_t*>(dst[t]);
+    a.src[t] = static_cast<const uint32_t*>(src[t]);
+    a.words[t] = row_bytes[t] / 4;
+    r.stride[t] = src_stride[t] / 4;
+    wmax = a.words[t] > wmax ? a.words[t] : wmax;
+  }
+  r.src_of_env = src_of_env;
+  chunks = (int)((wmax + RESTORE_CHUNK - 1) / RESTORE_CHUNK);
+  return 0;
+}
+}  // namespace mdq_mesh
+
+extern "C" int mdq_restore_rows_src(int32_t n, void* const* dst, const void* const* src, const int64_t* src_stride,
+                                    const int64_t* row_bytes, int32_t n_idx, const int32_t* idx, const int32_t* src_of_env,
+                                    void* stream) {
+  mdq_mesh::RestoreArgs a;
+  mdq_mesh::RestoreSrc r;
+  int chunks = 0;
+  if (n_idx < 0 || (n_idx > 0 && !idx)) return mdq_set_error("mdq_restore_rows_src: bad index list");
+  if (mdq_mesh::restore_src_args("mdq_restore_rows_src: bad arguments (at most 16 tensors; rows, strides and pointers multiples "
+                                 "of 4 bytes)", n, dst, src, src_stride, row_bytes, src_of_env, a, r, chunks))
+    return -1;
+  if (n_idx == 0) return 0;
+  hipLaunchKernelGGL(mdq_mesh::restore_rows_src_kernel, dim3(n_idx, n, chunks), dim3(256), 0, (hipStream_t)stream, a, r, idx);
+  if (hipGetLastError() != hipSuccess) return mdq_set_error("restore_rows_src_kernel launch failed");
+  return 0;
+}
+
+extern "C" int mdq_restore_rows_masked_src(int32_t n, void* const* dst, const void* const* src, const int64_t* src_stride,
+                                           const int64_t* row_bytes, int32_t B, const uint8_t* mask, const int32_t* src_of_env,
+                                           void* stream) {
+  mdq_mesh::RestoreArgs a;
+  mdq_mesh::RestoreSrc r;
+  int chunks = 0;
+  if (B <= 0 || !mask) return mdq_set_error("mdq_restore_rows_masked_src: bad mask");
+  if (mdq_mesh::restore_src_args("mdq_restore_rows_masked_src: bad arguments (at most 16 tensors; rows, strides and pointers "
+                                 "multiples of 4 bytes)", n, dst, src, src_stride, row_bytes, src_of_env, a, r, chunks))
+    return -1;
+  hipLaunchKernelGGL(mdq_mesh::restore_rows_masked_src_kernel, dim3(B, n, chunks), dim3(256), 0, (hipStream_t)stream, a, r, mask);
+  if (hipGetLastError() != hipSuccess) return mdq_set_error("restore_rows_masked_src_kernel launch failed");
   return 0;
 }
 
@@ -531,6 +639,11 @@ namespace mdq_mesh {
 // puts the counter back to zero - no workgroup waits for another.
 __global__ __launch_bounds__(256) void env_finish_kernel(mdq_env_finish_desc d) {
   const int b = blockIdx.x, y = blockIdx.y, Y = gridDim.y, tid = threadIdx.x;
+  // airfoil of this environment (a batch over several airfoils; workgroup-uniform): its ground truth, initial vertex count,
+  // cached initial rows and features
+  const int a = d.src_of_env ? __builtin_amdgcn_readfirstlane(d.src_of_env[b]) : 0;
+  const double* gt_drag = d.gt_drag + (int64_t)a * d.S;
+  const int nv0 = d.src_of_env ? d.nv0_of[a] : d.nv0;
   __shared__ int s_reset;
   if (tid == 0) {
 #pragma clang fp contract(off)
@@ -545,15 +658,15 @@ __global__ __launch_bounds__(256) void env_finish_kernel(mdq_env_finish_desc d) 
     double ss = 0.0;
     bool acc = false;
     for (int s = 0; s < d.S; ++s) {
-      const double g = d.gt_drag[s], dr = d.new_drags[(int64_t)b * d.S + s];
+      const double g = gt_drag[s], dr = d.new_drags[(int64_t)b * d.S + s];
       const double e = fabs(g - dr) / fabs(g);
       ss += e * e;
       acc = acc || fabs(fabs(g - dr) / g) > d.threshold;
     }
     const double drag_reward = 2.0 * exp(-drag_factor * sqrt(ss)) - 1.0;
     const int nvb = d.nv[b];
-    const double tr = (double)(d.nv0 - nvb) * d.time_reward;
-    const bool vert = (double)nvb < d.goal_vertices * (double)d.nv0;
+    const double tr = (double)(nv0 - nvb) * d.time_reward;
+    const bool vert = (double)nvb < d.goal_vertices * (double)nv0;
     const bool ok = c == 0;
     const double r = ok ? drag_reward + tr : d.negative_reward;
     bool dn = ok ? (acc || vert) : (c != 1);
@@ -576,6 +689,7 @@ __global__ __launch_bounds__(256) void env_finish_kernel(mdq_env_finish_desc d) 
   for (int t = 0; t < d.n_rows; ++t) {
     uint32_t* ho = static_cast<uint32_t*>(d.handover_dst[t]);
     const uint32_t* src = static_cast<const uint32_t*>(d.src[t]);
+    if (src && d.src_of_env) src += (a * d.src_stride[t]) >> 2;
     const bool late = d.dst[t] == static_cast<const void*>(d.nv) || d.dst[t] == static_cast<const void*>(d.nsel);
     const bool restore = reset && src != nullptr && !late;
     if (!ho && !restore) continue;
@@ -614,6 +728,7 @@ __global__ __launch_bounds__(256) void env_finish_kernel(mdq_env_finish_desc d) 
         for (int t = 0; t < d.n_rows; ++t) {
           const uint32_t* src = static_cast<const uint32_t*>(d.src[t]);
           if (!src || (d.dst[t] != static_cast<const void*>(d.nv) && d.dst[t] != static_cast<const void*>(d.nsel))) continue;
+          if (d.src_of_env) src += (a * d.src_stride[t]) >> 2;
           const int64_t words = d.row_bytes[t] >> 2;
           uint32_t* row = static_cast<uint32_t*>(d.dst[t]) + (int64_t)b * words;
           for (int64_t i = 0; i < words; ++i) row[i] = src[i];
@@ -626,7 +741,8 @@ __global__ __launch_bounds__(256) void env_finish_kernel(mdq_env_finish_desc d) 
   const int N = d.N, S = d.S, F = 2 + 3 * S;
   float* xb = d.x + (int64_t)b * N * F;
   if (reset && d.x_init) {
-    for (int i = lin; i < N * F; i += nlin) xb[i] = d.x_init[i];
+    const float* xi = d.x_init + (int64_t)a * N * F;
+    for (int i = lin; i < N * F; i += nlin) xb[i] = xi[i];
     return;
   }
   if (reset) {               // (no cached features: read the rows restored above - needs all of them: one workgroup only)
@@ -668,7 +784,10 @@ extern "C" int mdq_env_finish(const mdq_env_finish_desc* d, void* stream) {
                                 d->handover_off[t] + d->handover_bytes[t] > d->row_bytes[t])))
       return mdq_set_error("mdq_env_finish: rows must be non-empty 4-byte aligned multiples of 4 bytes with a hand-over window inside them");
     bytes += d->handover_dst[t] ? d->handover_bytes[t] : 0;
+    if (d->src_of_env && (d->src_stride[t] < 0 || (d->src_stride[t] & 3)))
+      return mdq_set_error("mdq_env_finish: src_stride must be a non-negative multiple of 4 bytes");
   }
+  if (d->src_of_env && !d->nv0_of) return mdq_set_error("mdq_env_finish: src_of_env needs nv0_of");
   // workgroups per environment: enough lanes for the hand-over copies AND the in-place reset of a terminated environment
   // (16 bytes per lane and pass, ~4 passes; the workgroups of the other environments find nothing to restore and leave);
   // without cached initial features the reset path needs the whole environment in one workgroup

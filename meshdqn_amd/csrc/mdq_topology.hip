@@ -554,8 +554,13 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
   if (tid == 0) D.nremovable[b] = nrem;
   TT_STAMP(3)
   // ================= distances to the airfoil polygon (0 inside), stable argsort, window of N
-  const int np_ = D.npoly;
-  for (int i = tid; i < np_; i += TW) poly[i] = make_double2(D.polygon[2 * i], D.polygon[2 * i + 1]);
+  // (a batch over several airfoils: this environment's own polygon out of the concatenated ones; workgroup-uniform)
+  const int pa = D.poly_ptr ? __builtin_amdgcn_readfirstlane(D.src_of_env[b]) : 0;
+  const int p0 = D.poly_ptr ? __builtin_amdgcn_readfirstlane(D.poly_ptr[pa]) : 0;
+  // (never more points than the capacity the LDS tables were sized for: the caller keeps every polygon within npoly)
+  const int np_ = D.poly_ptr ? min(__builtin_amdgcn_readfirstlane(D.poly_ptr[pa + 1]) - p0, D.npoly) : D.npoly;
+  const double* polyg = D.polygon + 2 * (int64_t)p0;
+  for (int i = tid; i < np_; i += TW) poly[i] = make_double2(polyg[2 * i], polyg[2 * i + 1]);
   __syncthreads();
   // One lane per vertex, segments culled in GROUPS of four, waves made coherent by a counting sort.
   // Exactness is kept the way rounds 2-3 kept it: `seg_dist2` is evaluated on a SUPERSET of the segments that can attain
@@ -1346,6 +1351,8 @@ extern "C" int64_t mdq_env_topology_workspace_bytes(const mdq_env_topo_desc* d) 
 
 extern "C" int mdq_env_topology(const mdq_env_topo_desc* d, void* stream, int32_t* status) {
   if (!d || d->B <= 0 || !status) return mdq_set_error("mdq_env_topology: bad arguments");
+  if ((d->poly_ptr == nullptr) != (d->src_of_env == nullptr))
+    return mdq_set_error("mdq_env_topology: poly_ptr and src_of_env go together");
   {
     using C4_ = mdq_topo::TCap<4>;
     const bool huge_ = d->NV > C4_::NV || d->NT > C4_::NT || d->NP > C4_::NP;

@@ -126,6 +126,15 @@ class SnapshotInterpolator:
                       src_u=u_snap.to(dev, torch.float64).contiguous(), src_p=p_snap.to(dev, torch.float64).contiguous())
         self.grid = (gnx, gny, float(lo[0]), float(lo[1]), 1.0 / hx, 1.0 / hy)
 
+    def src_record(self) -> "_lib.InterpSrc":
+        """This source as one `mdq_interp_src` record (the per-airfoil sources of a mixed batch, ABI 8)."""
+        r = _lib.InterpSrc()
+        r.src_nv, r.src_nt, r.src_n2 = self.topo.nv, self.topo.nt, self.topo.np2
+        r.gnx, r.gny, r.x0, r.y0, r.inv_hx, r.inv_hy = self.grid
+        for k, v in self.t.items():
+            setattr(r, k, v.data_ptr())
+        return r
+
     def interpolate(self, topos: Sequence[MeshTopology], coords: Sequence[np.ndarray], NP=None, NP1=None, stream=None):
         """-> u (B,S,NP,2), p (B,S,NP1): snapshot values at every target's P2 dof points (vertices, then edge
         midpoints in the target's edge numbering) / P1 points (vertices)."""
@@ -224,6 +233,26 @@ def remesh_batch(coords: np.ndarray, cells: np.ndarray, nv: np.ndarray, nt: np.n
     return status
 
 
+def polygon_table(polygon, airfoil=None):
+    """The polygon argument of the topology engines: one (npoly, 2) array (every environment measures against it), or a list of
+    A arrays + `airfoil` (B,) = the airfoil of every environment (ABI 8: the polygons one after the other, `poly_ptr` (A+1,)
+    their first points; npoly = the largest).  -> (points (P, 2) f8, npoly, poly_ptr (A+1,) i4 or None, airfoil (B,) i4 or None)"""
+    if not isinstance(polygon, (list, tuple)):
+        pts = np.ascontiguousarray(polygon, dtype=np.float64)
+        return pts, pts.shape[0], None, None
+    polys = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 2) for p in polygon]
+    if airfoil is None:
+        raise ValueError("a list of polygons needs `airfoil` (the airfoil of every environment)")
+    airfoil = np.ascontiguousarray(airfoil, dtype=np.int32)
+    if airfoil.size and (airfoil.min() < 0 or airfoil.max() >= len(polys)):
+        raise ValueError("airfoil: indices outside the list of polygons")
+    if min(p.shape[0] for p in polys) < 3:
+        raise ValueError("every polygon needs at least 3 points")
+    ptr = np.zeros(len(polys) + 1, np.int32)
+    ptr[1:] = np.cumsum([p.shape[0] for p in polys])
+    return np.ascontiguousarray(np.concatenate(polys)), int(max(p.shape[0] for p in polys)), ptr, airfoil
+
+
 class HostTopologyBatch:
     """Host arrays + descriptor of `mdq_env_topology_host` for B environments (capacities fixed at construction).
 
@@ -243,11 +272,12 @@ class HostTopologyBatch:
         array again before the caller has synchronised on results of this step)."""
         return self.pinned[name].to(device, non_blocking=True)
 
-    def __init__(self, B, NV, NT, NE, NAF, N, EMAX, polygon, ipcs=False, nbo_cap=64, nse1_cap=0):
+    def __init__(self, B, NV, NT, NE, NAF, N, EMAX, polygon, ipcs=False, nbo_cap=64, nse1_cap=0, airfoil=None):
         self.lib = _lib.load()
         NP = NV + NE
         self.B, self.NV, self.NT, self.NE, self.NP, self.NAF, self.N, self.EMAX = B, NV, NT, NE, NP, NAF, N, EMAX
-        self.polygon = np.ascontiguousarray(polygon, dtype=np.float64)
+        # (a list of polygons + `airfoil`: one polygon per airfoil of a mixed batch, see polygon_table)
+        self.polygon, npoly, self.poly_ptr, self.airfoil = polygon_table(polygon, airfoil)
         # page-locked host arrays (when a GPU is present): uploads run at full PCIe rate and asynchronously
         self._pin = torch.cuda.is_available()
         self.pinned = {}
@@ -266,9 +296,13 @@ class HostTopologyBatch:
                       edge_src=np.zeros((B, EMAX), np.int32), edge_dst=np.zeros((B, EMAX), np.int32),
                       edge_len=np.zeros((B, EMAX)))
         d = _lib.EnvTopoDesc()
-        d.B, d.NV, d.NT, d.NP, d.NAF, d.N, d.EMAX, d.npoly = B, NV, NT, NP, NAF, N, EMAX, self.polygon.shape[0]
+        d.B, d.NV, d.NT, d.NP, d.NAF, d.N, d.EMAX, d.npoly = B, NV, NT, NP, NAF, N, EMAX, npoly
         d.coords, d.cells, d.nv, d.nt = (a.ctypes.data for a in (self.coords, self.cells, self.nv, self.nt))
         d.offset, d.polygon = self.offset.ctypes.data, self.polygon.ctypes.data
+        if self.poly_ptr is not None:
+            if self.airfoil.shape != (B,):
+                raise ValueError("airfoil: one entry per environment")
+            d.poly_ptr, d.src_of_env = self.poly_ptr.ctypes.data, self.airfoil.ctypes.data
         for k, a in self.h.items():
             setattr(d, k, a.ctypes.data)
         self.hi = None
@@ -388,7 +422,8 @@ class DeviceTopologyBatch:
     (B,NT,3), `nv`, `nt`, `offset` and all outputs are device tensors (`t` for the mesh / state outputs, `ti` for the
     matrix-free IPCS index data); nothing but what the caller asks for ever crosses PCIe."""
 
-    def __init__(self, B, NV, NT, NE, NAF, N, EMAX, polygon, device, ipcs=False, nbo_cap=64, nse1_cap=0, flow_only=False):
+    def __init__(self, B, NV, NT, NE, NAF, N, EMAX, polygon, device, ipcs=False, nbo_cap=64, nse1_cap=0, flow_only=False,
+                 airfoil=None):
         self.lib = _lib.load()
         dev = torch.device(device)
         NP = NV + NE
@@ -399,7 +434,13 @@ class DeviceTopologyBatch:
             return torch.zeros(shape, dtype=dt, device=dev)
 
         i32, f64 = torch.int32, torch.float64
-        self.polygon = torch.as_tensor(np.ascontiguousarray(polygon, dtype=np.float64), device=dev)
+        # (a list of polygons + `airfoil`: one polygon per airfoil of a mixed batch, see polygon_table)
+        pts, npoly, ptr, af = polygon_table(polygon, airfoil)
+        self.polygon = torch.as_tensor(pts, device=dev)
+        self.poly_ptr = None if ptr is None else torch.from_numpy(ptr).to(dev)
+        self.airfoil = None if af is None else torch.from_numpy(af).to(dev)
+        if af is not None and af.shape != (B,):
+            raise ValueError("airfoil: one entry per environment")
         self.coords, self.cells = z((B, NV, 2), f64), z((B, NT, 3), i32)
         self.nv, self.nt, self.offset = z((B,), i32), z((B,), i32), z((B,), i32)
         self.status = z((B,), i32)
@@ -408,9 +449,11 @@ class DeviceTopologyBatch:
                       n_closest=z((B, N), i32), coord_map=z((B, N), i32), nedges=z((B,), i32),
                       edge_src=z((B, EMAX), i32), edge_dst=z((B, EMAX), i32), edge_len=z((B, EMAX), f64))
         d = _lib.EnvTopoDesc()
-        d.B, d.NV, d.NT, d.NP, d.NAF, d.N, d.EMAX, d.npoly = B, NV, NT, NP, NAF, N, EMAX, self.polygon.shape[0]
+        d.B, d.NV, d.NT, d.NP, d.NAF, d.N, d.EMAX, d.npoly = B, NV, NT, NP, NAF, N, EMAX, npoly
         d.coords, d.cells, d.nv, d.nt = (a.data_ptr() for a in (self.coords, self.cells, self.nv, self.nt))
         d.offset, d.polygon = self.offset.data_ptr(), self.polygon.data_ptr()
+        if ptr is not None:
+            d.poly_ptr, d.src_of_env = self.poly_ptr.data_ptr(), self.airfoil.data_ptr()
         for k, a in self.t.items():
             setattr(d, k, a.data_ptr())
         self.ti = None

@@ -891,15 +891,24 @@ def train_loop_per_worker(trainer: DQNTrainer, env_factory, num_episodes: int, m
     return history
 
 
+def _episode_airfoil(venv, b):
+    """Airfoil of environment b of a batch over several airfoils (TrainingLog's `airfoil.npy`), None for one airfoil."""
+    return int(venv.airfoil[b]) if getattr(venv, "A", 1) > 1 else None
+
+
 class TrainingLog:
     """The reference's on-disk training log (DataHandler, airfoil_dqn.py:79-133): `reward.npy` (sum per episode),
     `rewards.npy` / `actions.npy` (per-episode lists), `losses.npy`, `eps.npy`, written under `save_dir + prefix`;
     `restart=True` continues from existing files and switches to the `RESTART_` prefix like the reference."""
-    FILES = dict(rewards="reward.npy", ep_rewards="rewards.npy", losses="losses.npy", actions="actions.npy", epss="eps.npy")
+    FILES = dict(rewards="reward.npy", ep_rewards="rewards.npy", losses="losses.npy", actions="actions.npy", epss="eps.npy",
+                 airfoils="airfoil.npy")
 
     def __init__(self, save_dir: str, prefix: str = "", restart: bool = False, restart_num: int = 1):
         self.base = os.path.join(save_dir, prefix)
         self.rewards, self.ep_rewards, self.losses, self.actions, self.epss = [], [], [], [], []
+        # a batch over several airfoils (VecEnv2DAirfoil with a list of configs): the airfoil of every finished episode,
+        # `airfoil.npy` beside `reward.npy` (not written by single-airfoil runs)
+        self.airfoils = []
         if restart:
             # the n-th restart reads the files of restart n - 1 and writes with one more prefix (airfoil_dqn.py:87-110)
             self.base += "RESTART_" * (max(int(restart_num), 1) - 1)
@@ -916,10 +925,12 @@ class TrainingLog:
     def add_loss(self, loss):
         self.losses.append(float(loss))
 
-    def add_episode(self, ep_rewards, ep_actions):
+    def add_episode(self, ep_rewards, ep_actions, airfoil=None):
         self.rewards.append(float(sum(ep_rewards)))
         self.ep_rewards.append(list(ep_rewards))
         self.actions.append(list(ep_actions))
+        if airfoil is not None:
+            self.airfoils.append(int(airfoil))
 
     def write(self):
         os.makedirs(os.path.dirname(self.base) or ".", exist_ok=True)
@@ -928,6 +939,8 @@ class TrainingLog:
         np.save(self.base + "losses.npy", np.array(self.losses))
         np.save(self.base + "actions.npy", np.array(self.actions, dtype=object), allow_pickle=True)
         np.save(self.base + "eps.npy", np.array(self.epss))
+        if self.airfoils:
+            np.save(self.base + "airfoil.npy", np.array(self.airfoils, dtype=np.int64))
 
 
 class StateRef:
@@ -1237,7 +1250,7 @@ def train_loop_vec(trainer: DQNTrainer, venv, num_steps: int, optim_per_step: in
                 ep_r[b].append(float(rew[b]))
                 ep_a[b].append(int(actions[b]))
                 if done[b]:
-                    log.add_episode(ep_r[b], ep_a[b])
+                    log.add_episode(ep_r[b], ep_a[b], _episode_airfoil(venv, b))
                     ep_r[b], ep_a[b] = [], []
         rewards.append(rew.copy())
         dones_hist.append(done.copy())
@@ -1409,7 +1422,7 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
                     ep_r[b].append(float(rew[b]))
                     ep_a[b].append(int(out["actions"][k][b]))
                     if done[b]:
-                        log.add_episode(ep_r[b], ep_a[b])
+                        log.add_episode(ep_r[b], ep_a[b], _episode_airfoil(venv, b))
                         ep_r[b], ep_a[b] = [], []
         if log is not None:
             for l_ in new_losses:

@@ -9,9 +9,11 @@ Env2DAirfoil.py:318-428 step / reward / state logic), batched:
   GPU    mdq_probe_forces            2S force integrals per env                         (one launch)
   GPU    feature gather (torch indexing) and, optionally, the fused Q-network forward (mdq_gcn_forward)
 
-All environments start from the same smoothed original mesh and share its ground truth and snapshots
+All environments of one airfoil start from the same smoothed original mesh and share its ground truth and snapshots
 (computed once by a base `Env2DAirfoil`, i.e. the reference's first `reset()`); terminated environments
-are reset in place.  Triangulations are identical to the reference's as SETS of cells; the cell ORDER
+are reset in place.  A batch may mix A airfoils (a list of A configs / base envs): environment b then belongs to
+airfoil `airfoil[b]` - its mesh, ground truth, snapshots, polygon and resets are that airfoil's - while every kernel
+launch still covers the whole batch (capacities = the largest airfoil's).  Triangulations are identical to the reference's as SETS of cells; the cell ORDER
 (an artefact of Qhull in the reference) is the engine's own, so `edge_index` columns come in a different
 order than in the single-environment class.
 """
@@ -43,15 +45,86 @@ def _host_cores() -> int:
     return n
 
 
+# keys whose values may differ between the configs of a batch over several airfoils: everything else - flow / solver /
+# agent parameters, hence N_closest, S = solver_steps // save_steps, mu, rho, dt - is batch-wide
+_PER_AIRFOIL_KEYS = {("flow_config", "geometry_params", "mesh")} | {
+    ("agent_params", k) for k in ("gt_drag", "gt_lift", "gt_time", "u", "p", "plot_dir")}
+
+
+def _same_value(a, b) -> bool:
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        return np.array_equal(np.asarray(a), np.asarray(b))
+    if isinstance(a, (list, tuple)) and isinstance(b, (list, tuple)):
+        return len(a) == len(b) and all(_same_value(x, y) for x, y in zip(a, b))
+    return type(a) is type(b) and a == b or (isinstance(a, (int, float)) and isinstance(b, (int, float)) and a == b)
+
+
+def _diff_keys(a, b, path=()):
+    """Key paths (tuples) where two configs differ, allowed per-airfoil keys excluded."""
+    if path in _PER_AIRFOIL_KEYS:
+        return []
+    if isinstance(a, dict) and isinstance(b, dict):
+        out = []
+        for k in list(a) + [k for k in b if k not in a]:
+            if k not in a or k not in b:
+                if path + (k,) not in _PER_AIRFOIL_KEYS:
+                    out.append(path + (k,))
+            else:
+                out += _diff_keys(a[k], b[k], path + (k,))
+        return out
+    return [] if _same_value(a, b) else [path]
+
+
+def check_airfoil_configs(configs):
+    """A batch over several airfoils: the configs may differ only in the mesh path, gt_drag / gt_lift / gt_time, u / p and
+    plot_dir.  Raises ValueError naming the first offending key."""
+    for i, c in enumerate(configs[1:], 1):
+        bad = _diff_keys(configs[0], c)
+        if bad:
+            raise ValueError(f"configs 0 and {i} of a mixed-airfoil batch differ in `{'.'.join(map(str, bad[0]))}` (only the mesh, "
+                             "gt_drag, gt_lift, gt_time, u, p and plot_dir may differ between airfoils)")
+
+
+def airfoil_assignment(num_envs: int, n_airfoils: int, first_env: int = 0) -> np.ndarray:
+    """Airfoil of the environments with global ids first_env .. first_env + num_envs - 1: id mod A (a rank that owns the
+    contiguous block of ids `DistContext.shard` hands it sees every airfoil as long as it has at least A environments)."""
+    return ((int(first_env) + np.arange(int(num_envs))) % int(n_airfoils)).astype(np.int32)
+
+
 class VecEnv2DAirfoil:
     FLOW_NRL = 4032         # row capacity of a chunk's list in the device-built tile maps (the kernels' LDS stage holds 4064 rows)
 
-    def __init__(self, config, num_envs: int, compute_device="cuda", nthreads: int = 0, base_env: Env2DAirfoil | None = None,
+    def __init__(self, config, num_envs: int, compute_device="cuda", nthreads: int = 0, base_env=None,
                  auto_reset: bool = True, emax: int = 1536, flow_steps: int = 0, flow_rtol: float = 1e-10,
                  gpu_smoothing: bool = True, gpu_topology: bool = True, gpu_remesh: bool = True,
-                 flow_overlap: bool = False, flow_pressure: str = "cg", flow_pcg_degree: int = 0):
+                 flow_overlap: bool = False, flow_pressure: str = "cg", flow_pcg_degree: int = 0, airfoil_of_env=None):
+        """`config`: one config dict, or a list of A of them (a batch over A airfoils, see `check_airfoil_configs`);
+        `base_env`: an `Env2DAirfoil` or a list of A of them (None: built from the configs); `airfoil_of_env` (B,) ints in
+        [0, A): the airfoil of every environment (default b mod A)."""
         self.lib = _lib.load()
         self.B = int(num_envs)
+        configs = list(config) if isinstance(config, (list, tuple)) else [config]
+        if not configs:
+            raise ValueError("config: an empty list")
+        check_airfoil_configs(configs)
+        self.A = A = len(configs)
+        if base_env is None:
+            bases = [Env2DAirfoil(c, compute_device=compute_device) for c in configs]
+        else:
+            bases = list(base_env) if isinstance(base_env, (list, tuple)) else [base_env]
+            if len(bases) != A:
+                raise ValueError(f"base_env: {len(bases)} base environments for {A} configs")
+        self.bases = bases
+        if airfoil_of_env is None:
+            airfoil = airfoil_assignment(self.B, A)
+        else:
+            airfoil = np.asarray(airfoil_of_env)
+            if airfoil.shape != (self.B,) or not np.issubdtype(airfoil.dtype, np.integer):
+                raise ValueError("airfoil_of_env: one integer per environment")
+            if self.B and (airfoil.min() < 0 or airfoil.max() >= A):
+                raise ValueError(f"airfoil_of_env: values outside [0, {A})")
+        self.airfoil = np.ascontiguousarray(airfoil, dtype=np.int32)
+        config = configs[0]
         self.device = torch.device(compute_device)
         # workers of the host engine's persistent pool (one environment per task)
         self.nthreads = int(nthreads) if nthreads > 0 else max(1, min(_host_cores(), self.B))
@@ -83,7 +156,7 @@ class VecEnv2DAirfoil:
             raise ValueError("flow_pressure: 'cg' or 'direct'")
         self.flow_pressure = flow_pressure
         self.flow_pcg_degree = int(flow_pcg_degree)     # Chebyshev degree of the pressure CG's preconditioner (0: Jacobi-CG kernel)
-        base = base_env or Env2DAirfoil(config, compute_device=compute_device)
+        base = bases[0]
         self.base = base
         ap = config["agent_params"]
         self.N = int(ap["N_closest"])
@@ -92,51 +165,82 @@ class VecEnv2DAirfoil:
         self.goal_vertices = float(ap["goal_vertices"])
         self.timesteps = int(ap["timesteps"])
         self.NEGATIVE_REWARD = -1.0
-        self.gt_drag = np.asarray(base.gt_drag, dtype=np.float64)
-        self.gt_lift = np.asarray(base.gt_lift, dtype=np.float64)
         self.S = len(base.original_u)
-        topo0 = base._orig_topo
-        self.x0 = topo0.coords.copy()
-        self.cells0 = np.ascontiguousarray(topo0.cells, dtype=np.int32)
-        self.NV, self.NT = topo0.nv, topo0.nt
-        self.NE = topo0.ne
+        if any(len(bb.original_u) != self.S or np.asarray(bb.gt_drag).shape != (self.S,) for bb in bases):
+            raise ValueError("snapshots: every airfoil needs the same S = solver_steps // save_steps snapshots and gt_drag values")
+        if any(bb.flow_solver.mu != base.flow_solver.mu or bb.flow_solver.rho != base.flow_solver.rho or
+               bb.flow_solver.dt_value != base.flow_solver.dt_value for bb in bases):
+            raise ValueError("flow_params / solver_params: mu, rho and dt must agree across the airfoils")
+        # per airfoil (index a): ground truth, initial mesh, polygon, interpolation source; one airfoil keeps the arrays of
+        # the single-airfoil batch (gt_drag (S,), x0 (NV, 2), ...)
+        self.gt_drags = np.stack([np.asarray(bb.gt_drag, dtype=np.float64) for bb in bases])            # (A, S)
+        self.gt_drag = self.gt_drags[0] if A == 1 else self.gt_drags
+        self.gt_lift = (np.asarray(base.gt_lift, dtype=np.float64) if A == 1 else
+                        np.stack([np.asarray(bb.gt_lift, dtype=np.float64) for bb in bases]))
+        topos = [bb._orig_topo for bb in bases]
+        topo0 = topos[0]
+        # capacities: the largest airfoil's (the kernel instance K = 1 / 4 / 16 follows from them)
+        self.NV, self.NT = max(t.nv for t in topos), max(t.nt for t in topos)
+        self.NE = max(t.ne for t in topos)
         self.NP = self.NV + self.NE
         self.EMAX = int(emax)
-        self.polygon = np.ascontiguousarray(base.polygon, dtype=np.float64)
-        self.interp = base._interp
+        self.nv0s = np.array([t.nv for t in topos], np.int32)                                           # (A,)
+        self.nt0s = np.array([t.nt for t in topos], np.int32)
+        self._x0s = np.zeros((A, self.NV, 2))                   # initial meshes at the batch's row strides (zero padding)
+        self._cells0s = np.zeros((A, self.NT, 3), np.int32)
+        for a, t in enumerate(topos):
+            self._x0s[a, :t.nv] = t.coords
+            self._cells0s[a, :t.nt] = t.cells
+        self.x0 = topo0.coords.copy() if A == 1 else self._x0s
+        self.cells0 = np.ascontiguousarray(topo0.cells, dtype=np.int32) if A == 1 else self._cells0s
+        self.polygons = [np.ascontiguousarray(bb.polygon, dtype=np.float64) for bb in bases]
+        self.polygon = self.polygons[0] if A == 1 else self.polygons
+        self.interps = [bb._interp for bb in bases]
+        self.interp = self.interps[0]
         self.mu = base.flow_solver.mu
         B, NV, NT, NP, N = self.B, self.NV, self.NT, self.NP, self.N
-        self.NAF = int(max((topo0.facet_tags() == 1).sum(), 1))
+        self.NAF = int(max(max((t.facet_tags() == 1).sum(), 1) for t in topos))
         # host state + outputs of the topology engine
-        nbr_ptr = topo0.vertex_adjacency()[0]
-        deg = np.zeros(64 * (NV // 64 + 1), np.int64)
-        deg[:NV] = np.diff(nbr_ptr) + 1
-        nse1 = int(64 * deg.reshape(-1, 64).max(axis=1).sum())        # SELL-64 entries of the P1 Laplacian, initial mesh
-        nse1_cap = (int(1.2 * nse1) + 63) // 64 * 64
+        nse1_cap = 0
+        for t in topos:
+            nbr_ptr = t.vertex_adjacency()[0]
+            deg = np.zeros(64 * (NV // 64 + 1), np.int64)
+            deg[:t.nv] = np.diff(nbr_ptr) + 1
+            nse1 = int(64 * deg.reshape(-1, 64).max(axis=1).sum())        # SELL-64 entries of the P1 Laplacian, initial mesh
+            nse1_cap = max(nse1_cap, (int(1.2 * nse1) + 63) // 64 * 64)
+        # outflow rows of the facet term: two vertices + one edge dof per outflow facet, shared vertices counted once
+        nbo_cap = max(max(64, 2 * (2 * int((t.facet_tags() == 3).sum()) + 1)) for t in topos)
+        af = None if A == 1 else self.airfoil
         self.topo = HostTopologyBatch(B, NV, NT, self.NE, self.NAF, N, self.EMAX, self.polygon,
                                       ipcs=self.flow_steps > 0 and not self.gpu_topology, nse1_cap=nse1_cap,
-                                      nbo_cap=max(64, 2 * (2 * int((topo0.facet_tags() == 3).sum()) + 1)))
+                                      nbo_cap=nbo_cap, airfoil=af)
         self.dtopo = None
-        # outflow rows of the facet term: two vertices + one edge dof per outflow facet, shared vertices counted once
-        nbo_cap = max(64, 2 * (2 * int((topo0.facet_tags() == 3).sum()) + 1))
         if self.gpu_topology:
             self.dtopo = DeviceTopologyBatch(B, NV, NT, self.NE, self.NAF, N, self.EMAX, self.polygon, self.device,
-                                             ipcs=self.flow_steps > 0 and not self.flow_overlap, nse1_cap=nse1_cap, nbo_cap=nbo_cap)
+                                             ipcs=self.flow_steps > 0 and not self.flow_overlap, nse1_cap=nse1_cap, nbo_cap=nbo_cap,
+                                             airfoil=af)
             if self.flow_overlap:
                 # the flow stream's own engine: a private copy of the meshes, the full topology (with the IPCS index data,
                 # which only the flow needs: 0.19 ms less on the critical path) and the IPCS step run there
                 self._ftopo = DeviceTopologyBatch(B, NV, NT, self.NE, self.NAF, N, self.EMAX, self.polygon, self.device,
-                                                  ipcs=True, nse1_cap=nse1_cap, flow_only=True, nbo_cap=nbo_cap)
+                                                  ipcs=True, nse1_cap=nse1_cap, flow_only=True, nbo_cap=nbo_cap, airfoil=af)
         self._packed_host, self._packed_ev, self._pending, self._step_pending = None, torch.cuda.Event(), None, None
         self._restore_args = {}
         self._deferred_mirror = None
         self._node_ptr = torch.arange(B + 1, dtype=torch.int32, device=self.device) * N   # (constant: N rows per graph)
-        # the initial mesh on the device: source rows of the in-place resets (mdq_restore_rows)
-        self._x0_dev = torch.from_numpy(np.ascontiguousarray(topo0.coords, dtype=np.float64)).to(self.device)
-        self._cells0_dev = torch.from_numpy(np.ascontiguousarray(topo0.cells, dtype=np.int32)).to(self.device)
-        self._nv0_dev = torch.tensor([NV], dtype=torch.int32, device=self.device)
-        self._nt0_dev = torch.tensor([NT], dtype=torch.int32, device=self.device)
+        # the initial meshes on the device (one row per airfoil, at the batch's row strides): source rows of the in-place
+        # resets (mdq_restore_rows; several airfoils: mdq_restore_rows_src, the row of environment b's airfoil)
+        self._x0_dev = torch.from_numpy(np.ascontiguousarray(self._x0s, dtype=np.float64)).to(self.device)
+        self._cells0_dev = torch.from_numpy(np.ascontiguousarray(self._cells0s, dtype=np.int32)).to(self.device)
+        self._nv0_dev = torch.from_numpy(self.nv0s.copy()).to(self.device)
+        self._nt0_dev = torch.from_numpy(self.nt0s.copy()).to(self.device)
         self._zero_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._airfoil_dev = torch.from_numpy(self.airfoil.copy()).to(self.device)
+        self._interp_srcs = None
+        if A > 1:       # the interpolation sources of the airfoils: one mdq_interp_src record each, on the device
+            recs = (_lib.InterpSrc * A)(*[it.src_record() for it in self.interps])
+            raw = np.frombuffer(bytes(recs), dtype=np.uint8).copy()
+            self._interp_srcs = torch.from_numpy(raw).to(self.device)
         if self.gpu_remesh:
             self._rstat = torch.zeros(B, dtype=torch.int32, device=self.device)
             self._rstat_host = torch.zeros(B, dtype=torch.int32, pin_memory=True)
@@ -149,7 +253,10 @@ class VecEnv2DAirfoil:
                                                                    self.topo.nt, self.topo.offset)
         self.h = self.topo.h   # (device engine: only nsel / n_closest / coord_map / nedges / ne are mirrored here)
         self.steps = np.zeros(B, np.int64)
-        self.initial_num_node = NV
+        # vertex count of the initial mesh, which the time reward and goal_vertices are measured against (per environment
+        # in a batch over several airfoils)
+        self.initial_num_node = NV if A == 1 else self.nv0s[self.airfoil].astype(np.int64)
+        self._gt_drag_env = self.gt_drags[self.airfoil]          # (B, S): the ground truth of every environment's airfoil
         self.new_drags = np.zeros((B, self.S))
         self.new_lifts = np.zeros((B, self.S))
         self.reset_all()
@@ -445,9 +552,10 @@ class VecEnv2DAirfoil:
 
     # ------------------------------------------------------------------
     def _reset_env(self, b):
-        self.coords[b] = self.x0
-        self.cells[b] = self.cells0
-        self.nv[b], self.nt[b] = self.NV, self.NT
+        a = self.airfoil[b]
+        self.coords[b] = self._x0s[a]
+        self.cells[b] = self._cells0s[a]
+        self.nv[b], self.nt[b] = self.nv0s[a], self.nt0s[a]
         self.offset[b] = 0
         self.steps[b] = 0
 
@@ -463,12 +571,26 @@ class VecEnv2DAirfoil:
         if self.gpu_topology:
             self._upload_mesh()
         self._refresh()
-        # every environment restarts from the same mesh: cache its derived data (row 0) for in-place resets
-        self._init_cache = dict(h={k: a[0].copy() for k, a in self.h.items()}, u=self.u[0].clone(), p=self.p[0].clone(),
-                                drags=self.new_drags[0].copy(), lifts=self.new_lifts[0].copy())
-        if self.gpu_topology:
-            self._init_cache["dev"] = {k: self.dtopo.t[k][0].clone() for k in self._STATE_KEYS}
+        if self.A == 1:
+            # every environment restarts from the same mesh: cache its derived data (row 0) for in-place resets
+            self._init_cache = dict(h={k: a[0].copy() for k, a in self.h.items()}, u=self.u[0].clone(), p=self.p[0].clone(),
+                                    drags=self.new_drags[0].copy(), lifts=self.new_lifts[0].copy())
+            if self.gpu_topology:
+                self._init_cache["dev"] = {k: self.dtopo.t[k][0].clone() for k in self._STATE_KEYS}
+        else:
+            # every environment of an airfoil restarts from the same mesh: the derived data of one environment per airfoil
+            # (rows (A, ...) at the batch's strides; row a = the first environment of airfoil a)
+            rows = [int(np.flatnonzero(self.airfoil == a)[0]) if (self.airfoil == a).any() else 0 for a in range(self.A)]
+            ri = torch.tensor(rows, dtype=torch.long, device=self.device)
+            self._init_cache = dict(h={k: a[rows].copy() for k, a in self.h.items()}, u=self.u[ri].contiguous(),
+                                    p=self.p[ri].contiguous(), drags=self.new_drags[rows].copy(), lifts=self.new_lifts[rows].copy())
+            if self.gpu_topology:
+                self._init_cache["dev"] = {k: self.dtopo.t[k][ri].contiguous() for k in self._STATE_KEYS}
         return self.get_state()
+
+    def _cached(self, v, idx):
+        """Cached initial rows `v` (one row for one airfoil, (A, ...) for several) for environments idx."""
+        return v if self.A == 1 else v[self.airfoil[idx]]
 
     _STATE_KEYS = ("n_closest", "nsel", "coord_map", "nedges", "edge_src", "edge_dst")   # what get_state reads
 
@@ -485,22 +607,33 @@ class VecEnv2DAirfoil:
         """Reset environments `idx` in place from the cached initial-mesh data (no recomputation)."""
         c = self._init_cache
         idx = np.asarray(idx)
+        af = self.airfoil[idx]          # (every environment restarts on its own airfoil)
         self._deferred_mirror = idx     # coords / cells host mirrors: written after the next state has been launched
-        self.nv[idx], self.nt[idx] = self.NV, self.NT
+        self.nv[idx], self.nt[idx] = self.nv0s[af], self.nt0s[af]
         self.offset[idx] = 0
         self.steps[idx] = 0
         # (device engine: only these are mirrored on the host, see _refresh_collect; the others are dead rows)
         keys = ("nsel", "n_closest", "coord_map", "nedges", "ne") if self.gpu_topology else tuple(self.h)
         for k in keys:
-            self.h[k][idx] = c["h"][k]
-        self.new_drags[idx] = c["drags"]
-        self.new_lifts[idx] = c["lifts"]
+            self.h[k][idx] = self._cached(c["h"][k], idx)
+        self.new_drags[idx] = self._cached(c["drags"], idx)
+        self.new_lifts[idx] = self._cached(c["lifts"], idx)
         # device side: ONE launch restores the rows of every tensor (a dozen index_put launches otherwise).  The
         # argument arrays are built once; only the two per-step buffers (u, p) change their addresses.
         ra = self._restore_arg_arrays()
         ti = torch.from_numpy(idx.astype(np.int32)).to(self.device)
-        _lib.check(self.lib.mdq_restore_rows(ra["n"], ra["dst"], ra["src"], ra["nbytes"], int(ti.numel()), ti.data_ptr(),
-                                             _lib.stream_ptr()), "mdq_restore_rows")
+        self._restore_rows(ra, int(ti.numel()), ti)
+
+    def _restore_rows(self, ra, n_idx, ti):
+        """mdq_restore_rows over the argument arrays `ra`; several airfoils: mdq_restore_rows_src (each environment from
+        the cached row of its own airfoil)."""
+        if self.A == 1:
+            _lib.check(self.lib.mdq_restore_rows(ra["n"], ra["dst"], ra["src"], ra["nbytes"], n_idx, ti.data_ptr(),
+                                                 _lib.stream_ptr()), "mdq_restore_rows")
+        else:
+            _lib.check(self.lib.mdq_restore_rows_src(ra["n"], ra["dst"], ra["src"], ra["stride"], ra["nbytes"], n_idx,
+                                                     ti.data_ptr(), self._airfoil_dev.data_ptr(), _lib.stream_ptr()),
+                       "mdq_restore_rows_src")
 
     def _restore_arg_arrays(self):
         c = self._init_cache
@@ -515,12 +648,15 @@ class VecEnv2DAirfoil:
                           (dt.offset, self._zero_dev)]
             n = len(pairs)
             nbytes = [a[0].numel() * a.element_size() for a, _ in pairs]
-            for (a, b_), nb in zip(pairs, nbytes):
-                assert a.is_contiguous() and b_.is_contiguous() and b_.numel() * b_.element_size() == nb and a.dtype == b_.dtype
+            # sources: one row per airfoil (stride = the row) or one row for all (the offset: stride 0)
+            stride = [nb if b_.numel() * b_.element_size() != nb else 0 for (_, b_), nb in zip(pairs, nbytes)]
+            for (a, b_), nb, st in zip(pairs, nbytes, stride):
+                assert a.is_contiguous() and b_.is_contiguous() and a.dtype == b_.dtype
+                assert b_.numel() * b_.element_size() == (self.A * nb if st else nb)
             ra = self._restore_args[0] = dict(n=n, dst=(C.c_void_p * n)(*[a.data_ptr() for a, _ in pairs]),
                                               src=(C.c_void_p * n)(*[b_.data_ptr() for _, b_ in pairs]),
-                                              nbytes=(C.c_int64 * n)(*nbytes), coords=self._coords_dev.data_ptr(),
-                                              keep=pairs)
+                                              nbytes=(C.c_int64 * n)(*nbytes), stride=(C.c_int64 * n)(*stride),
+                                              coords=self._coords_dev.data_ptr(), keep=pairs)
         ra["dst"][0], ra["dst"][1] = self.u.data_ptr(), self.p.data_ptr()
         return ra
 
@@ -573,6 +709,8 @@ class VecEnv2DAirfoil:
         d.npts_extra = None if npts_extra is None else npts_extra.data_ptr()
         for k, v in it.t.items():
             setattr(d, k, v.data_ptr())
+        if self._interp_srcs is not None:       # several airfoils: every environment from its own airfoil's source
+            d.n_src, d.src_of_env, d.srcs = self.A, self._airfoil_dev.data_ptr(), self._interp_srcs.data_ptr()
         d.out_u, d.out_p, d.out_cell = out_u.data_ptr(), out_p.data_ptr(), None
         if sparse and self.gpu_topology:
             # device-resident step: only the entries it reads (vertices, the last snapshot's edge values for the flow leg's warm
@@ -777,10 +915,11 @@ class VecEnv2DAirfoil:
         rewards = np.zeros(B)
         dones = np.zeros(B, bool)
         drag_factor = -2 * np.log(0.5) / self.threshold
-        err = np.abs(self.gt_drag[None] - self.new_drags) / np.abs(self.gt_drag[None])
+        gt = self._gt_drag_env          # (B, S): every environment's own airfoil
+        err = np.abs(gt - self.new_drags) / np.abs(gt)
         drag_reward = 2 * np.exp(-drag_factor * np.linalg.norm(err, axis=1)) - 1
         time_reward = (self.initial_num_node - self.nv) * self.TIME_REWARD
-        acc = (np.abs(np.abs(self.gt_drag[None] - self.new_drags) / self.gt_drag[None]) > self.threshold).any(axis=1)
+        acc = (np.abs(np.abs(gt - self.new_drags) / gt) > self.threshold).any(axis=1)
         vert = self.nv < self.goal_vertices * self.initial_num_node
         ok = code == 0
         rewards[ok] = (drag_reward + time_reward)[ok]
@@ -799,8 +938,9 @@ class VecEnv2DAirfoil:
             self._restore_initial(np.flatnonzero(dones))
         state = self.get_state()
         if self._deferred_mirror is not None:   # (off the critical path: the GPU is already working on the next state)
-            self.coords[self._deferred_mirror] = self.x0
-            self.cells[self._deferred_mirror] = self.cells0
+            af = self.airfoil[self._deferred_mirror]
+            self.coords[self._deferred_mirror] = self._x0s[af]
+            self.cells[self._deferred_mirror] = self._cells0s[af]
             self._deferred_mirror = None
         return state, rewards, dones, infos
 
@@ -934,8 +1074,8 @@ class VecEnv2DAirfoil:
                   # step counters: read by every workgroup of mdq_env_finish, written to the other array (si: the current one)
                   d_steps=[torch.from_numpy(self.steps.astype(np.int32)).to(dev), torch.empty(B, dtype=i32, device=dev)], si=0,
                   err=torch.zeros(1, dtype=i32, device=dev))
-        if getattr(self, "_gt_drag_dev", None) is None:
-            self._gt_drag_dev = torch.from_numpy(np.ascontiguousarray(self.gt_drag, dtype=np.float64)).to(dev)
+        if getattr(self, "_gt_drag_dev", None) is None:       # (A, S): row a = airfoil a
+            self._gt_drag_dev = torch.from_numpy(np.ascontiguousarray(self.gt_drags, dtype=np.float64)).to(dev)
         dt.offset.copy_(torch.from_numpy(self.offset))
         ro["state"] = self._state_device()
         return ro
@@ -1006,17 +1146,19 @@ class VecEnv2DAirfoil:
         if d is None:
             d = self._fin_desc = _lib.EnvFinishDesc()
             d.B, d.N, d.S, d.NV, d.NP = B, N, S, self.NV, self.NP
-            d.nv0, d.timesteps, d.auto_reset = int(self.initial_num_node), int(self.timesteps), 1 if self.auto_reset else 0
+            d.nv0, d.timesteps, d.auto_reset = int(self.nv0s[0]), int(self.timesteps), 1 if self.auto_reset else 0
             d.threshold, d.time_reward, d.goal_vertices, d.negative_reward = (float(self.threshold), float(self.TIME_REWARD),
                                                                                 float(self.goal_vertices), float(self.NEGATIVE_REWARD))
             d.gt_drag, d.nv, d.rstat = self._gt_drag_dev.data_ptr(), dt.nv.data_ptr(), self._rstat.data_ptr()
             d.topo_status, d.nsel, d.n_closest = dt.status.data_ptr(), dt.t["nsel"].data_ptr(), dt.t["n_closest"].data_ptr()
             self._fin_arrive = torch.zeros(B, dtype=torch.int32, device=self.device)   # (every launch leaves it at zero)
             d.arrive = self._fin_arrive.data_ptr()
+            if self.A > 1:          # per-airfoil ground truth, initial vertex counts, cached rows and features
+                d.src_of_env, d.nv0_of = self._airfoil_dev.data_ptr(), self._nv0_dev.data_ptr()
         c = self._init_cache
-        if c.get("x") is None:      # node features of the initial state (what an environment shows right after its reset)
-            xi = torch.empty((1, N, 2 + 3 * S), dtype=torch.float32, device=self.device)
-            _lib.check(self.lib.mdq_state_features(1, N, S, self.NV, self.NP, self._x0_dev.data_ptr(), c["u"].data_ptr(),
+        if c.get("x") is None:      # node features of the initial states (what an environment shows right after its reset)
+            xi = torch.empty((self.A, N, 2 + 3 * S), dtype=torch.float32, device=self.device)
+            _lib.check(self.lib.mdq_state_features(self.A, N, S, self.NV, self.NP, self._x0_dev.data_ptr(), c["u"].data_ptr(),
                                                    c["p"].data_ptr(), c["dev"]["n_closest"].data_ptr(),
                                                    c["dev"]["nsel"].data_ptr(), xi.data_ptr(), _lib.stream_ptr()),
                        "mdq_state_features")
@@ -1029,6 +1171,7 @@ class VecEnv2DAirfoil:
         d.n_rows = n
         for t in range(n):
             d.dst[t], d.src[t], d.row_bytes[t] = ra["dst"][t], ra["src"][t], ra["nbytes"][t]
+            d.src_stride[t] = ra["stride"][t]
             d.handover_dst[t], d.handover_off[t], d.handover_bytes[t] = None, 0, 0
         if not self.auto_reset:                        # nothing is restored: the rows stay as hand-over sources only
             for t in range(n):
@@ -1127,8 +1270,8 @@ class VecEnv2DAirfoil:
         self.new_drags, self.new_lifts = got["drag"], got["lift"]
         last_done = out["dones"][-1] if K and self.auto_reset else None
         if last_done is not None and last_done.any():      # (restarted environments: the cached initial forces, like step())
-            self.new_drags[last_done] = self._init_cache["drags"]
-            self.new_lifts[last_done] = self._init_cache["lifts"]
+            self.new_drags[last_done] = self._cached(self._init_cache["drags"], last_done)
+            self.new_lifts[last_done] = self._cached(self._init_cache["lifts"], last_done)
             # ... and their interpolated snapshots: `mdq_env_finish` leaves them alone inside a rollout (every step
             # interpolates again before anything reads them); whoever reads the state after the LAST step - get_state(), a
             # host-driven step() - must find the initial fields in the rows of the environments that step reset
@@ -1137,8 +1280,7 @@ class VecEnv2DAirfoil:
             dst = (C.c_void_p * 2)(self.u.data_ptr(), self.p.data_ptr())
             src = (C.c_void_p * 2)(c["u"].data_ptr(), c["p"].data_ptr())
             nb = (C.c_int64 * 2)(self.u[0].numel() * 8, self.p[0].numel() * 8)
-            _lib.check(self.lib.mdq_restore_rows(2, dst, src, nb, int(ti.numel()), ti.data_ptr(), _lib.stream_ptr()),
-                       "mdq_restore_rows")
+            self._restore_rows(dict(n=2, dst=dst, src=src, nbytes=nb, stride=(C.c_int64 * 2)(nb[0], nb[1])), int(ti.numel()), ti)
         self._deferred_mirror = None
         return out
 

@@ -24,7 +24,9 @@ import yaml
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", required=True)
+    ap.add_argument("--config", required=True, action="append",
+                    help="yaml config; repeat it to train ONE policy on several airfoils (their configs may differ only in the "
+                         "mesh, gt_*, u / p and plot_dir; global env id g steps airfoil g mod A)")
     ap.add_argument("--gpus", type=int, default=0,
                     help="N > 1 without a launcher (WORLD_SIZE unset): this process becomes the parent of N rank processes "
                          "(meshdqn_amd/launcher.py: 127.0.0.1 rendezvous, every rank watched, a dying rank ends the job)")
@@ -64,10 +66,11 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} and the launcher's WORLD_SIZE={os.environ['WORLD_SIZE']} disagree")
     from meshdqn_amd.env import Env2DAirfoil
     from meshdqn_amd.trainer import DistContext, DQNTrainer, TrainingLog, train_loop_device, train_loop_vec
-    from meshdqn_amd.vec_env import VecEnv2DAirfoil
+    from meshdqn_amd.vec_env import VecEnv2DAirfoil, airfoil_assignment, check_airfoil_configs
     import torch
     torch.set_num_threads(1)   # (many-core hosts under a CPU quota: the CPU-side tensor ops are tiny, no intra-op pool)
-    cfg = yaml.safe_load(open(args.config))
+    cfgs = [yaml.safe_load(open(path)) for path in args.config]
+    cfg = cfgs[0]
     ctx = DistContext()
     opt = cfg.get("optimizer", {})          # reference yaml sections: optimizer / epsilon (configs/ray_ys930.yaml)
     eps = cfg.get("epsilon", {})
@@ -88,9 +91,18 @@ def main():
         if steps_done0 is not None and len(steps_done0) != args.envs:      # other batch size: restart the counters at the mean
             steps_done0 = np.full(args.envs, int(np.mean(steps_done0)), np.int64)
     prefix = "restart_" * restart_num
-    base = Env2DAirfoil(cfg, compute_device=ctx.device)          # ground truth + snapshots (the reference's first reset())
-    venv = VecEnv2DAirfoil(cfg, args.envs, compute_device=ctx.device, base_env=base, flow_steps=args.flow_steps,
-                           flow_overlap=args.flow_steps > 0)
+    if len(cfgs) == 1:
+        base = Env2DAirfoil(cfg, compute_device=ctx.device)      # ground truth + snapshots (the reference's first reset())
+        venv = VecEnv2DAirfoil(cfg, args.envs, compute_device=ctx.device, base_env=base, flow_steps=args.flow_steps,
+                               flow_overlap=args.flow_steps > 0)
+    else:
+        # one policy over several airfoils: global env id g = rank * envs + b steps airfoil g mod A (every rank's block of
+        # ids sees every airfoil); one base environment (ground truth + snapshots) per airfoil
+        check_airfoil_configs(cfgs)
+        bases = [Env2DAirfoil(c, compute_device=ctx.device) for c in cfgs]
+        venv = VecEnv2DAirfoil(cfgs, args.envs, compute_device=ctx.device, base_env=bases, flow_steps=args.flow_steps,
+                               flow_overlap=args.flow_steps > 0,
+                               airfoil_of_env=airfoil_assignment(args.envs, len(cfgs), ctx.rank * args.envs))
     log = TrainingLog(args.save_dir, restart=args.restart, restart_num=restart_num) if ctx.rank == 0 else None
 
     def checkpoint(step, steps_done):
@@ -142,6 +154,8 @@ def main():
         checkpoint(args.steps, out["steps_done"])
         np.save(os.path.join(args.save_dir, prefix + "step_rewards.npy"), out["rewards"])
         yaml.safe_dump(cfg, open(os.path.join(args.save_dir, "config.yaml"), "w"))
+        for a, c in enumerate(cfgs[1:], 1):      # (several airfoils: config.yaml is airfoil 0's, config_<a>.yaml the others')
+            yaml.safe_dump(c, open(os.path.join(args.save_dir, f"config_{a}.yaml"), "w"))
         print(f"ranks {ctx.world}: {args.steps} batched steps x {args.envs} envs/rank, mean reward {out['rewards'].mean():.4f}")
         if ctx.backend:
             print(f"process group: backend {ctx.backend}, {ctx.world} rank(s)")
