@@ -552,8 +552,15 @@ typedef struct mdq_interp_desc {
 
 /*
  * Interpolate S stored (u, p) snapshots of the ORIGINAL mesh onto the P2 / P1 dof points of B
- * coarsened meshes: point location (containing cell, else nearest = extrapolation) + basis evaluation.
+ * coarsened meshes: point location (containing cell) + basis evaluation.
  * Replaces `v_func.interpolate(original_u)` / `p_func.interpolate(original_p)` (Env2DAirfoil.py:556-568).
+ * A point in no cell is extrapolated from the least violated candidate of its grid bin (bin-local: the bin
+ * clamped to the grid outside the grid's box, the nearest-centroid cell in an empty bin), not from the mesh's
+ * closest cell.  The environment only meets round-off cases: over the P2 dof points of both golden episodes
+ * (295 248 points) 1.4 % lie in no cell, each by at most 1.9e-15 in barycentric coordinates (points on shared
+ * or boundary edges).  out_cell[b][k] is the cell used, in [0, src_nt).
+ * Returns non-zero (mdq_last_error) and launches nothing when B, S or NP <= 0, when `sparse` lacks its
+ * target-mesh arrays, or when only one of srcs / src_of_env is set.
  */
 MDQ_API int mdq_interpolate_snapshots(const mdq_interp_desc* d, void* stream);
 

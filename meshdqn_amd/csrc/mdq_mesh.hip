@@ -10,8 +10,14 @@ namespace mdq_mesh {
 
 // One thread per target point: walk the candidate cells of its grid bin (ascending cell id), take the
 // first cell whose barycentric coordinates are all >= 0, otherwise the candidate with the smallest
-// violation (extrapolation from the nearest cell, `allow_extrapolation=True`), then evaluate all
-// snapshots with the P2 / P1 bases of that cell.
+// violation, then evaluate all snapshots with the P2 / P1 bases of that cell.
+// Outside every cell the choice is bin-local: the least violated candidate of the point's bin (beyond the
+// far field the bin clamped to the grid's edge; deep in the airfoil an empty bin, which holds only the cell
+// with the centroid nearest to its centre), not the mesh's closest cell of DOLFIN's `allow_extrapolation`;
+// the values are that cell's polynomials, extrapolated.  The environment never reaches beyond round-off:
+// of the P2 dof points of both golden episodes (154 752 and 140 496 points, 48 coarsened meshes each),
+// 1.6 % and 1.2 % lie in no cell, all on shared or boundary edges, outside by at most 1.9e-15 in
+// barycentric coordinates (tests/test_interp_probe_gpu.py).
 __global__ __launch_bounds__(256) void interpolate_kernel(mdq_interp_desc d) {
   const int b = blockIdx.y;
   // the source of this environment (workgroup-uniform): the descriptor's own fields, or - a batch over several airfoils -

@@ -80,7 +80,7 @@ class Function:
         self.name = name
 
     def set_allow_extrapolation(self, flag: bool):
-        pass  # evaluation always extrapolates from the nearest cell (see mesh_ops.interpolate)
+        pass  # evaluation always extrapolates, bin-locally (see interpolate_kernel in csrc/mdq_mesh.hip)
 
     def vertex_values(self) -> np.ndarray:
         """Values at the mesh vertices = the vertex dofs (P2 vertex dofs come first)."""
