@@ -36,6 +36,23 @@ def smooth_coords(topo: MeshTopology, iterations: int = 50, coords: np.ndarray |
     return x
 
 
+def pd_device_tables(d, B: int, NV: int, device, cap: dict, tables: dict | None = None) -> dict:
+    """The pd_* tables `mdq_ipcs_factorize_pressure` fills, for B environments of NV vertices at the capacities `cap`
+    (`IpcsBatch.PD_DEVICE_CAP`): allocated unless `tables` are given, their pointers and the six capacities set on the
+    descriptor `d`.  Returns the tables."""
+    if tables is None:
+        i32, f64 = torch.int32, torch.float64
+        z = lambda n, dt: torch.zeros((B, n), dtype=dt, device=device)   # noqa: E731
+        tables = dict(pd_hdr=z(4, i32), pd_node=z(NV, i32), pd_meta=z(cap["NPART"] * 6, i32), pd_rowblk=z(NV, i32),
+                      pd_W=z(cap["NPW"], f64), pd_F=z(cap["NPF"], f64), pd_gidx=z(cap["NPGI"], i32),
+                      pd_Sinv=z(cap["NPS"], f64), pd_gk_ptr=z(NV + 1, i32), pd_gk_col=z(cap["NPGK"], i32),
+                      pd_gk_val=z(cap["NPGK"], f64))
+    for k, a in tables.items():
+        setattr(d, k, a.data_ptr())
+    d.NPART, d.NPW, d.NPF, d.NPGI, d.NPS, d.NPGK = (cap[k] for k in ("NPART", "NPW", "NPF", "NPGI", "NPS", "NPGK"))
+    return tables
+
+
 class IpcsBatch:
     """Device-resident batch of Taylor-Hood IPCS problems."""
 
@@ -125,6 +142,7 @@ class IpcsBatch:
         h["sl1_off"] = stack("sl1_off", (NV // 64 + 2,), np.int32)
         h["sl1_col"] = stack("sl1_col", (NSE1,), np.int32)
         NCH = (NT + 1023) // 1024
+        self._NRL = self._rl_flags = 0      # row lists of the element-tile modes: capacity, first / last-touch bits in the row words
         if N2 > 4096:
             # capacity beyond the packed words (dof ids of 12 bits): the kernels read plain tile positions for EVERY mesh of
             # the batch (mode 5: element tiles with global vectors), also for the ones that would fit the packed form
@@ -239,8 +257,7 @@ class IpcsBatch:
             d.mf_tptr = d.mf_scat = d.mf_rlist = d.mf_rcnt = d.mf_lpos = None
         d.work_doubles = nwork
         d.status = self.status.data_ptr()
-        d.NRL = getattr(self, "_NRL", 0)
-        d.rl_flags = getattr(self, "_rl_flags", 0)
+        d.NRL, d.rl_flags = self._NRL, self._rl_flags
         d.pd_enabled = 0
         # Krylov pressure solve of mode 3: degree of the Chebyshev polynomial preconditioner (0, default: the plain Jacobi-CG
         # kernel).  Measured on ys930 (tools/time_pcg.py): iterations 154 -> 95 / 67 / 52 / 37 / 30 for degree 2 / 3 / 4 / 6 / 8,
@@ -260,6 +277,9 @@ class IpcsBatch:
         self.pressure_direct = "device" if pressure_direct == "device" else bool(pressure_direct)
         self.pressure_parts = int(pressure_parts)
         self._pd_cache = {}
+        self.pds = self.pd_cap = None               # host factors and their capacities (`_factorize_pressure`)
+        self._pd_dev = self.pd_status = None        # device-built factors and their status words (`factorize_pressure_device`)
+        self._inlet = self._gx_host = None          # inlet dofs + host copy of the Dirichlet values (`update_inflow`)
 
     # ------------------------------------------------------------------
     @staticmethod
@@ -345,21 +365,11 @@ class IpcsBatch:
         solve phase reads and switches the descriptor to the direct solve.  Needs the operators' set-up data (after
         `assemble()` or `mdq_ipcs_setup_matfree`).  `self.pd_status` (device int32 [B]): 0, or < 0 where a mesh exceeds
         the kernel's limits (that environment keeps the Krylov solve)."""
-        d, B, NV, dev = self.desc, self.B, self.cap["NV"], self.device
-        if getattr(self, "_pd_dev", None) is None:
-            cap = self.PD_DEVICE_CAP
-            i32, f64 = torch.int32, torch.float64
-            z = lambda n, dt: torch.zeros((B, n), dtype=dt, device=dev)   # noqa: E731
-            self._pd_dev = dict(pd_hdr=z(4, i32), pd_node=z(NV, i32), pd_meta=z(cap["NPART"] * 6, i32), pd_rowblk=z(NV, i32),
-                                pd_W=z(cap["NPW"], f64), pd_F=z(cap["NPF"], f64), pd_gidx=z(cap["NPGI"], i32),
-                                pd_Sinv=z(cap["NPS"], f64), pd_gk_ptr=z(NV + 1, i32), pd_gk_col=z(cap["NPGK"], i32),
-                                pd_gk_val=z(cap["NPGK"], f64))
-            self.pd_status = torch.zeros(B, dtype=i32, device=dev)
-        for k, a in self._pd_dev.items():
-            self.t[k] = a
-            setattr(d, k, a.data_ptr())
-        cap = self.PD_DEVICE_CAP
-        d.NPART, d.NPW, d.NPF, d.NPGI, d.NPS, d.NPGK = (cap[k] for k in ("NPART", "NPW", "NPF", "NPGI", "NPS", "NPGK"))
+        d = self.desc
+        if self.pd_status is None:
+            self.pd_status = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self._pd_dev = pd_device_tables(d, self.B, self.cap["NV"], self.device, self.PD_DEVICE_CAP, self._pd_dev)
+        self.t.update(self._pd_dev)
         _lib.check(self.lib.mdq_ipcs_factorize_pressure(C.byref(d), self.pd_status.data_ptr(), _lib.stream_ptr(stream)),
                    "mdq_ipcs_factorize_pressure")
         d.pd_enabled = 1
@@ -370,7 +380,7 @@ class IpcsBatch:
         the boundary conditions): new Dirichlet values profile(x, y, t) at the inlet dofs of every environment, then the
         vectors that depend on them (the lifting vectors A1[:, bc] g and M[:, bc] g) rebuilt on the device by
         `mdq_ipcs_setup_matfree` (which leaves the operators' other data as they are: same mesh)."""
-        if not hasattr(self, "_inlet"):
+        if self._inlet is None:
             self._inlet = []
             for t_, p_ in zip(self.topos, self.per):
                 d = t_.boundary_conditions(p_["coords"])["inlet_dofs"]
@@ -522,7 +532,7 @@ class IpcsBatch:
             napply = 2 + 2 * iu + 2 + im  # rhs1, A x0, 2 per BiCGStab it, rhs3, M x0, 1 per CG it
             per_it_vec = 32.0 * n2 * iu
             state = (16.0 * n2 * 6 + 8.0 * nv * 6) + 12.0 * nt * 3 * 2 + 25.0 * n2
-            if getattr(self, "pds", None) is not None and self.desc.pd_enabled:
+            if self.pds is not None and self.desc.pd_enabled:
                 q = self.pds[b]
                 prs = 8.0 * (q["W"].size + q["F"].size + q["Sinv"].size + q["gk_val"].size) + 4.0 * (
                     q["gk_col"].size + 2 * nv + q["gidx"].size)
@@ -553,7 +563,7 @@ class IpcsBatch:
             vec = (15.0 * iu + 8.0 * im) * 16.0 * n2
             rhs = 3 * (65.0 + 112.0) * nt
             state = 10 * 16.0 * n2 + 4 * 8.0 * nv
-            if getattr(self, "pds", None) is not None and self.desc.pd_enabled:
+            if self.pds is not None and self.desc.pd_enabled:
                 q = self.pds[b]
                 prs = 8.0 * (q["W"].size + q["F"].size + q["Sinv"].size + q["gk_val"].size) + 4.0 * (
                     q["gk_col"].size + 2 * nv + q["gidx"].size)

@@ -27,6 +27,7 @@ import torch
 
 from . import _lib
 from .env import Env2DAirfoil
+from .flow_leg import FlowLeg, check_flow_forces
 from .mesh_ops import (DeviceTopologyBatch, HostTopologyBatch, remesh_batch, remesh_batch_gpu, remesh_workspace, smooth_batch_gpu,
                        smooth_env_gpu)
 
@@ -92,7 +93,7 @@ def airfoil_assignment(num_envs: int, n_airfoils: int, first_env: int = 0) -> np
 
 
 class VecEnv2DAirfoil:
-    FLOW_NRL = 4032         # row capacity of a chunk's list in the device-built tile maps (the kernels' LDS stage holds 4064 rows)
+    FLOW_NRL = FlowLeg.NRL
 
     def __init__(self, config, num_envs: int, compute_device="cuda", nthreads: int = 0, base_env=None,
                  auto_reset: bool = True, emax: int = 1536, flow_steps: int = 0, flow_rtol: float = 1e-10,
@@ -214,7 +215,7 @@ class VecEnv2DAirfoil:
         self.topo = HostTopologyBatch(B, NV, NT, self.NE, self.NAF, N, self.EMAX, self.polygon,
                                       ipcs=self.flow_steps > 0 and not self.gpu_topology, nse1_cap=nse1_cap,
                                       nbo_cap=nbo_cap, airfoil=af)
-        self.dtopo = None
+        self.dtopo = ftopo = None
         if self.gpu_topology:
             self.dtopo = DeviceTopologyBatch(B, NV, NT, self.NE, self.NAF, N, self.EMAX, self.polygon, self.device,
                                              ipcs=self.flow_steps > 0 and not self.flow_overlap, nse1_cap=nse1_cap, nbo_cap=nbo_cap,
@@ -222,11 +223,17 @@ class VecEnv2DAirfoil:
             if self.flow_overlap:
                 # the flow stream's own engine: a private copy of the meshes, the full topology (with the IPCS index data,
                 # which only the flow needs: 0.19 ms less on the critical path) and the IPCS step run there
-                self._ftopo = DeviceTopologyBatch(B, NV, NT, self.NE, self.NAF, N, self.EMAX, self.polygon, self.device,
-                                                  ipcs=True, nse1_cap=nse1_cap, flow_only=True, nbo_cap=nbo_cap, airfoil=af)
+                ftopo = DeviceTopologyBatch(B, NV, NT, self.NE, self.NAF, N, self.EMAX, self.polygon, self.device,
+                                            ipcs=True, nse1_cap=nse1_cap, flow_only=True, nbo_cap=nbo_cap, airfoil=af)
         self._packed_host, self._packed_ev, self._pending, self._step_pending = None, torch.cuda.Event(), None, None
         self._restore_args = {}
         self._deferred_mirror = None
+        # filled at their first use: the two result sets of the interpolation + its last launch, the rollouts' own main
+        # stream, ground truth on the device, descriptor of mdq_env_finish, page-locked buffer of rollout_end
+        self._interp_bufs = self._interp_last = self._main_stream = self._gt_drag_dev = self._fin_desc = self._rollout_host = None
+        self._interp_i, self._fin_arrive = 0, None
+        self.smooth_events = None               # (bench: a list here collects HIP event pairs around every smoothing launch)
+        self._calibrated_for, self.calibration_ms = None, []      # (`calibrate_streams`)
         self._node_ptr = torch.arange(B + 1, dtype=torch.int32, device=self.device) * N   # (constant: N rows per graph)
         # the initial meshes on the device (one row per airfoil, at the batch's row strides): source rows of the in-place
         # resets (mdq_restore_rows; several airfoils: mdq_restore_rows_src, the row of environment b's airfoil)
@@ -247,8 +254,17 @@ class VecEnv2DAirfoil:
             self._mirror_stream = torch.cuda.Stream(device=self.device)
             self._mirror_ev = torch.cuda.Event()
             self._mirror_done = torch.cuda.Event()
+        # the S3 flow leg (None without one): descriptor, arrays, the second stream and its double buffering live there
+        self.flow = None
+        self.flow_t = self.flow_iters = self.flow_status = self.flow_pd_status = None
+        self._flow_tile_maps = False
         if self.flow_steps > 0:
-            self._init_flow(base)
+            fl = self.flow = FlowLeg(self.device, self.dtopo if self.gpu_topology else self.topo, base.flow_solver, self.flow_steps,
+                                     self.flow_rtol, self.flow_pressure, self.flow_pcg_degree, ftopo)
+            self.flow_t, self.flow_iters, self.flow_status, self.flow_pd_status = fl.t, fl.iters, fl.status, fl.pd_status
+            self._flow_tile_maps = fl.tile_maps
+            self.flow_drag = np.zeros((B, self.flow_steps))
+            self.flow_lift = np.zeros((B, self.flow_steps))
         self.coords, self.cells, self.nv, self.nt, self.offset = (self.topo.coords, self.topo.cells, self.topo.nv,
                                                                    self.topo.nt, self.topo.offset)
         self.h = self.topo.h   # (device engine: only nsel / n_closest / coord_map / nedges / ne are mirrored here)
@@ -261,294 +277,18 @@ class VecEnv2DAirfoil:
         self.new_lifts = np.zeros((B, self.S))
         self.reset_all()
 
-    # ------------------------------------------------------------------
-    def _init_flow(self, base):
-        """Device arrays + descriptor(s) of the matrix-free IPCS path (mode 3, CG pressure) over the batch."""
-        dev, tp = self.device, (self.dtopo if self.gpu_topology else self.topo)
-        if self.flow_overlap:
-            tp = self._ftopo
-        B, NV, NT, NE, NP = self.B, self.NV, self.NT, self.NE, self.NP
+    @property
+    def _flow_stream(self):
+        """Overlap mode: the stream the flow legs run on (assignable: stream calibration, tools)."""
+        return None if self.flow is None else self.flow.stream
 
-        def z(*shape):
-            return torch.zeros(shape, dtype=torch.float64, device=dev)
-
-        own = dict(geom=z(B, 5, NT), bo_val=z(B, tp.NBE, 4), lift1=z(B, NP, 2), lift3=z(B, NP, 2), idiag1=z(B, NP, 2),
-                   sdiagM=z(B, NP), sdiagK=z(B, NV), K1s=z(B, tp.NSE1), u_n=z(B, NP, 2), p_n=z(B, NV))
-        nwork = int(self.lib.mdq_ipcs_workspace_doubles(B, NV, NT, NE))
-        own["work"] = z(nwork)
-        fs = base.flow_solver
-        if self.gpu_topology:   # the device engine's outputs ARE the descriptor's index arrays
-            index_sets = [dict(tp.ti)]
-        else:
-            index_sets = [{k: torch.from_numpy(a).to(dev) for k, a in tp.hi.items()}]
-        self.flow_descs, self.flow_ts = [], []
-        for idx in index_sets:
-            t = dict(idx)
-            t.update(own)
-            d = _lib.IpcsDesc()
-            d.B, d.NV, d.NT, d.NE, d.N2, d.NAF = B, NV, NT, NE, NP, self.NAF
-            d.NSE1, d.NBO, d.NBE = tp.NSE1, tp.NBO, tp.NBE
-            d.mu, d.rho, d.dt, d.rtol = fs.mu, fs.rho, fs.dt_value, self.flow_rtol
-            d.maxit_u, d.maxit_p, d.maxit_m = 200, 4000, 200
-            # mode 3 (LDS-resident vectors) on the lab meshes; a mesh beyond its limits (the red-refined ones): auto, i.e. the
-            # element tiles with global vectors (mode 5, here without tile maps: the dof <- slot lists of the topology engine)
-            d.mode, d.pd_enabled = (3 if NP <= 3584 else -1), 0
-            d.pcg_degree = int(getattr(self, "flow_pcg_degree", 0))
-            for name, _typ in _lib.IpcsDesc._fields_:
-                if name in t:
-                    setattr(d, name, t[name].data_ptr())
-            d.work_doubles = nwork
-            # meshes beyond the LDS-resident modes (auto: the element tiles, modes 5 / 7): the tile maps of every coarsened mesh are
-            # built on the device in front of the IPCS step (mdq_ipcs_build_tile_maps: row lists + packed local maps) - without
-            # them the element results of every operator application go through 0.6 MB of global scratch per environment
-            # (MDQ_NO_DEVICE_TILE_MAPS=1: that path, A / B switch)
-            if NP > 3584 and self.gpu_topology and os.environ.get("MDQ_NO_DEVICE_TILE_MAPS", "") != "1":
-                nch = (NT + 1023) // 1024
-                nrl = min(self.FLOW_NRL, NP)
-                if (nch + 4) * ((NP + 15) & ~15) + 256 <= 160 * 1024:
-                    t["mf_rlist"] = torch.zeros((B, nch, nrl, 2), dtype=torch.int32, device=dev)
-                    t["mf_rcnt"] = torch.zeros((B, nch), dtype=torch.int32, device=dev)
-                    t["mf_lpos"] = torch.zeros((B, 6, NT), dtype=torch.int32, device=dev)
-                    for k in ("mf_rlist", "mf_rcnt", "mf_lpos"):
-                        setattr(d, k, t[k].data_ptr())
-                    d.NRL, d.rl_flags = nrl, 1
-                    d.mf_scat = d.mf_tptr = None
-                    self._flow_tile_maps = True
-            self.flow_descs.append(d)
-            self.flow_ts.append(t)
-        self.flow_t, self.flow_desc = self.flow_ts[0], self.flow_descs[0]
-        if self.flow_pressure == "direct":      # outputs of mdq_ipcs_factorize_pressure (capacities: its limits)
-            from .ipcs_batch import IpcsBatch
-            cap = IpcsBatch.PD_DEVICE_CAP
-            i32, f64 = torch.int32, torch.float64
-            zz = lambda n, dt_: torch.zeros((B, n), dtype=dt_, device=dev)   # noqa: E731
-            pdt = dict(pd_hdr=zz(4, i32), pd_node=zz(NV, i32), pd_meta=zz(cap["NPART"] * 6, i32), pd_rowblk=zz(NV, i32),
-                       pd_W=zz(cap["NPW"], f64), pd_F=zz(cap["NPF"], f64), pd_gidx=zz(cap["NPGI"], i32),
-                       pd_Sinv=zz(cap["NPS"], f64), pd_gk_ptr=zz(NV + 1, i32), pd_gk_col=zz(cap["NPGK"], i32),
-                       pd_gk_val=zz(cap["NPGK"], f64))
-            for t, d in zip(self.flow_ts, self.flow_descs):
-                t.update(pdt)
-                for k, a in pdt.items():
-                    setattr(d, k, a.data_ptr())
-                d.NPART, d.NPW, d.NPF, d.NPGI, d.NPS, d.NPGK = (cap[k] for k in ("NPART", "NPW", "NPF", "NPGI", "NPS", "NPGK"))
-                d.pd_enabled = 1
-            self.flow_pd_status = torch.zeros(B, dtype=i32, device=dev)
-        self.flow_iters = torch.zeros((B, 3), dtype=torch.int32, device=dev)
-        # sticky status words of the flow legs (mdq_ipcs_desc.status, ABI 7): a leg that gave up - team barrier time-out of the
-        # two-workgroup operator modes - is an ERROR at the next read-back (rollout_end / flow_wait), not a silent NaN
-        self.flow_status = torch.zeros(B, dtype=torch.int32, device=dev)
-        for d in self.flow_descs:
-            d.status = self.flow_status.data_ptr()
-        self.flow_drag = np.zeros((B, self.flow_steps))
-        self.flow_lift = np.zeros((B, self.flow_steps))
-        if self.flow_overlap:
-            from .streams import role_streams
-            self._flow_stream = role_streams(dev)["flow"]   # (the process's flow stream: fixed creation order, one probe)
-            self._flow_ready = torch.cuda.Event()
-            self._late_handover = os.environ.get("MDQ_LATE_HANDOVER", "") == "1"      # (A / B switch of the early mesh hand-over)
-            # the last IPCS kernel writes drag / lift of the leg straight into the page-locked result buffers (2 KB over the bus)
-            # instead of two device-to-host copies behind it (12 us of the flow chain); MDQ_FLOW_RESULT_COPY=1: the copies
-            self._flow_direct_results = os.environ.get("MDQ_FLOW_RESULT_COPY", "") != "1"
-            self._handover_in_kernel = os.environ.get("MDQ_HANDOVER_COPY", "") != "1"    # (A / B: the copy launch of the first version)
-            # page-locked result buffers (two: the results of step k are read while step k + 1 is in flight) + events
-            self._flow_res = [dict(host=torch.zeros((2, B, self.flow_steps), dtype=torch.float64, pin_memory=True),
-                                   done=torch.cuda.Event()) for _ in range(2)]
-            self._flow_n = 0          # flows launched
-            self._flow_prev = None
-            # TWO sets of the flow engine's inputs (private meshes + start fields): the main stream fills set k % 2 for
-            # flow k while flow k - 1 still reads the other one.  With one set the hand-over was a serial chain - flow
-            # k - 1 ends -> main copies -> flow k starts, two event round trips + the copy per step on the flow's
-            # critical path - and the S3 step lasted (flow leg + ~70 us) instead of max(main chain, flow leg).
-            ft, t0 = self._ftopo, self.flow_ts[0]
-            self._flow_in = [dict(coords=ft.coords, cells=ft.cells, nv=ft.nv, nt=ft.nt, u_n=t0["u_n"], p_n=t0["p_n"],
-                                  # the main engine's cell dofs / edge counts of the same meshes: the flow's topology run takes
-                                  # its edge numbering from them (no second hash pass)
-                                  cell_dofs=torch.zeros_like(self.dtopo.t["cell_dofs"]), ne=torch.zeros_like(self.dtopo.t["ne"]))]
-            self._flow_in.append({k: torch.zeros_like(a) for k, a in self._flow_in[0].items()})
-
-    def _flow(self, keep, out_u, out_p):
-        """`flow_steps` IPCS steps on every (coarsened) mesh, warm-started from the interpolated last snapshot."""
-        t, d = self.flow_ts[0], self.flow_descs[0]
-        if not self.gpu_topology:
-            for kk in self.topo.hi:
-                t[kk].copy_(self.topo.pinned[kk], non_blocking=True)
-        if self.flow_overlap:
-            return self._flow_overlapped(out_u, out_p)
-        for kk in ("coords", "cell_dofs", "af_facets", "nv", "nt", "ne", "naf"):
-            setattr(d, kk, keep[kk].data_ptr())
-        return self._flow_launch(t, d, keep, out_u, out_p)
-
-    def _flow_reset(self, d):
-        # no initial-guess history on a new mesh: the counters inside the workspace (not a fill of its 100 MB) + the
-        # iteration counters, one small launch
-        _lib.check(self.lib.mdq_ipcs_reset_history(C.byref(d), self.flow_iters.data_ptr(), _lib.stream_ptr()),
-                   "mdq_ipcs_reset_history")
-
-    def _flow_launch(self, t, d, keep, out_u, out_p, before_evolve=None, reset=True, out=None):
-        """`reset=False`: the caller has already enqueued `_flow_reset` (ahead of a wait: off the leg's critical path).
-        `out` = (drag, lift) tensors the kernels write - page-locked host tensors are written over the bus directly, which
-        saves the two result copies at the end of the leg."""
-        if out_u is not None:
-            t["u_n"].copy_(out_u[:, self.S - 1])
-            t["p_n"].copy_(out_p[:, self.S - 1])
-        if reset:
-            self._flow_reset(d)
-        _lib.check(self.lib.mdq_ipcs_setup_matfree(C.byref(d), _lib.stream_ptr()), "mdq_ipcs_setup_matfree")
-        if getattr(self, "_flow_tile_maps", False):
-            _lib.check(self.lib.mdq_ipcs_build_tile_maps(C.byref(d), None, _lib.stream_ptr()), "mdq_ipcs_build_tile_maps")
-        if self.flow_pressure == "direct":
-            _lib.check(self.lib.mdq_ipcs_factorize_pressure(C.byref(d), self.flow_pd_status.data_ptr(), _lib.stream_ptr()),
-                       "mdq_ipcs_factorize_pressure")
-        if out is not None:
-            drag, lift = out
-        else:
-            drag = torch.empty((self.B, self.flow_steps), dtype=torch.float64, device=self.device)
-            lift = torch.empty_like(drag)
-        if before_evolve is not None:       # (the set-up above reads the mesh only; the warm start is needed from here on)
-            before_evolve()
-        _lib.check(self.lib.mdq_ipcs_evolve(C.byref(d), self.flow_steps, drag.data_ptr(), lift.data_ptr(),
-                                            self.flow_iters.data_ptr(), _lib.stream_ptr()), "mdq_ipcs_evolve")
-        self._flow_keep = keep       # device buffers the descriptor points at
-        return drag, lift
-
-    def _flow_handover(self, out_u, out_p):
-        """First half of the overlapped flow leg: the input set the flow stream will read (filled alternately: flow k - 1
-        may still be reading the other one) and the (destination, source) pairs of the hand-over - the meshes, the main
-        engine's edge numbering and the warm start (last interpolated snapshot), copied BEFORE an in-place reset of a
-        terminated environment rewrites them."""
-        dt = self.dtopo
-        main = torch.cuda.current_stream(self.device)
-        fin = self._flow_in[self._flow_n % 2]
-        if self._flow_n >= 2 and self._flow_prev is not None:          # flow k - 2 read this input set (long finished)
-            main.wait_event(self._flow_res[self._flow_n % 2]["done"])
-        su, sp_ = out_u[:, self.S - 1], out_p[:, self.S - 1]
-        pairs = [(fin["coords"], dt.coords), (fin["cells"], dt.cells), (fin["nv"], dt.nv), (fin["nt"], dt.nt), (fin["u_n"], su), (fin["p_n"], sp_),
-                 (fin["cell_dofs"], dt.t["cell_dofs"]), (fin["ne"], dt.t["ne"])]
-        return fin, pairs
-
-    def _flow_handover_target(self):
-        """Before the main topology run of a device-resident step: the flow input set this step fills becomes the second
-        output set of the topology kernel (meshes + edge numbering written by that launch itself: no copy launch on the main
-        chain, 6 us + two event gaps per step)."""
-        main = torch.cuda.current_stream(self.device)
-        fin = self._flow_in[self._flow_n % 2]
-        if self._flow_n >= 2 and self._flow_prev is not None:          # flow k - 2 read this input set (long finished)
-            main.wait_event(self._flow_res[self._flow_n % 2]["done"])
-        self.dtopo.set_handover(fin["coords"], fin["cells"], fin["nv"], fin["nt"], fin["cell_dofs"], fin["ne"])
-
-    def _flow_handover_mesh(self):
-        """Device-resident step, EARLY half of the hand-over: meshes + the main engine's edge numbering are copied (one
-        launch on the main stream) right after the main topology run, so that the flow stream can derive its own topology
-        and the operator set-up while the main stream still interpolates / evaluates the step - handing everything over
-        inside `mdq_env_finish` left the flow stream idle for ~60 us of every step (profiles/r04_timeline_s3_step.txt).
-        The warm start (u / p windows) follows in `mdq_env_finish` as before."""
-        dt = self.dtopo
-        main = torch.cuda.current_stream(self.device)
-        fin = self._flow_in[self._flow_n % 2]
-        if not self._handover_in_kernel and self._flow_n >= 2 and self._flow_prev is not None:   # flow k - 2 read this input set
-            main.wait_event(self._flow_res[self._flow_n % 2]["done"])
-        if self._handover_in_kernel:
-            # the main topology kernel has written this input set itself (`_flow_handover_target`, mdq_topo_handover)
-            dt.set_handover()                    # (this launch only: a later host-driven step() must not write there)
-            if getattr(self, "_flow_mesh_ready", None) is None:
-                self._flow_mesh_ready = torch.cuda.Event()
-            self._flow_mesh_ready.record(main)
-            self._flow_fin_early = fin
-            return
-        pairs = [(fin["coords"], dt.coords), (fin["cells"], dt.cells), (fin["nv"], dt.nv), (fin["nt"], dt.nt),
-                 (fin["cell_dofs"], dt.t["cell_dofs"]), (fin["ne"], dt.t["ne"])]
-        n = len(pairs)
-        vp, i64 = C.c_void_p * n, C.c_int64 * n
-        nb = [src.numel() * src.element_size() for _, src in pairs]
-        for dst, src in pairs:
-            if dst.shape != src.shape or dst.dtype != src.dtype or not dst.is_contiguous() or not src.is_contiguous():
-                raise ValueError("flow hand-over: buffers of different shapes")
-        _lib.check(self.lib.mdq_copy_strided(n, vp(*[d_.data_ptr() for d_, _ in pairs]), vp(*[s_.data_ptr() for _, s_ in pairs]),
-                                             i64(*([1] * n)), i64(*nb), i64(*nb), i64(*nb), _lib.stream_ptr()), "mdq_copy_strided")
-        if getattr(self, "_flow_mesh_ready", None) is None:
-            self._flow_mesh_ready = torch.cuda.Event()
-        self._flow_mesh_ready.record(main)
-        self._flow_fin_early = fin
-
-    def _flow_start(self, fin, mesh_early=False):
-        """Second half: the hand-over is enqueued on the main stream - topology (edges from the main engine), matrix-free
-        set-up and the IPCS step(s) follow on the flow stream; results land in page-locked memory.  `mesh_early`: the
-        meshes were handed over by `_flow_handover_mesh` - topology and set-up wait for THAT, only the IPCS step for the
-        rest."""
-        ft = self._ftopo
-        t, d = self.flow_ts[0], self.flow_descs[0]
-        main = torch.cuda.current_stream(self.device)
-        self._flow_ready.record(main)
-        keep = dict(coords=fin["coords"], cell_dofs=ft.t["cell_dofs"], af_facets=ft.t["af_facets"], nv=fin["nv"], nt=fin["nt"],
-                    ne=ft.t["ne"], naf=ft.t["naf"], u_n=fin["u_n"], p_n=fin["p_n"])
-        for kk, v in keep.items():
-            setattr(d, kk, v.data_ptr())
-        for kk in ("coords", "cells", "nv", "nt"):            # the flow's topology engine reads the same set
-            setattr(ft.desc, kk, fin[kk].data_ptr())
-        ft.take_edges_from(fin["cell_dofs"], fin["ne"])
-        t["u_n"], t["p_n"] = fin["u_n"], fin["p_n"]
-        res = self._flow_res[self._flow_n % 2]
-        direct = self._flow_direct_results and tuple(res["host"][0].shape) == (self.B, self.flow_steps)
-        with torch.cuda.stream(self._flow_stream):
-            self._flow_reset(d)                  # (behind flow k - 1, in FRONT of the wait for this step's meshes)
-            self._flow_stream.wait_event(self._flow_mesh_ready if mesh_early else self._flow_ready)
-            fe = getattr(self, "flow_events", None)     # (tools: HIP events around the leg, on the flow stream)
-            if fe is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            if getattr(self, "_flow_tile_maps", False):
-                # the private copy's cells in a spatial order (chunks of 1 024 triangles that share their rows: what the tile maps
-                # of the IPCS step need), the main engine's cell dofs of the same cells permuted alike
-                _lib.check(self.lib.mdq_flow_sort_cells(self.B, self.NV, self.NT, fin["coords"].data_ptr(), fin["nv"].data_ptr(),
-                                                        fin["nt"].data_ptr(), fin["cells"].data_ptr(), fin["cell_dofs"].data_ptr(),
-                                                        _lib.stream_ptr()), "mdq_flow_sort_cells")
-            ft.run(check=False)                  # (same meshes, same deterministic kernel as the main stream's run)
-            drag, lift = self._flow_launch(t, d, keep, None, None,
-                                           (lambda: self._flow_stream.wait_event(self._flow_ready)) if mesh_early else None,
-                                           reset=False, out=(res["host"][0], res["host"][1]) if direct else None)
-            if fe is not None:
-                e1.record()
-                fe.append((e0, e1))
-            if not direct:
-                res["host"][0].copy_(drag, non_blocking=True)
-                res["host"][1].copy_(lift, non_blocking=True)
-            res["done"].record(self._flow_stream)
-        self._flow_prev = self._flow_n % 2
-        self._flow_n += 1
-
-    def _flow_overlapped(self, out_u, out_p):
-        """The IPCS leg on the flow stream: the meshes are copied to the flow's own engine (on the main stream, behind the
-        last flow), which derives topology + IPCS index data itself (host-driven `step()`; the device-resident step hands
-        the rows over inside `mdq_env_finish`)."""
-        fin, pairs = self._flow_handover(out_u, out_p)
-        # meshes + the warm start in ONE launch (six torch copies were ~50 us of the main chain)
-        n = len(pairs)
-        vp, i64 = C.c_void_p * n, C.c_int64 * n
-        rows, rb, ss, ds = [], [], [], []
-        for dst, src in pairs:
-            if dst.shape != src.shape or dst.dtype != src.dtype or not dst.is_contiguous():
-                raise ValueError("flow hand-over: buffers of different shapes")
-            if src.is_contiguous():
-                rows.append(1); rb.append(src.numel() * src.element_size()); ss.append(rb[-1]); ds.append(rb[-1])
-            else:                                   # a snapshot slice: contiguous per environment
-                per = src[0].numel() * src.element_size()
-                if not src[0].is_contiguous():
-                    raise ValueError("flow hand-over: rows of the source must be contiguous")
-                rows.append(src.shape[0]); rb.append(per); ss.append(src.stride(0) * src.element_size()); ds.append(per)
-        _lib.check(self.lib.mdq_copy_strided(n, vp(*[d_.data_ptr() for d_, _ in pairs]), vp(*[s_.data_ptr() for _, s_ in pairs]),
-                                             i64(*rows), i64(*rb), i64(*ss), i64(*ds), _lib.stream_ptr()), "mdq_copy_strided")
-        self._flow_start(fin)
-        return None, None
+    @_flow_stream.setter
+    def _flow_stream(self, stream):
+        self.flow.stream = stream
 
     def flow_wait(self):
         """Overlap mode: wait for the IPCS step launched last and return its (drag, lift), or None."""
-        if not self.flow_overlap or self._flow_prev is None:
-            return None
-        res = self._flow_res[self._flow_prev]
-        res["done"].synchronize()
-        fd, fl = res["host"][0].numpy().copy(), res["host"][1].numpy().copy()
-        _check_flow_forces(fd, fl, "flow_wait", self.flow_status.cpu().numpy())
-        return fd, fl
+        return None if self.flow is None else self.flow.results()
 
     # ------------------------------------------------------------------
     def _reset_env(self, b):
@@ -560,12 +300,8 @@ class VecEnv2DAirfoil:
         self.steps[b] = 0
 
     def reset_all(self):
-        if getattr(self, "flow_overlap", False) and getattr(self, "_flow_prev", None) is not None:
-            # results of a flow leg launched before the reset belong to meshes that no longer exist: the first step
-            # after a reset (or a stream calibration) reports no "previous step" forces
-            self.flow_wait()
-            self._flow_prev = None
-            self._flow_prev2 = None
+        if self.flow is not None:
+            self.flow.drop_pending()
         for b in range(self.B):
             self._reset_env(b)
         if self.gpu_topology:
@@ -695,10 +431,9 @@ class VecEnv2DAirfoil:
         # meshes and nothing reads the padding behind them (INVARIANT: rows behind nv / np2 of a set hold stale values of
         # earlier, larger meshes, not zeros) (two 45 MB fills per step were ~30 us of the main chain); the
         # set of the previous step stays intact for whoever still holds it
-        if getattr(self, "_interp_bufs", None) is None:
+        if self._interp_bufs is None:
             self._interp_bufs = [(torch.zeros((B, self.S, NP, 2), dtype=torch.float64, device=dev),
                                   torch.zeros((B, self.S, NV), dtype=torch.float64, device=dev)) for _ in range(2)]
-            self._interp_i = 0
         self._interp_i ^= 1
         out_u, out_p = self._interp_bufs[self._interp_i]
         d = _lib.InterpDesc()
@@ -741,8 +476,11 @@ class VecEnv2DAirfoil:
         self.u, self.p, self._coords_dev = out_u, out_p, t_coords
         self._dev_drag, self._dev_lift = drag, lift
         fd = fl = None
-        if self.flow_steps > 0 and not (defer_flow and self.flow_overlap):   # (deferred: handed over by mdq_env_finish)
-            fd, fl = self._flow(keep, out_u, out_p)
+        if self.flow_overlap:
+            if not defer_flow:                  # (deferred: the device-resident step hands over through mdq_env_finish)
+                self.flow.start_from_copies(out_u[:, self.S - 1], out_p[:, self.S - 1])
+        elif self.flow is not None:
+            fd, fl = self.flow.run_inline(keep, out_u[:, self.S - 1], out_p[:, self.S - 1])
             if not self.gpu_topology:
                 self.flow_drag, self.flow_lift = fd.cpu().numpy(), fl.cpu().numpy()
         if not readback:
@@ -800,15 +538,8 @@ class VecEnv2DAirfoil:
         """dict of device tensors: x (B,N,2+3S) f32, esrc/edst (sumE,) i32 local ids, edge_ptr (B+1,) i32,
         node_ptr (B+1,) i32 - directly consumable by the fused Q-network forward - plus host copies of
         n_closest / coord_map / nedges."""
-        dev, h, B, N, S = self.device, self.h, self.B, self.N, self.S
-        x = torch.empty((B, N, 2 + 3 * S), dtype=torch.float32, device=dev)
-        if self.gpu_topology:
-            nc, nsel = self.dtopo.t["n_closest"], self.dtopo.t["nsel"]
-        else:
-            nc, nsel = self.topo.upload("n_closest", dev), self.topo.upload("nsel", dev)
-        _lib.check(self.lib.mdq_state_features(B, N, S, self.NV, self.NP, self._coords_dev.data_ptr(), self.u.data_ptr(),
-                                               self.p.data_ptr(), nc.data_ptr(), nsel.data_ptr(), x.data_ptr(),
-                                               _lib.stream_ptr()), "mdq_state_features")
+        dev, h, B = self.device, self.h, self.B
+        x = self._state_features()
         ne = h["nedges"].astype(np.int64)
         edge_ptr = np.zeros(B + 1, np.int32)
         edge_ptr[1:] = np.cumsum(ne)
@@ -899,13 +630,8 @@ class VecEnv2DAirfoil:
         B, N, h = self.B, self.N, self.h
         code, status = self._step_pending
         self._step_pending = None
-        prev_flow = None
-        if self.flow_overlap:     # results of the IPCS step launched in the PREVIOUS env step (this step's is still running)
-            prev, self._flow_prev2 = getattr(self, "_flow_prev2", None), self._flow_prev
-            if prev is not None:
-                res = self._flow_res[prev]
-                res["done"].synchronize()
-                prev_flow = (res["host"][0].numpy().copy(), res["host"][1].numpy().copy())
+        # results of the IPCS step launched in the PREVIOUS env step (this step's is still running)
+        prev_flow = self.flow.results(previous=True) if self.flow_overlap else None
         self._refresh_collect()
         if status is None:
             self._mirror_done.synchronize()
@@ -946,17 +672,26 @@ class VecEnv2DAirfoil:
 
 
     # ------------------------------------------------------------------ device-resident rollout
-    def _state_device(self):
-        """`get_state` without the host: node features from device data only; the edge lists stay in the padded (B, EMAX)
-        layout the topology engine writes (`mdq_gcn_forward_padded` and `mdq_replay_step` read them as they are: no edge
-        offsets, no compaction launches)."""
-        dev, B, N, S, dt = self.device, self.B, self.N, self.S, self.dtopo
+    def _state_features(self):
+        """Node features x (B, N, 2 + 3 S) f32 of the current meshes and fields (one launch on the current stream)."""
+        dev, B, N, S = self.device, self.B, self.N, self.S
         x = torch.empty((B, N, 2 + 3 * S), dtype=torch.float32, device=dev)
+        if self.gpu_topology:
+            nc, nsel = self.dtopo.t["n_closest"], self.dtopo.t["nsel"]
+        else:
+            nc, nsel = self.topo.upload("n_closest", dev), self.topo.upload("nsel", dev)
         _lib.check(self.lib.mdq_state_features(B, N, S, self.NV, self.NP, self._coords_dev.data_ptr(), self.u.data_ptr(),
-                                               self.p.data_ptr(), dt.t["n_closest"].data_ptr(), dt.t["nsel"].data_ptr(),
-                                               x.data_ptr(), _lib.stream_ptr()), "mdq_state_features")
-        return dict(x=x, node_ptr=self._node_ptr, edge_src_pad=dt.t["edge_src"], edge_dst_pad=dt.t["edge_dst"],
-                    nedges_dev=dt.t["nedges"])
+                                               self.p.data_ptr(), nc.data_ptr(), nsel.data_ptr(), x.data_ptr(),
+                                               _lib.stream_ptr()), "mdq_state_features")
+        return x
+
+    def _state_device(self, x=None):
+        """`get_state` without the host: node features `x` (None: computed here) from device data only; the edge lists stay
+        in the padded (B, EMAX) layout the topology engine writes (`mdq_gcn_forward_padded` and `mdq_replay_step` read them
+        as they are: no edge offsets, no compaction launches)."""
+        dt = self.dtopo
+        return dict(x=self._state_features() if x is None else x, node_ptr=self._node_ptr, edge_src_pad=dt.t["edge_src"],
+                    edge_dst_pad=dt.t["edge_dst"], nedges_dev=dt.t["nedges"])
 
     def rollout_device(self, fused, steps: int, explore=None, rand_actions=None, actions=None):
         """`steps` batched env steps WITHOUT a host round trip inside a step: the Q-network forward (`fused`: a
@@ -971,7 +706,7 @@ class VecEnv2DAirfoil:
         if cur == torch.cuda.default_stream(self.device):
             # not on the legacy default stream: with the main chain there, the factorisation kernel of the flow stream
             # was measured to serialise with it (2.5 instead of 1.8 ms per batched step); a stream of the pool is fine
-            if getattr(self, "_main_stream", None) is None:
+            if self._main_stream is None:
                 from .streams import role_streams
                 self._main_stream = role_streams(self.device)["main"]
             self._main_stream.wait_stream(cur)
@@ -1074,7 +809,7 @@ class VecEnv2DAirfoil:
                   # step counters: read by every workgroup of mdq_env_finish, written to the other array (si: the current one)
                   d_steps=[torch.from_numpy(self.steps.astype(np.int32)).to(dev), torch.empty(B, dtype=i32, device=dev)], si=0,
                   err=torch.zeros(1, dtype=i32, device=dev))
-        if getattr(self, "_gt_drag_dev", None) is None:       # (A, S): row a = airfoil a
+        if self._gt_drag_dev is None:       # (A, S): row a = airfoil a
             self._gt_drag_dev = torch.from_numpy(np.ascontiguousarray(self.gt_drags, dtype=np.float64)).to(dev)
         dt.offset.copy_(torch.from_numpy(self.offset))
         ro["state"] = self._state_device()
@@ -1106,7 +841,7 @@ class VecEnv2DAirfoil:
                                       dt.t["coord_map"].data_ptr(), dt.offset.data_ptr(), ro["act"][k].data_ptr(),
                                       rem.data_ptr(), ro["code_act"].data_ptr(), self._rstat.data_ptr(),
                                       *remesh_workspace(self.device, sp(), B, NVc, NTc), sp()), "mdq_remesh_act")
-        tm = getattr(self, "smooth_events", None)     # (bench: HIP events around the launch, on this stream)
+        tm = self.smooth_events     # (bench: HIP events around the launch, on this stream)
         if tm is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -1115,34 +850,29 @@ class VecEnv2DAirfoil:
         if tm is not None:
             e1.record()
             tm.append((e0, e1))
-        flow = self.flow_steps > 0 and self.flow_overlap
-        early = flow and self.gpu_topology and not self._late_handover
+        # overlapped flow leg: the main topology run writes the meshes into the leg's free input set, `mdq_env_finish` the warm
+        # start; the leg starts on its stream behind both
+        flow = self.flow if self.flow_overlap else None
         sparse = 0 if os.environ.get("MDQ_FULL_INTERP", "") == "1" else (1 if self.flow_steps > 0 else 2)
-        self._refresh_launch(readback=False, defer_flow=True, after_topology=self._flow_handover_mesh if early else None, sparse=sparse,
-                             before_topology=self._flow_handover_target if early and self._handover_in_kernel else None)
+        self._refresh_launch(readback=False, defer_flow=True, sparse=sparse, before_topology=flow.arm_handover if flow else None,
+                             after_topology=flow.mesh_ready if flow else None)
         # ---- the end of the step in one launch
         x = torch.empty((B, N, 2 + 3 * S), dtype=torch.float32, device=self.device)
         d = self._finish_desc(ro, k, x)
-        fin = None
-        if flow and early:
-            fin = self._flow_fin_early
-            self._finish_handover(d, [(fin["u_n"], self.u[:, self.S - 1]), (fin["p_n"], self.p[:, self.S - 1])])
-        elif flow:
-            fin, pairs = self._flow_handover(self.u, self.p)
-            self._finish_handover(d, pairs)
+        if flow is not None:
+            self._finish_handover(d, flow.warm_start_pairs(self.u[:, self.S - 1], self.p[:, self.S - 1]))
         _lib.check(lib.mdq_env_finish(C.byref(d), sp()), "mdq_env_finish")
-        if fin is not None:
-            self._flow_start(fin, mesh_early=early)
+        if flow is not None:
+            flow.start()
         ro["si"] ^= 1
-        ro["state"] = dict(x=x, node_ptr=self._node_ptr, edge_src_pad=dt.t["edge_src"], edge_dst_pad=dt.t["edge_dst"],
-                           nedges_dev=dt.t["nedges"])
+        ro["state"] = self._state_device(x)
         ro["k"] = k + 1
 
     def _finish_desc(self, ro, k, x):
         """Descriptor of `mdq_env_finish` for step k of a rollout (built once per environment object; the per-step
         pointers are patched in)."""
         dt, B, N, S = self.dtopo, self.B, self.N, self.S
-        d = getattr(self, "_fin_desc", None)
+        d = self._fin_desc
         if d is None:
             d = self._fin_desc = _lib.EnvFinishDesc()
             d.B, d.N, d.S, d.NV, d.NP = B, N, S, self.NV, self.NP
@@ -1218,7 +948,7 @@ class VecEnv2DAirfoil:
     def rollout_end(self, ro):
         """The one read-back of a rollout; the host mirrors of the environments follow the device."""
         K = ro["k"]
-        last = getattr(self, "_interp_last", None)
+        last = self._interp_last
         if K and last is not None and last[1]:
             # the steps of a rollout interpolate only what they read (sparse: most edge-midpoint entries of `self.u` are skipped);
             # `self.u` / `self.p` are public - whoever reads them after the rollout (field dumps, deploy, tests, a host-driven
@@ -1247,7 +977,7 @@ class VecEnv2DAirfoil:
         flat = [t.contiguous().view(torch.uint8).reshape(-1) for _, t in parts]
         pad = [(-f.numel()) % 8 for f in flat]                  # (every part starts 8-byte aligned in the packed buffer)
         packed = torch.cat([x for f, p_ in zip(flat, pad) for x in ((f, f.new_zeros(p_)) if p_ else (f,))])
-        host = getattr(self, "_rollout_host", None)
+        host = self._rollout_host
         if host is None or host.numel() < packed.numel():
             host = self._rollout_host = torch.empty(max(packed.numel(), 1 << 16), dtype=torch.uint8, pin_memory=True)
         host[:packed.numel()].copy_(packed, non_blocking=True)
@@ -1263,7 +993,7 @@ class VecEnv2DAirfoil:
         if int(got["err"][0]) != 0:
             raise _lib.MeshDQNHipError("topology kernel failed inside rollout_device")
         if K:               # a failed flow leg is an ERROR here, not a NaN in what the caller reads later
-            _check_flow_forces(got["drag"], got["lift"], "rollout_device", got.get("flow_status"))
+            check_flow_forces(got["drag"], got["lift"], "rollout_device", got.get("flow_status"))
         self.nv[...], self.nt[...], self.offset[...], self.steps[...] = got["nv"], got["nt"], got["offset"], got["steps"]
         for k in ("nsel", "nedges", "ne", "coord_map", "n_closest"):
             h[k][...] = got[k]
@@ -1283,22 +1013,6 @@ class VecEnv2DAirfoil:
             self._restore_rows(dict(n=2, dst=dst, src=src, nbytes=nb, stride=(C.c_int64 * 2)(nb[0], nb[1])), int(ti.numel()), ti)
         self._deferred_mirror = None
         return out
-
-
-def _check_flow_forces(drag, lift, where, status=None):
-    """Raises when a flow leg reported a step it could not take: a set status word (mdq_ipcs_desc.status: the two-workgroup
-    operator modes 4 / 7 abandon a step when a team barrier times out - the partner workgroup was not resident because another
-    process or stream held its CU; csrc/mdq_ipcs.hip `team_failed`; u_n / p_n of that environment were not advanced) or
-    non-finite drag / lift (the same event seen through the forces, or a solve that diverged)."""
-    bad = ~(np.isfinite(drag) & np.isfinite(lift))
-    bad = bad.reshape(bad.shape[0], -1).any(1)
-    timed_out = np.zeros_like(bad) if status is None else (np.asarray(status) != 0)
-    if bad.any() or timed_out.any():
-        which = np.flatnonzero(bad | timed_out)
-        raise _lib.MeshDQNHipError(
-            f"{where}: the flow leg failed in environment(s) {which[:8].tolist()}{' ...' if which.size > 8 else ''}: "
-            + ("team barrier time-out of the two-workgroup IPCS modes (is another process or a CU-masked stream holding CUs? "
-               "MDQ_NO_TEAM_TILES=1 keeps one workgroup per environment)" if timed_out.any() else "non-finite drag / lift"))
 
 
 class VecEnvGroups:

@@ -973,7 +973,7 @@ def test_refined_s3_rollouts_run_whole_episodes(lib_built, tmp_path):
         out = venv.rollout_device(fused, 10, ex, ra)
         fd, fl = venv.flow_wait()
         it = venv.flow_iters.cpu().numpy()
-        rc = venv.flow_ts[0]["mf_rcnt"].cpu().numpy()
+        rc = venv.flow_t["mf_rcnt"].cpu().numpy()
         assert np.isfinite(out["rewards"]).all() and (out["codes"] == 0).all() and np.isfinite(fd).all() and np.isfinite(fl).all()
         assert (rc[:, 0] > 0).all() and rc.max() < 2400, (r0, rc.min(), rc.max())
         assert (it[:, 0] > 5).all() and (it[:, 0] < 40).all() and (it[:, 1] > 100).all() and (it[:, 1] < 260).all(), (r0, it.max(0))

@@ -29,17 +29,17 @@ for maps, deg in ((True, 0), (True, -2), (False, 0)):
         ex = np.array([rng.random(B) < 0.5 for _ in range(k)]); ra = np.array([rng.integers(0, 181, B) for _ in range(k)])
         return venv.rollout_device(fused, k, ex, ra)
     run(6)
-    venv.flow_events = []
+    venv.flow.events = []
     torch.cuda.synchronize(); t0 = time.perf_counter()
     run(10)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
-    legs = np.array([a.elapsed_time(b) for a, b in venv.flow_events])
-    venv.flow_events = None
+    legs = np.array([a.elapsed_time(b) for a, b in venv.flow.events])
+    venv.flow.events = None
     fd, fl = venv.flow_wait()
     it = venv.flow_iters.cpu().numpy().mean(0)
     line = f"maps={maps} pcg_degree={deg}: step {dt / 10 * 1e3:.3f} ms, flow leg median {np.median(legs):.3f} ms, iters {it.round(1).tolist()}, drag[0] {fd[0, 0]:.12e}"
-    if maps and getattr(venv, "_flow_tile_maps", False):
-        rc = venv.flow_ts[0]["mf_rcnt"].cpu().numpy()
+    if maps and venv._flow_tile_maps:
+        rc = venv.flow_t["mf_rcnt"].cpu().numpy()
         line += f"; rcnt min {rc.min(0).tolist()} max {rc.max(0).tolist()}, marked {(rc[:, 0] < 0).sum()} of {B}"
     print(line, flush=True)
     del venv

@@ -28,7 +28,7 @@ for r0 in range(0, STEPS, 10):
     out = venv.rollout_device(fused, 10, ex, ra)
     fd, fl = venv.flow_wait()
     it = venv.flow_iters.cpu().numpy()
-    rc = venv.flow_ts[0]["mf_rcnt"].cpu().numpy() if getattr(venv, "_flow_tile_maps", False) else None
+    rc = venv.flow_t["mf_rcnt"].cpu().numpy() if venv._flow_tile_maps else None
     done_total += int(out["dones"].sum())
     worst = max(worst, int(it[:, 1].max()))
     assert np.isfinite(out["rewards"]).all() and (out["codes"] == 0).all() and np.isfinite(fd).all()

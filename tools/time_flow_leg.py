@@ -24,20 +24,20 @@ def run(k):
     return venv.rollout_device(fused, k, ex, ra)
 run(30)
 resets = []
-_orig_reset = venv._flow_reset
-def _reset(d):
+_orig_reset = venv.flow._reset
+def _reset():
     ea = torch.cuda.Event(enable_timing=True); ea.record()
-    _orig_reset(d)
+    _orig_reset()
     eb = torch.cuda.Event(enable_timing=True); eb.record()
     resets.append((ea, eb))
-venv._flow_reset = _reset
-venv.flow_events = []
+venv.flow._reset = _reset
+venv.flow.events = []
 torch.cuda.synchronize(); t0 = time.perf_counter()
 run(50)
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
-legs = np.array([a.elapsed_time(b) for a, b in venv.flow_events]) * 1e3
-ev = venv.flow_events
-venv.flow_events = None
+legs = np.array([a.elapsed_time(b) for a, b in venv.flow.events]) * 1e3
+ev = venv.flow.events
+venv.flow.events = None
 n = min(len(ev), len(resets))
 wait = np.array([resets[k][1].elapsed_time(ev[k][0]) for k in range(5, n)]) * 1e3        # after the reset .. leg start = wait for the meshes
 rst = np.array([resets[k][0].elapsed_time(resets[k][1]) for k in range(5, n)]) * 1e3

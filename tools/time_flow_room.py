@@ -31,9 +31,12 @@ for name, kw in (("flow_steps=1 cg", dict(flow_steps=1)), ("flow_steps=2 cg", di
         torch.cuda.synchronize(); return (time.perf_counter() - t0) / k * 1e3
     run(10)
     best = min(run(K) for _ in range(3))
-    env.flow_events = []
-    run(20)
-    leg = np.median([a.elapsed_time(b) for a, b in env.flow_events]) if env.flow_events else float("nan")
-    env.flow_events = None
+    leg = float("nan")                  # (only an overlapped leg is timed on its own stream)
+    if env.flow is not None:
+        env.flow.events = []
+        run(20)
+        if env.flow.events:
+            leg = np.median([a.elapsed_time(b) for a, b in env.flow.events])
+        env.flow.events = None
     print(f"{name:28s}: {best:.3f} ms per batched step; flow leg on its stream {leg:.3f} ms", flush=True)
     env.flow_wait(); del env

@@ -33,7 +33,7 @@ for fp in ("cg", "direct"):
             cal = env.calibrate_streams(fg)
             run(10)
             ts = [run(K) for _ in range(4)]
-            env.flow_events = []; run(20)
-            leg = np.median([a.elapsed_time(b) for a, b in env.flow_events]); env.flow_events = None
+            env.flow.events = []; run(20)
+            leg = np.median([a.elapsed_time(b) for a, b in env.flow.events]); env.flow.events = None
             print(f"{fp:6s} env created and run on the {where:14s}: {min(ts):.3f} ms per batched step (before calibration {t_before:.2f}; candidates {', '.join(f'{c:.2f}' for c in cal)}; runs {', '.join(f'{t:.2f}' for t in ts)}); flow leg {leg:.3f} ms", flush=True)
             env.flow_wait(); del env
