@@ -123,6 +123,23 @@ class EnvFinishDesc(C.Structure):
         (n, C.c_void_p) for n in ("src_of_env", "nv0_of")] + [("src_stride", C.c_int64 * FINISH_MAX_ROWS)]
 
 
+PACK_MAX = 32      # MDQ_GCN_PACK_MAX
+
+
+class AdamDesc(C.Structure):
+    """Mirror of `mdq_adam_desc`."""
+    _fields_ = [("n", C.c_int32), ("_pad", C.c_int32), ("param", C.c_void_p * PACK_MAX), ("offset", C.c_int32 * PACK_MAX),
+                ("len", C.c_int32 * PACK_MAX)] + [(n, C.c_void_p) for n in ("grad", "exp_avg", "exp_avg_sq")] + [
+        (n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "bias_correction1", "bias_correction2")]
+
+
+class ReplaySampleDesc(C.Structure):
+    """Mirror of `mdq_replay_sample_desc`."""
+    _fields_ = [("n", C.c_int32), ("rec_len", C.c_int32), ("nf", C.c_int32), ("EM", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("R", "idx", "x_s", "x_n", "esrc_s", "edst_s", "esrc_n", "edst_n", "edge_ptr_s", "edge_ptr_n",
+                                  "action", "reward", "nonfinal")]
+
+
 # every symbol include/meshdqn_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mdq_abi_version": (C.c_int, []),

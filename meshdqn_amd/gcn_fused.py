@@ -13,6 +13,7 @@ import math
 import torch
 
 from . import _lib
+from ._lib import PACK_MAX
 
 
 class GcnLevel(C.Structure):
@@ -51,9 +52,6 @@ class GcnTrainDesc(C.Structure):
                 ("edge_ptr", C.c_void_p), ("q_other", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p),
                 ("nonfinal", C.c_void_p), ("workspace", C.c_void_p), ("partial", C.c_void_p), ("grad", C.c_void_p),
                 ("loss", C.c_void_p), ("out", C.c_void_p), ("layout", GcnGradLayout)]
-
-
-PACK_MAX = 32
 
 
 class GcnPackTable(C.Structure):
@@ -288,7 +286,14 @@ class FusedGcn:
         return out
 
 
+def fused_of(net, role: str = "act") -> FusedGcn:
+    """The packed device copy of `net` for `role`, created on first use and kept on the module: "act" (`net._fused`,
+    the inference forwards) or "train" (`net._fused_train`, see `DQNTrainer._fused_of`)."""
+    attr = "_fused" if role == "act" else "_fused_train"
+    if not hasattr(net, attr):
+        setattr(net, attr, FusedGcn(net))
+    return getattr(net, attr)
+
+
 def node_removal_forward(net, data):
-    if not hasattr(net, "_fused"):
-        net._fused = FusedGcn(net)
-    return net._fused.forward(data)
+    return fused_of(net).forward(data)

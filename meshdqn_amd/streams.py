@@ -16,6 +16,12 @@ import torch
 _PROBE_WARM = False
 
 
+def same_stream(a, b) -> bool:
+    """`a == b` for streams either of which may be None (torch.cuda.Stream defines `==` between streams only:
+    `None != stream` is False)."""
+    return (a is None and b is None) or (a is not None and b is not None and a == b)
+
+
 def _overlaps(cand: torch.cuda.Stream, other: torch.cuda.Stream, device) -> bool:
     """True when a CHAIN of kernels on `cand` (six launches of one-workgroup-per-half-the-CUs spin kernels with 150 KB of
     LDS, 40 us each: the shape of the flow leg / optimiser chain) runs at its own pace while `other` is busy the way the

@@ -23,6 +23,6 @@ for mode in ("flow", "own", "flow", "own"):
     train_loop_device(trainer, venv, n, optimiser_stream=mode)
     torch.cuda.synchronize(); dt = time.time() - t0
     print(f"optimiser_stream={mode}: {dt / n * 1e3:.3f} ms per batched step -> {B * n / dt:.0f} env-steps/s; calibration flow "
-          f"{[round(v, 2) for v in getattr(venv, 'calibration_ms', [])]} opt {[round(v, 2) for v in getattr(trainer, 'opt_calibration_ms', [])]}", flush=True)
+          f"{[round(v, 2) for v in getattr(venv, 'calibration_ms', [])]} opt {[round(v, 2) for v in trainer.opt_calibration_ms]}", flush=True)
     venv.flow_wait()
     del venv, trainer

@@ -32,6 +32,6 @@ for rep in range(3):
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / 40
         print(f"rep {rep} flow_pressure={fp:6s} optimiser on {osm:4s} stream: {dt * 1e3:.3f} ms per batched step ({128 / dt:.0f} env-steps/s); "
-              f"calibration flow {[round(v, 2) for v in venv.calibration_ms]} optimiser {[round(v, 2) for v in getattr(tr, 'opt_calibration_ms', [])]}", flush=True)
+              f"calibration flow {[round(v, 2) for v in venv.calibration_ms]} optimiser {[round(v, 2) for v in tr.opt_calibration_ms]}", flush=True)
         venv.flow_wait()
         del venv, tr

@@ -134,7 +134,7 @@ def main():
 
         def on_every(step, steps_done):          # noqa: F811 - every batched step: digests, then the periodic checkpoint
             torch.cuda.synchronize() if ctx.device.type == "cuda" else None
-            rep = getattr(trainer, "device_memory", None)
+            rep = trainer.device_memory
             opt_state = [v for o in trainer.opts for st in o.state.values() for k, v in sorted(st.items()) if torch.is_tensor(v)]
             rec = dict(step=int(step), net1=sha(trainer.policy_net_1.parameters()), net2=sha(trainer.policy_net_2.parameters()),
                        optimiser=sha(opt_state), optimiser_steps=len(trainer.losses),
