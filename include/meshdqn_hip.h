@@ -66,7 +66,8 @@ typedef struct mdq_ipcs_desc {
   int32_t NNZ2, NNZ1;   /* CSR capacities of the P2 / P1 patterns            */
   int32_t NAF;          /* capacity of the airfoil (tag 1) facet list        */
   int32_t NSE2, NSE1;   /* SELL-64 entry capacities of the P2 / P1 operators */
-  /* physics: flow_params / solver_params of FlowSolver (flow_solver.py:49-52,95) */
+  /* physics: flow_params / solver_params of FlowSolver (flow_solver.py:49-52,95); batch-wide unless env_phys (the
+     struct's last field) is set */
   double mu, rho, dt;
   /* Krylov controls (the reference uses MUMPS LU, flow_solver.py:150-151;
      these bound the error of the iterative replacement) */
@@ -189,6 +190,16 @@ typedef struct mdq_ipcs_desc {
      (4 / 7) was abandoned because a team barrier timed out - the partner workgroup was not resident (another process or stream
      held its CU).  That step and the later steps of the launch report NaN drag / lift; u_n / p_n keep the last completed step. */
   int32_t* status;
+  /* optional, appended within ABI 8 (NULL: off): per-environment flow constants, device [B][4]; row b = mu, rho, dt, 0 of
+     environment b (rows are 32 bytes: the base must be 32-byte aligned).  Set, the kernels of mdq_ipcs_assemble /
+     _setup_matfree / _evolve / mdq_probe_forces read the constants of environment b from its row instead of the scalars
+     mu / rho / dt above - one batch then spans several Reynolds numbers or time steps.  The scalars are still validated
+     (dt, rho > 0): a caller that sets env_phys fills them from row 0.  The entry points cannot read a device table:
+     checking that every row is finite and > 0 is the CALLER's job (meshdqn_amd.ipcs_batch.flow_table does it).
+     MDQ_ABI_VERSION stays 8: the field is the struct's last one and NULL means what ABI 8 meant, so a caller that
+     zero-initialises the descriptor (every ABI 8 caller must: the optional fields above are NULL-is-off as well) and is
+     rebuilt against this header behaves as before; no entry point or exported symbol is added. */
+  const double* env_phys;
 } mdq_ipcs_desc;
 #define MDQ_IPCS_TEAM_TIMEOUT 1
 

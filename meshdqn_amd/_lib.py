@@ -52,6 +52,7 @@ class IpcsDesc(C.Structure):
         ("work", C.c_void_p), ("work_doubles", C.c_int64),
         ("mf_rlist", C.c_void_p), ("mf_rcnt", C.c_void_p), ("mf_lpos", C.c_void_p), ("NRL", C.c_int32), ("rl_flags", C.c_int32),
         ("status", C.c_void_p),
+        ("env_phys", C.c_void_p),       # optional, appended within ABI 8: per-environment mu, rho, dt, 0 (device [B][4])
     ]
 
 

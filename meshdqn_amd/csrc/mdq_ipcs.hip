@@ -104,6 +104,7 @@ __host__ __device__ inline size_t tile_lds_bytes(const mdq_ipcs_desc& d) {
 
 struct EnvView {
   int nv, nt, ne, n2, nnz2, nnz1, naf;
+  double mu, rho, dt;  // flow constants of THIS environment (the descriptor's scalars, or its row of env_phys)
   int NT;  // capacity (SoA stride of cell_dofs / geom)
   const double* coords;
   const int32_t* cell_dofs;  // [6][NT]
@@ -142,8 +143,30 @@ struct EnvView {
 #endif
 };
 
+// a workgroup-uniform double moved to scalar registers (two v_readfirstlane): loop invariants such as rho / dt, mu or the
+// squared tolerance otherwise occupy a VGPR pair each for the whole Krylov loop (the 768-thread velocity kernel, capped at
+// 168 VGPRs, spilled two of them and re-read them in every iteration)
+__device__ __forceinline__ double uniform_double(double x) {
+  const long long b = __double_as_longlong(x);
+  const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffll)), hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
 __device__ __forceinline__ EnvView env_view(const mdq_ipcs_desc& d, int b) {
   EnvView v;
+  // flow constants: the batch-wide scalars, or row b of env_phys [B][4] = mu, rho, dt, 0.  b is the same for the whole
+  // workgroup, so the row is one uniform 32-byte load; the values go through uniform_double and stay in scalar registers
+  // like the kernel arguments they replace.  rho / dt is formed by the kernels from the view in both cases: a table whose
+  // rows equal the scalars gives the bits of env_phys = NULL.
+  v.mu = d.mu;
+  v.rho = d.rho;
+  v.dt = d.dt;
+  if (d.env_phys) {
+    const double4 q = *reinterpret_cast<const double4*>(d.env_phys + 4 * (int64_t)b);
+    v.mu = uniform_double(q.x);
+    v.rho = uniform_double(q.y);
+    v.dt = uniform_double(q.z);
+  }
   v.nv = d.nv[b];
   v.nt = d.nt[b];
   v.ne = d.ne[b];
@@ -289,7 +312,7 @@ static __global__ __launch_bounds__(WG) void assemble_kernel(mdq_ipcs_desc d) {
   v.nnz2 = v.rowptr2[v.n2];
   v.nnz1 = v.rowptr1[v.nv];
   const int tid = threadIdx.x;
-  const double a = d.rho / d.dt, mu = d.mu;
+  const double a = v.rho / v.dt, mu = v.mu;
 
   // ---- phase 0: affine geometry per triangle
   for (int e = tid; e < v.nt; e += WG) {
@@ -518,7 +541,7 @@ __global__ __launch_bounds__(SWG) void setup_matfree_kernel(mdq_ipcs_desc d) {
   static_assert(GEO || !LS, "the slot lists are staged in the full instance only");
   const int b = blockIdx.x, tid = threadIdx.x;
   const EnvView v = env_view(d, b);
-  const double a = d.rho / d.dt, mu = d.mu;
+  const double a = v.rho / v.dt, mu = v.mu;
   extern __shared__ __align__(16) unsigned char setup_lds[];
   double* sGeo = reinterpret_cast<double*>(setup_lds);             // [5][NT]   (GEO)
   double* sGx = sGeo + (GEO ? 5 * (size_t)d.NT : 0);                // [N2]      (GEO)
@@ -834,7 +857,7 @@ __device__ __forceinline__ ElemIdx load_dofs(const EnvView& v, int e) {
 // per-environment scratch (slot = cell*6+i / cell*3+j) that the dof-gather passes read
 __device__ inline void rhs1_elements(const EnvView& v, const mdq_ipcs_desc& d, const double2* __restrict__ u,
                                      const double* __restrict__ p, double2* __restrict__ escr) {
-  const double a = d.rho / d.dt;
+  const double a = v.rho / v.dt;
   for (int e = threadIdx.x; e < v.nt; e += WG) {
     const ElemIdx E = load_dofs(v, e);
     const Geo g = load_geo(v, e);
@@ -845,12 +868,12 @@ __device__ inline void rhs1_elements(const EnvView& v, const mdq_ipcs_desc& d, c
 #pragma unroll
     for (int i = 0; i < 3; ++i) pe[i] = p[E.dof[i]];
     double2 r[6];
-    elem_rhs1_vol(g, a, d.mu, d.rho, ue, pe, r);
+    elem_rhs1_vol(g, a, v.mu, v.rho, ue, pe, r);
     const int ko = v.cell_outflow[e];
     if (ko >= 0) {
       double X[3][2];
       load_cell_coords(v, e, X);
-      elem_outflow_add(g, X, ko, 0.5 * d.mu, ue, r);  // + mu/2 <nabla_grad(u_n) n, v>
+      elem_outflow_add(g, X, ko, 0.5 * v.mu, ue, r);  // + mu/2 <nabla_grad(u_n) n, v>
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) escr[e * 6 + i] = r[i];
@@ -860,7 +883,7 @@ __device__ inline void rhs1_elements(const EnvView& v, const mdq_ipcs_desc& d, c
 template <int NTH = WG>
 __device__ inline void rhs2_elements(const EnvView& v, const mdq_ipcs_desc& d, const double2* __restrict__ u,
                                      const double* __restrict__ p, double* __restrict__ escr) {
-  const double idt = 1.0 / d.dt;
+  const double idt = 1.0 / v.dt;
   for (int e = threadIdx.x; e < v.nt; e += NTH) {
     const ElemIdx E = load_dofs(v, e);
     const Geo g = load_geo(v, e);
@@ -884,7 +907,7 @@ __device__ inline void rhs2_elements(const EnvView& v, const mdq_ipcs_desc& d, c
 template <int NTH>
 __device__ inline void rhs2_accumulate_lds(const EnvView& v, const mdq_ipcs_desc& d, const double2* __restrict__ u,
                                            const double* __restrict__ p, double* acc) {
-  const double idt = 1.0 / d.dt;
+  const double idt = 1.0 / v.dt;
   for (int e0 = threadIdx.x; e0 < v.nt; e0 += 2 * NTH) {
     const int e1 = e0 + NTH;
     const bool two = e1 < v.nt;
@@ -928,7 +951,7 @@ __device__ inline void rhs3_elements(const EnvView& v, const mdq_ipcs_desc& d, c
 #pragma unroll
     for (int i = 0; i < 3; ++i) dp[i] = pnew[E.dof[i]] - pold[E.dof[i]];
     double2 r[6];
-    elem_rhs3(g, d.dt, ue, dp, r);
+    elem_rhs3(g, v.dt, ue, dp, r);
 #pragma unroll
     for (int i = 0; i < 6; ++i) escr[e * 6 + i] = r[i];
   }
@@ -2895,7 +2918,7 @@ static __global__ __launch_bounds__(WG) void probe_kernel(mdq_ipcs_desc d, int n
     const double2* uf = reinterpret_cast<const double2*>(u) + ((int64_t)b * nfields + f) * d.N2;
     const double* pf = p + ((int64_t)b * nfields + f) * d.NV;
     double dr, li;
-    forces(v, d.mu, uf, pf, red, dr, li);
+    forces(v, v.mu, uf, pf, red, dr, li);
     if (threadIdx.x == 0) {
       drag[(int64_t)b * nfields + f] = dr;
       lift[(int64_t)b * nfields + f] = li;
@@ -2982,8 +3005,8 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
   vc.rh = vh;
   vc.vv = vv;
   vc.t = vt;
-  vc.a = d.rho / d.dt;
-  vc.mu = d.mu;
+  vc.a = v.rho / v.dt;
+  vc.mu = v.mu;
   // MF: the element-tile operators (mode 5; the MODE == 2 branches of this kernel are the same formulas with an LDS stage)
   constexpr bool MF = MODE == 2 || MODE == 5;
   double2* ytmp = reinterpret_cast<double2*>(w + work_ytmp_offset(d.NV, d.NT, d.NE));   // mode 5: accumulation vector
@@ -3194,7 +3217,7 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
     for (int i = tid; i < nv; i += WG) v.p_n[i] = pnew[i];
     __syncthreads();
     double dr, li;
-    forces(v, d.mu, v.u_n, v.p_n, red, dr, li);
+    forces(v, v.mu, v.u_n, v.p_n, red, dr, li);
     if (tid == 0) {
       drag[(int64_t)b * nsteps + step] = dr;
       lift[(int64_t)b * nsteps + step] = li;
@@ -3406,7 +3429,7 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
   const int32_t* so1 = K1_LDS ? lso : v.sl1_off;
   const int32_t* ci1 = K1_LDS ? lci : v.sl1_col;
   const double* K1 = K1_LDS ? lK : v.K1s;
-  const double a = d.rho / d.dt;
+  const double a = v.rho / v.dt;
   int it_u = 0, it_p = 0, it_m = 0;
   const int lane = tid & 63, gw = rank * NWAVE + (tid >> 6);
   constexpr int GW = TEAM * NWAVE;
@@ -3461,12 +3484,12 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
 #pragma unroll
       for (int i = 0; i < 3; ++i) pe[i] = v.p_n[E.dof[i]];
       double2 rr_[6];
-      elem_rhs1_vol(g, a, d.mu, d.rho, ue, pe, rr_);
+      elem_rhs1_vol(g, a, v.mu, v.rho, ue, pe, rr_);
       const int ko = v.cell_outflow[e];
       if (ko >= 0) {
         double X[3][2];
         load_cell_coords(v, e, X);
-        elem_outflow_add(g, X, ko, 0.5 * d.mu, ue, rr_);
+        elem_outflow_add(g, X, ko, 0.5 * v.mu, ue, rr_);
       }
 #pragma unroll
       for (int i = 0; i < 6; ++i) escr2[e * 6 + i] = rr_[i];
@@ -3596,7 +3619,7 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
     }
     // ---------------- step 2: pressure (element loop by the team, the solve by rank 0)
     {
-      const double idt = 1.0 / d.dt;
+      const double idt = 1.0 / v.dt;
       for (int e = gt; e < v.nt; e += GS) {
         const ElemIdx E = load_dofs(v, e);
         const Geo g = load_geo(v, e);
@@ -3651,7 +3674,7 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
 #pragma unroll
       for (int i = 0; i < 3; ++i) dp[i] = pnew[E.dof[i]] - v.p_n[E.dof[i]];
       double2 rr_[6];
-      elem_rhs3(g, d.dt, ue, dp, rr_);
+      elem_rhs3(g, v.dt, ue, dp, rr_);
 #pragma unroll
       for (int i = 0; i < 6; ++i) escr2[e * 6 + i] = rr_[i];
     }
@@ -3740,7 +3763,7 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
     team_sync(T);
     if (rank == 0) {
       double dr, li;
-      forces(v, d.mu, v.u_n, v.p_n, red, dr, li);
+      forces(v, v.mu, v.u_n, v.p_n, red, dr, li);
       if (tid == 0) {
         const bool failed = team_failed(T);
         drag[(int64_t)b * nsteps + step] = failed ? __builtin_nan("") : dr;
@@ -3967,7 +3990,7 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
   const int32_t* so1 = K1_LDS ? lso : v.sl1_off;
   const int32_t* ci1 = K1_LDS ? lci : v.sl1_col;
   const double* K1 = K1_LDS ? lK : v.K1s;
-  const double a = d.rho / d.dt, mu = d.mu;
+  const double a = v.rho / v.dt, mu = v.mu;
   const bool packed = d.N2 <= 4096;
   int it_u = 0, it_p = 0, it_m = 0;
   // y = D^-1 A x (0 on constrained rows) / y = S^-1 M x' on the team's rows
@@ -4005,7 +4028,7 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
 #pragma unroll
       for (int i = 0; i < 3; ++i) pe[i] = v.p_n[E.dof[i]];
       double2 rr_[6];
-      elem_rhs1_vol(g, a, mu, d.rho, ue, pe, rr_);
+      elem_rhs1_vol(g, a, mu, v.rho, ue, pe, rr_);
       const int ko = v.cell_outflow[e];
       if (ko >= 0) {
         double X[3][2];
@@ -4140,7 +4163,7 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
     }
     // ---------------- step 2: pressure (element loop by the team, the solve by rank 0)
     {
-      const double idt = 1.0 / d.dt;
+      const double idt = 1.0 / v.dt;
       for (int e = gt; e < v.nt; e += GS) {
         const ElemIdx E = load_dofs(v, e);
         const Geo g = load_geo(v, e);
@@ -4196,7 +4219,7 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
 #pragma unroll
       for (int i = 0; i < 3; ++i) dp[i] = pnew[E.dof[i]] - v.p_n[E.dof[i]];
       double2 rr_[6];
-      elem_rhs3(g, d.dt, ue, dp, rr_);
+      elem_rhs3(g, v.dt, ue, dp, rr_);
 #pragma unroll
       for (int i = 0; i < 6; ++i) escr2[e * 6 + i] = rr_[i];
     }
@@ -4295,7 +4318,7 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
     team_sync(T);
     if (rank == 0) {
       double dr, li;
-      forces(v, d.mu, v.u_n, v.p_n, red, dr, li);
+      forces(v, v.mu, v.u_n, v.p_n, red, dr, li);
       if (tid == 0) {
         const bool failed = team_failed(T);
         drag[(int64_t)b * nsteps + step] = failed ? __builtin_nan("") : dr;
@@ -4405,7 +4428,7 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
 
   if constexpr (PHASE == 1) {
     // ================= step 1: tentative velocity
-    const double a = d.rho / d.dt, mu = d.mu;
+    const double a = v.rho / v.dt, mu = v.mu;
     double2* stage = reinterpret_cast<double2*>(U);  // gather copy of the operator input
     double2* tile = stage + P.N2p;                    // element results of one chunk
     double2* rg = reinterpret_cast<double2*>(w);     // (the element scratch of phase 2, idle here: room for the row scaling)
@@ -4470,7 +4493,7 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
               double pe[3];
 #pragma unroll
               for (int i = 0; i < 3; ++i) pe[i] = pn[E.dof[i]];
-              elem_rhs1_vol(g, a, mu, d.rho, ue, pe, ye);
+              elem_rhs1_vol(g, a, mu, v.rho, ue, pe, ye);
               if (ko >= 0) {
                 double X[3][2];
                 load_cell_coords(v, e, X);
@@ -4700,7 +4723,7 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
               double dp[3];
 #pragma unroll
               for (int i = 0; i < 3; ++i) dp[i] = pnew[E.dof[i]] - pold[E.dof[i]];
-              elem_rhs3(g, d.dt, ue, dp, ye);
+              elem_rhs3(g, v.dt, ue, dp, ye);
             },
             y);
       }
@@ -4833,7 +4856,7 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
     for (int i = tid; i < nv; i += WG) v.p_n[i] = pnew[i];
     __syncthreads();
     double dr, li;
-    forces(v, d.mu, v.u_n, v.p_n, red, dr, li);
+    forces(v, v.mu, v.u_n, v.p_n, red, dr, li);
     if (tid == 0) {
       drag[(int64_t)b * nsteps + step] = dr;
       lift[(int64_t)b * nsteps + step] = li;
@@ -5050,15 +5073,6 @@ __device__ __forceinline__ void outflow_entries_add(const EnvView& v, const BoEn
 }
 
 
-// a workgroup-uniform double moved to scalar registers (two v_readfirstlane): loop invariants such as rho / dt, mu or the
-// squared tolerance otherwise occupy a VGPR pair each for the whole Krylov loop (the 768-thread velocity kernel, capped at
-// 168 VGPRs, spilled two of them and re-read them in every iteration)
-__device__ __forceinline__ double uniform_double(double x) {
-  const long long b = __double_as_longlong(x);
-  const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffll)), hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 // ---- mode 3 as three kernels per time step (separate register allocation per phase: the BiCGStab
 // loop then runs without spill reloads; state is handed over through global memory as before) ----
 template <int TW, int TROWS, int TPAIR>
@@ -5068,7 +5082,7 @@ __global__ __launch_bounds__(TW) void at_velocity_kernel(mdq_ipcs_desc d, int32_
   const EnvView v = env_view(d, b);
   const int n2 = v.n2, nv = v.nv;
   const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
-  const double a = uniform_double(d.rho / d.dt), mu = d.mu;
+  const double a = uniform_double(v.rho / v.dt), mu = v.mu;
   (void)a; (void)mu; (void)nv; (void)n2;
   double* red = smem;  // 64 doubles
   double* U = smem + 64;
@@ -5141,7 +5155,7 @@ __global__ __launch_bounds__(TW) void at_velocity_kernel(mdq_ipcs_desc d, int32_
         double pe[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) pe[i] = Pn[E.dof[i]];
-        elem_rhs1_vol(g, a, mu, d.rho, ue, pe, ye);
+        elem_rhs1_vol(g, a, mu, v.rho, ue, pe, ye);
       });
     }
     // initial guess: polynomial extrapolation in time of the previous tentative velocities (xs still holds
@@ -5411,7 +5425,7 @@ __global__ __launch_bounds__(NTH) void at_pressure_kernel(mdq_ipcs_desc d, int32
   const EnvView v = env_view(d, b);
   const int n2 = v.n2, nv = v.nv;
   const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
-  const double a = d.rho / d.dt, mu = d.mu;
+  const double a = v.rho / v.dt, mu = v.mu;
   (void)a; (void)mu; (void)nv; (void)n2;
   double* red = smem;  // 64 doubles
   double* U = smem + 64;
@@ -5518,7 +5532,7 @@ static __global__ __launch_bounds__(WG) void at_correction_kernel(mdq_ipcs_desc 
   const EnvView v = env_view(d, b);
   const int n2 = v.n2, nv = v.nv;
   const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
-  const double a = d.rho / d.dt, mu = d.mu;
+  const double a = v.rho / v.dt, mu = v.mu;
   (void)a; (void)mu; (void)nv; (void)n2;
   double* red = smem;  // 64 doubles
   double* U = smem + 64;
@@ -5620,7 +5634,7 @@ static __global__ __launch_bounds__(WG) void at_correction_kernel(mdq_ipcs_desc 
       double dp[3];
 #pragma unroll
       for (int i = 0; i < 3; ++i) dp[i] = Dp[E.dof[i]];
-      elem_rhs3(g, d.dt, ue, dp, ye);
+      elem_rhs3(g, v.dt, ue, dp, ye);
     });
     // own rows of the global vectors of the next phase: issued in front of the barrier that ends the element loop
     double2 l3[MF_ROWS], dlt[MF_ROWS];
@@ -5802,7 +5816,7 @@ static __global__ __launch_bounds__(WG) void at_correction_kernel(mdq_ipcs_desc 
     __syncthreads();
     CT_STAMP(9)
     double dr, li;
-    forces(v, d.mu, v.u_n, v.p_n, red, dr, li);
+    forces(v, v.mu, v.u_n, v.p_n, red, dr, li);
     CT_STAMP(10)
     if (tid == 0) {
       drag[(int64_t)b * nsteps + step] = dr;

@@ -19,9 +19,13 @@ from .streams import role_streams
 class FlowLeg:
     NRL = 4032         # row capacity of a chunk's list in the device-built tile maps (the kernels' LDS stage holds 4064 rows)
 
-    def __init__(self, device, topo, solver, steps: int, rtol: float, pressure: str = "cg", pcg_degree: int = 0, ftopo=None):
+    def __init__(self, device, topo, solver, steps: int, rtol: float, pressure: str = "cg", pcg_degree: int = 0, ftopo=None,
+                 env_phys=None):
         """`topo`: the environment's topology engine (host or device); `solver`: mu / rho / dt_value of the flow;
-        `ftopo`: the flow stream's own `DeviceTopologyBatch` (flow_only, with the IPCS index data) = overlap mode."""
+        `ftopo`: the flow stream's own `DeviceTopologyBatch` (flow_only, with the IPCS index data) = overlap mode;
+        `env_phys`: device float64 (B, 4) rows mu, rho, dt, 0 - the flow constants per environment (validated by the
+        caller, `ipcs_batch.flow_table`; `solver` then carries row 0 for the descriptor's scalars, which are only
+        validated) - or None."""
         self.lib, self.device, self.steps, self.pressure = _lib.load(), device, int(steps), pressure
         self.topo, self.ftopo = topo, ftopo
         tp = ftopo if ftopo is not None else topo           # the engine whose index data the descriptor reads
@@ -54,6 +58,11 @@ class FlowLeg:
             if name in t:
                 setattr(d, name, t[name].data_ptr())
         d.work_doubles = nwork
+        self.env_phys = env_phys
+        if env_phys is not None:
+            if env_phys.shape != (B, 4) or env_phys.dtype != torch.float64 or not env_phys.is_contiguous() or env_phys.device.type != "cuda":
+                raise ValueError(f"env_phys: a contiguous float64 device tensor of shape ({B}, 4)")
+            d.env_phys = env_phys.data_ptr()
         # meshes beyond the LDS-resident modes (auto: the element tiles, modes 5 / 7): the tile maps of every coarsened mesh are
         # built on the device in front of the IPCS step (mdq_ipcs_build_tile_maps: row lists + packed local maps) - without
         # them the element results of every operator application go through 0.6 MB of global scratch per environment

@@ -53,11 +53,32 @@ def pd_device_tables(d, B: int, NV: int, device, cap: dict, tables: dict | None 
     return tables
 
 
+def flow_table(mu, rho, dt, B: int) -> np.ndarray | None:
+    """The per-environment flow constants of a batch of B environments (`mdq_ipcs_desc.env_phys`): None when mu, rho and
+    dt are all scalars (the descriptor's scalars then hold for the whole batch), else a float64 (B, 4) array whose row b
+    is mu, rho, dt, 0 of environment b - scalars broadcast, sequences of length B.  The library cannot read a device
+    table, so this is where it is validated: a wrong length or a value that is not finite and > 0 raises ValueError
+    naming the argument."""
+    args = dict(mu=mu, rho=rho, dt=dt)
+    table = np.zeros((int(B), 4), np.float64)
+    per_env = False
+    for k, (name, val) in enumerate(args.items()):
+        a = np.asarray(val.detach().cpu().numpy() if isinstance(val, torch.Tensor) else val, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != B):
+            raise ValueError(f"{name} must be a scalar or a sequence of length {B} (one value per environment), got shape {a.shape}")
+        if not (np.isfinite(a).all() and (a > 0).all()):
+            raise ValueError(f"{name} must be finite and > 0, got {val!r}")
+        per_env = per_env or a.ndim == 1
+        table[:, k] = a
+    return table if per_env else None
+
+
 class IpcsBatch:
-    """Device-resident batch of Taylor-Hood IPCS problems."""
+    """Device-resident batch of Taylor-Hood IPCS problems.  `mu`, `rho` and `dt` are scalars (one flow condition for the
+    batch) or sequences of length B (one per environment: `self.env_phys`, see `flow_table`)."""
 
     def __init__(self, topos: Sequence[MeshTopology], coords: Sequence[np.ndarray] | None = None,
-                 mu: float = 1e-3, rho: float = 1.0, dt: float = 1e-3, rtol: float = 1e-10,
+                 mu=1e-3, rho=1.0, dt=1e-3, rtol: float = 1e-10,
                  maxit=(200, 4000, 200), device: str | torch.device = "cuda", capacities: dict | None = None,
                  mode: int = -1, pressure_direct: bool = True, pressure_parts: int = 16,
                  cell_order: str = "auto", pcg_degree: int = 0):
@@ -69,6 +90,7 @@ class IpcsBatch:
         B = len(self.topos)
         if B == 0:
             raise ValueError("empty batch")
+        table = flow_table(mu, rho, dt, B)      # (validated before any device work)
         if cell_order == "auto":
             # the LDS-resident operator modes (every mesh of the batch within 3 584 velocity dofs): the conflict-free order of the
             # LDS-atomic mode 3; beyond them (element tiles, modes 5 / 7): a spatial order, so that a chunk of 1 024 triangles
@@ -93,7 +115,9 @@ class IpcsBatch:
             raise ValueError("cell_order must be 'auto', 'conflictfree', 'morton' or 'mesh'")
         coords = [t.coords for t in self.topos] if coords is None else list(coords)
         self.B = B
-        self.mu, self.rho, self.dt, self.rtol = float(mu), float(rho), float(dt), float(rtol)
+        # the scalars stay what existing callers read (row 0 of a table: what the entry points validate)
+        self.mu, self.rho, self.dt = (float(v) for v in (table[0, :3] if table is not None else (mu, rho, dt)))
+        self.rtol = float(rtol)
         self.maxit = tuple(int(m) for m in maxit)
 
         per = [self._host_arrays(t, x) for t, x in zip(self.topos, coords)]
@@ -237,6 +261,7 @@ class IpcsBatch:
         t["work"] = z(nwork)
         self.iters = torch.zeros((B, 3), dtype=torch.int32, device=dev)
         self.status = torch.zeros(B, dtype=torch.int32, device=dev)       # sticky (mdq_ipcs_desc.status, ABI 7): see `check`
+        self.env_phys = None if table is None else torch.from_numpy(table).to(dev)    # (B, 4) mu, rho, dt, 0 per environment
         self.steps_done = 0
 
         d = _lib.IpcsDesc()
@@ -257,6 +282,7 @@ class IpcsBatch:
             d.mf_tptr = d.mf_scat = d.mf_rlist = d.mf_rcnt = d.mf_lpos = None
         d.work_doubles = nwork
         d.status = self.status.data_ptr()
+        d.env_phys = None if self.env_phys is None else self.env_phys.data_ptr()
         d.NRL, d.rl_flags = self._NRL, self._rl_flags
         d.pd_enabled = 0
         # Krylov pressure solve of mode 3: degree of the Chebyshev polynomial preconditioner (0, default: the plain Jacobi-CG

@@ -19,16 +19,20 @@ import torch
 from scipy.spatial import Delaunay
 
 from . import _lib
+from .ipcs_batch import flow_table
 from .topology import TAG_AIRFOIL, MeshTopology
 
 
 class LightMeshBatch:
-    def __init__(self, topos: Sequence[MeshTopology], coords: Sequence[np.ndarray], mu: float, device="cuda",
+    def __init__(self, topos: Sequence[MeshTopology], coords: Sequence[np.ndarray], mu, device="cuda",
                  capacities: dict | None = None):
+        """`mu`: the viscosity of the force integrals - a scalar, or one value per environment (`self.env_phys`, the
+        descriptor's table of per-environment constants: the probe reads its mu column only)."""
         self.lib = _lib.load()
         self.device = torch.device(device)
         self.topos = list(topos)
         B = len(self.topos)
+        table = flow_table(mu, 1.0, 1.0, B)         # (rho and dt: placeholders the probe never reads)
         afs = []
         for t, x in zip(self.topos, coords):
             tags = t.facet_tags(x)
@@ -58,9 +62,11 @@ class LightMeshBatch:
                       naf=torch.tensor([a.shape[0] for a in afs], dtype=torch.int32, device=dev))
         d = _lib.IpcsDesc()
         d.B, d.NV, d.NT, d.NE, d.N2, d.NAF = B, NV, NT, NE, NV + NE, NAF
-        d.mu = float(mu)
+        d.mu = float(mu) if table is None else float(table[0, 0])
         for k, v in self.t.items():
             setattr(d, k, v.data_ptr())
+        self.env_phys = None if table is None else torch.from_numpy(table).to(dev)
+        d.env_phys = None if self.env_phys is None else self.env_phys.data_ptr()
         self.desc = d
 
     def probe_forces(self, u: torch.Tensor, p: torch.Tensor, stream=None):

@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -28,6 +29,7 @@ import torch
 from . import _lib
 from .env import Env2DAirfoil
 from .flow_leg import FlowLeg, check_flow_forces
+from .ipcs_batch import flow_table
 from .mesh_ops import (DeviceTopologyBatch, HostTopologyBatch, remesh_batch, remesh_batch_gpu, remesh_workspace, smooth_batch_gpu,
                        smooth_env_gpu)
 
@@ -50,6 +52,9 @@ def _host_cores() -> int:
 # agent parameters, hence N_closest, S = solver_steps // save_steps, mu, rho, dt - is batch-wide
 _PER_AIRFOIL_KEYS = {("flow_config", "geometry_params", "mesh")} | {
     ("agent_params", k) for k in ("gt_drag", "gt_lift", "gt_time", "u", "p", "plot_dir")}
+# ... and, in a mixed-FLOW batch (opt-in: a typo in a yaml stays an error), the flow constants
+_PER_FLOW_KEYS = {("flow_config", "flow_params", "mu"), ("flow_config", "flow_params", "rho"),
+                  ("flow_config", "solver_params", "dt")}
 
 
 def _same_value(a, b) -> bool:
@@ -60,30 +65,34 @@ def _same_value(a, b) -> bool:
     return type(a) is type(b) and a == b or (isinstance(a, (int, float)) and isinstance(b, (int, float)) and a == b)
 
 
-def _diff_keys(a, b, path=()):
-    """Key paths (tuples) where two configs differ, allowed per-airfoil keys excluded."""
-    if path in _PER_AIRFOIL_KEYS:
+def _diff_keys(a, b, path=(), allowed=_PER_AIRFOIL_KEYS):
+    """Key paths (tuples) where two configs differ, `allowed` per-config keys excluded."""
+    if path in allowed:
         return []
     if isinstance(a, dict) and isinstance(b, dict):
         out = []
         for k in list(a) + [k for k in b if k not in a]:
             if k not in a or k not in b:
-                if path + (k,) not in _PER_AIRFOIL_KEYS:
+                if path + (k,) not in allowed:
                     out.append(path + (k,))
             else:
-                out += _diff_keys(a[k], b[k], path + (k,))
+                out += _diff_keys(a[k], b[k], path + (k,), allowed)
         return out
     return [] if _same_value(a, b) else [path]
 
 
-def check_airfoil_configs(configs):
+def check_airfoil_configs(configs, mixed_flow: bool = False):
     """A batch over several airfoils: the configs may differ only in the mesh path, gt_drag / gt_lift / gt_time, u / p and
-    plot_dir.  Raises ValueError naming the first offending key."""
+    plot_dir - and, with `mixed_flow`, in flow_params.mu / .rho and solver_params.dt (two configs may then name the same
+    mesh).  Raises ValueError naming the first offending key."""
+    allowed = _PER_AIRFOIL_KEYS | _PER_FLOW_KEYS if mixed_flow else _PER_AIRFOIL_KEYS
     for i, c in enumerate(configs[1:], 1):
-        bad = _diff_keys(configs[0], c)
+        bad = _diff_keys(configs[0], c, allowed=allowed)
         if bad:
             raise ValueError(f"configs 0 and {i} of a mixed-airfoil batch differ in `{'.'.join(map(str, bad[0]))}` (only the mesh, "
-                             "gt_drag, gt_lift, gt_time, u, p and plot_dir may differ between airfoils)")
+                             "gt_drag, gt_lift, gt_time, u, p and plot_dir may differ between airfoils"
+                             + ("; mu, rho and dt as well in a mixed-flow batch)" if mixed_flow else
+                                "; mixed_flow=True / --mixed-flow also admits mu, rho and dt)"))
 
 
 def airfoil_assignment(num_envs: int, n_airfoils: int, first_env: int = 0) -> np.ndarray:
@@ -98,16 +107,19 @@ class VecEnv2DAirfoil:
     def __init__(self, config, num_envs: int, compute_device="cuda", nthreads: int = 0, base_env=None,
                  auto_reset: bool = True, emax: int = 1536, flow_steps: int = 0, flow_rtol: float = 1e-10,
                  gpu_smoothing: bool = True, gpu_topology: bool = True, gpu_remesh: bool = True,
-                 flow_overlap: bool = False, flow_pressure: str = "cg", flow_pcg_degree: int = 0, airfoil_of_env=None):
+                 flow_overlap: bool = False, flow_pressure: str = "cg", flow_pcg_degree: int = 0, airfoil_of_env=None,
+                 mixed_flow: bool = False):
         """`config`: one config dict, or a list of A of them (a batch over A airfoils, see `check_airfoil_configs`);
         `base_env`: an `Env2DAirfoil` or a list of A of them (None: built from the configs); `airfoil_of_env` (B,) ints in
-        [0, A): the airfoil of every environment (default b mod A)."""
+        [0, A): the airfoil of every environment (default b mod A); `mixed_flow`: the configs may also differ in mu, rho
+        and dt (one batch over several Reynolds numbers: `self.flow_of_env`), also on one and the same mesh."""
         self.lib = _lib.load()
         self.B = int(num_envs)
         configs = list(config) if isinstance(config, (list, tuple)) else [config]
         if not configs:
             raise ValueError("config: an empty list")
-        check_airfoil_configs(configs)
+        self.mixed_flow = bool(mixed_flow)
+        check_airfoil_configs(configs, mixed_flow=self.mixed_flow)
         self.A = A = len(configs)
         if base_env is None:
             bases = [Env2DAirfoil(c, compute_device=compute_device) for c in configs]
@@ -169,9 +181,22 @@ class VecEnv2DAirfoil:
         self.S = len(base.original_u)
         if any(len(bb.original_u) != self.S or np.asarray(bb.gt_drag).shape != (self.S,) for bb in bases):
             raise ValueError("snapshots: every airfoil needs the same S = solver_steps // save_steps snapshots and gt_drag values")
-        if any(bb.flow_solver.mu != base.flow_solver.mu or bb.flow_solver.rho != base.flow_solver.rho or
-               bb.flow_solver.dt_value != base.flow_solver.dt_value for bb in bases):
-            raise ValueError("flow_params / solver_params: mu, rho and dt must agree across the airfoils")
+        if not self.mixed_flow and any(bb.flow_solver.mu != base.flow_solver.mu or bb.flow_solver.rho != base.flow_solver.rho or
+                                       bb.flow_solver.dt_value != base.flow_solver.dt_value for bb in bases):
+            raise ValueError("flow_params / solver_params: mu, rho and dt must agree across the airfoils (mixed_flow=True "
+                             "admits one flow condition per config)")
+        # mixed-flow batch: mu, rho, dt of every environment's config, and the table both descriptors that carry the
+        # constants point at (the probe's light descriptor and the flow leg's: mdq_ipcs_desc.env_phys), uploaded once
+        self.flow_of_env = self.env_phys = None
+        if self.mixed_flow:
+            per_cfg = np.array([[bb.flow_solver.mu, bb.flow_solver.rho, bb.flow_solver.dt_value] for bb in bases], np.float64)
+            self.flow_of_env = per_cfg[self.airfoil]                                                   # (B, 3)
+            table = flow_table(self.flow_of_env[:, 0], self.flow_of_env[:, 1], self.flow_of_env[:, 2], self.B)
+            self.env_phys = torch.from_numpy(table).to(self.device)
+        # the descriptors' scalar mu / rho / dt (validated, not read by the kernels, when a table is set): the table's row 0 -
+        # environment 0's config, which need not be configs[0] (`airfoil_of_env`, `airfoil_assignment` on a rank > 0)
+        self._flow0 = base.flow_solver if self.flow_of_env is None else SimpleNamespace(
+            mu=float(self.flow_of_env[0, 0]), rho=float(self.flow_of_env[0, 1]), dt_value=float(self.flow_of_env[0, 2]))
         # per airfoil (index a): ground truth, initial mesh, polygon, interpolation source; one airfoil keeps the arrays of
         # the single-airfoil batch (gt_drag (S,), x0 (NV, 2), ...)
         self.gt_drags = np.stack([np.asarray(bb.gt_drag, dtype=np.float64) for bb in bases])            # (A, S)
@@ -259,8 +284,8 @@ class VecEnv2DAirfoil:
         self.flow_t = self.flow_iters = self.flow_status = self.flow_pd_status = None
         self._flow_tile_maps = False
         if self.flow_steps > 0:
-            fl = self.flow = FlowLeg(self.device, self.dtopo if self.gpu_topology else self.topo, base.flow_solver, self.flow_steps,
-                                     self.flow_rtol, self.flow_pressure, self.flow_pcg_degree, ftopo)
+            fl = self.flow = FlowLeg(self.device, self.dtopo if self.gpu_topology else self.topo, self._flow0, self.flow_steps,
+                                     self.flow_rtol, self.flow_pressure, self.flow_pcg_degree, ftopo, env_phys=self.env_phys)
             self.flow_t, self.flow_iters, self.flow_status, self.flow_pd_status = fl.t, fl.iters, fl.status, fl.pd_status
             self._flow_tile_maps = fl.tile_maps
             self.flow_drag = np.zeros((B, self.flow_steps))
@@ -458,7 +483,8 @@ class VecEnv2DAirfoil:
         # forces: light mesh descriptor over the batch
         md = _lib.IpcsDesc()
         md.B, md.NV, md.NT, md.NE, md.N2, md.NAF = B, NV, NT, self.NE, NP, self.NAF
-        md.mu = self.mu
+        md.mu = self._flow0.mu
+        md.env_phys = None if self.env_phys is None else self.env_phys.data_ptr()
         if self.gpu_topology:
             t_coords = dt.coords
             keep = dict(coords=t_coords, cell_dofs=dt.t["cell_dofs"], af_facets=dt.t["af_facets"], nv=np1, nt=dt.nt,
