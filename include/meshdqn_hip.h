@@ -277,6 +277,21 @@ MDQ_API int mdq_ipcs_evolve(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
                     int32_t* iters, void* stream);
 
 /*
+ * mdq_ipcs_evolve under a per-environment, time-dependent SEPARABLE inflow u_x(inlet, t) = a_b(t) * parabola(y)
+ * (the reference's `inflow_profile` evaluated per step, flow_solver.py:366-371, for profiles of that form).
+ *   inflow_scale : device double[B][nsteps], laid out like drag / lift: entry [b][s] is the factor a_b that step s of THIS
+ *                  launch applies to environment b's inlet values.  NULL: exactly mdq_ipcs_evolve.
+ * Every velocity boundary condition but the inlet is zero and the symmetric elimination is linear in the Dirichlet vector,
+ * so g(t) = a g0, lift1(t) = a lift1_0, lift3(t) = a lift3_0 and the pressure lifting is zero: the kernels multiply every
+ * read of bcu_gx / lift1 / lift3 by the step's factor and rewrite nothing - the descriptor (set up ONCE, for a = 1) serves
+ * any schedule.  A table of ones gives the bits of NULL in the fixed-order modes.
+ * The entry point cannot read a device table: checking that the factors are finite is the CALLER's job
+ * (meshdqn_amd/inflow.py builds and checks them on the host; no trigonometry runs on the device).
+ */
+MDQ_API int mdq_ipcs_evolve_inflow(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift,
+                    int32_t* iters, const double* inflow_scale, void* stream);
+
+/*
  * Same as mdq_ipcs_evolve (`FlowSolver.evolve`, flow_solver.py:362-396) for the three-kernel mode 3, with HIP events recorded on `stream` around every
  * kernel launch; the accumulated durations (milliseconds over all nsteps) of the velocity / pressure /
  * correction kernels are returned in host array kernel_ms[3].  Synchronises the stream (measurement aid).

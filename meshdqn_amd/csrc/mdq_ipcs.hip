@@ -152,6 +152,26 @@ __device__ __forceinline__ double uniform_double(double x) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
+// Inflow schedule (mdq_ipcs_evolve_inflow): the factor a_b of environment b at step `step` of a launch of `nsteps`, table
+// [B][nsteps] laid out like drag / lift.  Every velocity boundary condition but the inlet is zero and the symmetric
+// elimination is linear in the Dirichlet vector, so a(t) * parabola needs no new set-up: the factor multiplies every READ of
+// bcu_gx, lift1 and lift3 in that step (right-hand sides, Dirichlet rows of the initial guesses, norms of the stopping tests)
+// and no array is rewritten: the set-up kernels and what they wrote for a = 1 stay as they are.  One uniform 8-byte load per
+// workgroup and step, kept in scalar registers.  Without a table the factor is the literal 1.0; a table of ones gives the same
+// bits (x * 1.0 is exact, and so is a contraction of f - 1.0 * l).  The pressure lifting is zero: at_pressure_kernel and phase
+// 2 of evolve_mf_kernel read none of the three arrays.
+__device__ __forceinline__ double inflow_factor(const double* tab, int b, int nsteps, int step) {
+  return tab ? uniform_double(tab[(int64_t)b * nsteps + step]) : 1.0;
+}
+// the row of environment b as a pointer kept in a VGPR pair, and the factor loaded per lane through it: for a kernel whose
+// scalar registers are the scarce ones (evolve_kernel's instance with the pressure vectors in the slab)
+__device__ __forceinline__ const double* inflow_row_lane(const double* tab, int b, int nsteps) {
+  unsigned long long a = reinterpret_cast<unsigned long long>(tab ? tab + (int64_t)b * nsteps : nullptr);
+  asm volatile("" : "+v"(a));
+  return reinterpret_cast<const double*>(a);
+}
+__device__ __forceinline__ double2 scaled2(double a, double2 x) { return make_double2(a * x.x, a * x.y); }
+
 __device__ __forceinline__ EnvView env_view(const mdq_ipcs_desc& d, int b) {
   EnvView v;
   // flow constants: the batch-wide scalars, or row b of env_phys [B][4] = mu, rho, dt, 0.  b is the same for the whole
@@ -2960,7 +2980,7 @@ __host__ __device__ inline LdsPlan lds_plan(int N2, int NV, int NSE1) {
 // step 2) - a mesh whose pressure vectors exceed the LDS (NV > ~4000) still steps; modes 0 / 5 only, K1_LDS = false.
 template <int MODE, bool K1_LDS, bool PG = false>
 __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps, double* drag, double* lift,
-                                                     int32_t* iters) {
+                                                     int32_t* iters, const double* inflow_scale) {
   static_assert(!PG || (!K1_LDS && (MODE == 0 || MODE == 5)), "global pressure vectors: modes 0 / 5 without the LDS matrix");
   extern __shared__ __align__(16) double smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -3045,6 +3065,7 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
   const double* K1 = K1_LDS ? lK : v.K1s;
 
   int it_u = 0, it_p = 0, it_m = 0;
+  const double* frow = PG ? inflow_row_lane(inflow_scale, b, nsteps) : nullptr;
 #ifdef MDQ_PROFILE
   long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   long long tprev = __builtin_amdgcn_s_memtime();
@@ -3059,6 +3080,9 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
     MDQ_STAMP(0)
     double acc[2] = {0.0, 0.0};
     const int nhist = (int)hcnt[0];
+    // (the step's inflow factor is loaded where it is used, here and in front of the correction's rows, rather than held
+    //  across the two solves between them)
+    double ai = PG ? (frow ? frow[step] : 1.0) : inflow_factor(inflow_scale, b, nsteps, step);
     for (int i = tid; i < n2; i += WG) {
       double2 f = make_double2(0.0, 0.0);
       for (int s = v.g2_ptr[i]; s < v.g2_ptr[i + 1]; ++s) {
@@ -3066,9 +3090,9 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
         f.x += c.x;
         f.y += c.y;
       }
-      const double2 l = v.lift1[i], id = v.idiag1[i];
+      const double2 l = scaled2(ai, v.lift1[i]), id = v.idiag1[i];
       const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(v.bcu_gx[i], 0.0);
+      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
       const double2 bi = fl ? g : make_double2((f.x - l.x) * id.x, (f.y - l.y) * id.y);
       // initial guess: polynomial extrapolation in time of the previous tentative velocities h1 = u*_n .. h5 (the
       // correction solve re-uses xs, so the history is kept separately; see at_velocity_kernel), u_n while there is
@@ -3164,6 +3188,7 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
     rhs3_elements(v, d, xs, pnew, v.p_n, escr2);
     __syncthreads();
     double am[2] = {0.0, 0.0};
+    ai = PG ? (frow ? frow[step] : 1.0) : inflow_factor(inflow_scale, b, nsteps, step);
     for (int i = tid; i < n2; i += WG) {
       double2 f = make_double2(0.0, 0.0);
       for (int s = v.g2_ptr[i]; s < v.g2_ptr[i + 1]; ++s) {
@@ -3171,10 +3196,10 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
         f.x += c.x;
         f.y += c.y;
       }
-      const double2 l = v.lift3[i];
+      const double2 l = scaled2(ai, v.lift3[i]);
       const double sd = v.sdiagM[i];
       const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(v.bcu_gx[i], 0.0);
+      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
       const double2 bi = fl ? g : make_double2((f.x - l.x) / sd, (f.y - l.y) / sd);
       const double2 x0 = fl ? g : xs[i];
       xs[i] = make_double2(x0.x * sd, x0.y * sd);  // scaled unknown S x
@@ -3238,12 +3263,12 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
 
 template <int MODE, bool K1_LDS, bool PG = false>
 static hipError_t launch_evolve(const mdq_ipcs_desc* d, size_t lds, int nsteps, double* drag, double* lift,
-                                int32_t* iters, hipStream_t stream) {
+                                int32_t* iters, const double* inflow_scale, hipStream_t stream) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&evolve_kernel<MODE, K1_LDS, PG>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((evolve_kernel<MODE, K1_LDS, PG>), dim3(d->B), dim3(WG), lds, stream, *d, nsteps, drag, lift,
-                     iters);
+                     iters, inflow_scale);
   return hipGetLastError();
 }
 
@@ -3381,7 +3406,7 @@ static __global__ void team_reset_kernel(mdq_ipcs_desc d) {
 
 template <bool K1_LDS>
 __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int nsteps, double* drag, double* lift,
-                                                          int32_t* iters, int general) {
+                                                          int32_t* iters, int general, const double* inflow_scale) {
   extern __shared__ __align__(16) double smem[];
   // teams on neighbouring-by-8 block ids: with the dispatcher's round-robin both workgroups tend to share an XCD's L2
   // (a speed choice only: the protocol is placement-independent)
@@ -3473,6 +3498,7 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
   };
   team_place(T, reinterpret_cast<unsigned*>(spare + 25), general);
   for (int step = 0; step < nsteps; ++step) {
+    const double ai = inflow_factor(inflow_scale, b, nsteps, step);
     // ---------------- step 1: tentative velocity
     for (int e = gt; e < v.nt; e += GS) {
       const ElemIdx E = load_dofs(v, e);
@@ -3504,9 +3530,9 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
         f.x += c.x;
         f.y += c.y;
       }
-      const double2 l = v.lift1[i], id = v.idiag1[i];
+      const double2 l = scaled2(ai, v.lift1[i]), id = v.idiag1[i];
       const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(v.bcu_gx[i], 0.0);
+      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
       const double2 bi = fl ? g : make_double2((f.x - l.x) * id.x, (f.y - l.y) * id.y);
       double2 x0 = v.u_n[i];
       if (nhist >= 2) {
@@ -3687,10 +3713,10 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
         f.x += c.x;
         f.y += c.y;
       }
-      const double2 l = v.lift3[i];
+      const double2 l = scaled2(ai, v.lift3[i]);
       const double sd = v.sdiagM[i];
       const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(v.bcu_gx[i], 0.0);
+      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
       const double2 bi = fl ? g : make_double2((f.x - l.x) / sd, (f.y - l.y) / sd);
       const double2 x0 = fl ? g : xs[i];
       xs[i] = make_double2(x0.x * sd, x0.y * sd);
@@ -3809,14 +3835,14 @@ static int team_cus(hipStream_t st) {
 
 template <bool K1_LDS>
 static hipError_t launch_evolve_team(const mdq_ipcs_desc* d, size_t lds, int nsteps, double* drag, double* lift,
-                                     int32_t* iters, hipStream_t stream) {
+                                     int32_t* iters, const double* inflow_scale, hipStream_t stream) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&evolve_team_kernel<K1_LDS>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(team_reset_kernel, dim3((d->B + 63) / 64), dim3(64), 0, stream, *d);
   const int teams8 = (d->B + 7) / 8;                       // blocks: groups of 8 environments x TEAM ranks
   hipLaunchKernelGGL((evolve_team_kernel<K1_LDS>), dim3(teams8 * 8 * TEAM), dim3(WG), lds, stream, *d, nsteps, drag, lift,
-                     iters, team_general_barrier());
+                     iters, team_general_barrier(), inflow_scale);
   return hipGetLastError();
 }
 
@@ -3924,7 +3950,7 @@ __device__ __forceinline__ void tile_apply_team(const EnvView& v, Team& T, bool 
 
 template <bool K1_LDS>
 __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, int nsteps, double* drag, double* lift,
-                                                                int32_t* iters, int general) {
+                                                                int32_t* iters, int general, const double* inflow_scale) {
   extern __shared__ __align__(16) double smem[];
   const int q = blockIdx.x / (8 * TEAM), r8 = blockIdx.x % (8 * TEAM);
   const int b = q * 8 + (r8 & 7), rank = r8 >> 3;
@@ -4017,6 +4043,7 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
   if (d.NRL > tt.stride) tt.first = nullptr;       // (cannot happen: a list holds at most min(N2, 6 MF_CH) rows)
   else team_touch_setup(v, T, tt);                  // (published by the team barriers of step 1's right-hand side)
   for (int step = 0; step < nsteps; ++step) {
+    const double ai = inflow_factor(inflow_scale, b, nsteps, step);
     // ---------------- step 1: tentative velocity
     for (int e = gt; e < v.nt; e += GS) {
       const ElemIdx E = load_dofs(v, e);
@@ -4048,9 +4075,9 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
         f.x += c.x;
         f.y += c.y;
       }
-      const double2 l = v.lift1[i], id = v.idiag1[i];
+      const double2 l = scaled2(ai, v.lift1[i]), id = v.idiag1[i];
       const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(v.bcu_gx[i], 0.0);
+      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
       const double2 bi = fl ? g : make_double2((f.x - l.x) * id.x, (f.y - l.y) * id.y);
       double2 x0 = v.u_n[i];
       if (nhist >= 2) {
@@ -4232,10 +4259,10 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
         f.x += c.x;
         f.y += c.y;
       }
-      const double2 l = v.lift3[i];
+      const double2 l = scaled2(ai, v.lift3[i]);
       const double sd = v.sdiagM[i];
       const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(v.bcu_gx[i], 0.0);
+      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
       const double2 bi = fl ? g : make_double2((f.x - l.x) / sd, (f.y - l.y) / sd);
       const double2 x0 = fl ? g : xs[i];
       xs[i] = make_double2(x0.x * sd, x0.y * sd);   // scaled unknown S x
@@ -4335,14 +4362,14 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
 
 template <bool K1_LDS>
 static hipError_t launch_evolve_team_tiles(const mdq_ipcs_desc* d, size_t lds, int nsteps, double* drag, double* lift,
-                                           int32_t* iters, hipStream_t stream) {
+                                           int32_t* iters, const double* inflow_scale, hipStream_t stream) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&evolve_team_tiles_kernel<K1_LDS>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(team_reset_kernel, dim3((d->B + 63) / 64), dim3(64), 0, stream, *d);
   const int teams8 = (d->B + 7) / 8;                       // blocks: groups of 8 environments x TEAM ranks
   hipLaunchKernelGGL((evolve_team_tiles_kernel<K1_LDS>), dim3(teams8 * 8 * TEAM), dim3(WG), lds, stream, *d, nsteps, drag,
-                     lift, iters, team_general_barrier());
+                     lift, iters, team_general_barrier(), inflow_scale);
   return hipGetLastError();
 }
 
@@ -4396,10 +4423,11 @@ __device__ __forceinline__ void velocity_op(const EnvView& v, double a, double m
 // element results still meet in the LDS tile in ascending triangle order.
 template <bool K1_LDS, int PHASE>
 __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nsteps, int step, double* drag, double* lift,
-                                                        int32_t* iters) {
+                                                        int32_t* iters, const double* inflow_scale) {
   extern __shared__ __align__(16) double smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const EnvView v = env_view(d, b);
+  const double ai = inflow_factor(inflow_scale, b, nsteps, step);
   const int n2 = v.n2, nv = v.nv;
   const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
 
@@ -4473,7 +4501,7 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
           }
         }
       }
-      if (v.bcu_flag[row] != 0) x0 = make_double2(v.bcu_gx[row], 0.0);
+      if (v.bcu_flag[row] != 0) x0 = make_double2(ai * v.bcu_gx[row], 0.0);
       xs[row] = x0;
       stage[row] = x0;
     }
@@ -4507,9 +4535,9 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
         const int row = tid + k * WG;
         if (row < n2) {
           const bool fl = v.bcu_flag[row] != 0;
-          const double2 g = make_double2(v.bcu_gx[row], 0.0);
+          const double2 g = make_double2(ai * v.bcu_gx[row], 0.0);
           // |D^-1 b|^2 with b = f - lift (free) / g (constrained): same norm as the assembled path
-          const double2 l = v.lift1[row];
+          const double2 l = scaled2(ai, v.lift1[row]);
           const double2 sc = idgg[row];
           const double2 bi = fl ? g : make_double2((y[k].x - l.x) * sc.x, (y[k].y - l.y) * sc.y);
           acc[0] += bi.x * bi.x + bi.y * bi.y;
@@ -4754,7 +4782,7 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
           const bool fl = v.bcu_flag[row] != 0;
           if (!fl) ism[k] = 1.0 / v.sdiagM[row];
           stage[row] = x[k];
-          const double2 l = v.lift3[row];
+          const double2 l = scaled2(ai, v.lift3[row]);
           const double2 bi = fl ? x[k] : make_double2((y[k].x - l.x) * ism[k], (y[k].y - l.y) * ism[k]);
           am[0] += bi.x * bi.x + bi.y * bi.y;
         }
@@ -4867,7 +4895,7 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
 
 template <bool K1_LDS>
 static hipError_t launch_evolve_mf(const mdq_ipcs_desc* d, size_t lds, int nsteps, double* drag, double* lift,
-                                   int32_t* iters, hipStream_t stream) {
+                                   int32_t* iters, const double* inflow_scale, hipStream_t stream) {
   static const hipError_t attr = [] {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&evolve_mf_kernel<K1_LDS, 1>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -4886,9 +4914,9 @@ static hipError_t launch_evolve_mf(const mdq_ipcs_desc* d, size_t lds, int nstep
   const size_t lds_p = red_bytes + P.prs_vec_bytes + (K1_LDS ? P.prs_mat_bytes : 0);
   (void)lds;
   for (int step = 0; step < nsteps; ++step) {
-    hipLaunchKernelGGL((evolve_mf_kernel<K1_LDS, 1>), dim3(d->B), dim3(WG), lds_v, stream, *d, nsteps, step, drag, lift, iters);
-    hipLaunchKernelGGL((evolve_mf_kernel<K1_LDS, 2>), dim3(d->B), dim3(WG), lds_p, stream, *d, nsteps, step, drag, lift, iters);
-    hipLaunchKernelGGL((evolve_mf_kernel<K1_LDS, 3>), dim3(d->B), dim3(WG), lds_v, stream, *d, nsteps, step, drag, lift, iters);
+    hipLaunchKernelGGL((evolve_mf_kernel<K1_LDS, 1>), dim3(d->B), dim3(WG), lds_v, stream, *d, nsteps, step, drag, lift, iters, inflow_scale);
+    hipLaunchKernelGGL((evolve_mf_kernel<K1_LDS, 2>), dim3(d->B), dim3(WG), lds_p, stream, *d, nsteps, step, drag, lift, iters, inflow_scale);
+    hipLaunchKernelGGL((evolve_mf_kernel<K1_LDS, 3>), dim3(d->B), dim3(WG), lds_v, stream, *d, nsteps, step, drag, lift, iters, inflow_scale);
   }
   return hipGetLastError();
 }
@@ -5076,10 +5104,12 @@ __device__ __forceinline__ void outflow_entries_add(const EnvView& v, const BoEn
 // ---- mode 3 as three kernels per time step (separate register allocation per phase: the BiCGStab
 // loop then runs without spill reloads; state is handed over through global memory as before) ----
 template <int TW, int TROWS, int TPAIR>
-__global__ __launch_bounds__(TW) void at_velocity_kernel(mdq_ipcs_desc d, int32_t* iters) {
+__global__ __launch_bounds__(TW) void at_velocity_kernel(mdq_ipcs_desc d, int32_t* iters, const double* inflow_scale, int nsteps,
+                                                         int step) {
   extern __shared__ __align__(16) double smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const EnvView v = env_view(d, b);
+  const double ai = inflow_factor(inflow_scale, b, nsteps, step);
   const int n2 = v.n2, nv = v.nv;
   const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
   const double a = uniform_double(v.rho / v.dt), mu = v.mu;
@@ -5222,8 +5252,8 @@ __global__ __launch_bounds__(TW) void at_velocity_kernel(mdq_ipcs_desc d, int32_
     double gx[TROWS];
 #pragma unroll
     for (int k = 0; k < TROWS; ++k) {
-      lf[k] = v.lift1[rc[k]];
-      gx[k] = v.bcu_gx[rc[k]];
+      lf[k] = scaled2(ai, v.lift1[rc[k]]);
+      gx[k] = ai * v.bcu_gx[rc[k]];
     }
     __syncthreads();
     AT_STAMP(1)
@@ -5526,10 +5556,11 @@ __global__ __launch_bounds__(NTH) void at_pressure_kernel(mdq_ipcs_desc d, int32
 
 #if MDQ_IN_PART(0)
 static __global__ __launch_bounds__(WG) void at_correction_kernel(mdq_ipcs_desc d, int nsteps, int step, double* drag,
-                                                            double* lift, int32_t* iters) {
+                                                            double* lift, int32_t* iters, const double* inflow_scale) {
   extern __shared__ __align__(16) double smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const EnvView v = env_view(d, b);
+  const double ai = inflow_factor(inflow_scale, b, nsteps, step);
   const int n2 = v.n2, nv = v.nv;
   const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
   const double a = v.rho / v.dt, mu = v.mu;
@@ -5642,7 +5673,8 @@ static __global__ __launch_bounds__(WG) void at_correction_kernel(mdq_ipcs_desc 
     if (!fused) load_delta(dlt);   // (the fused start reads delta0 back from its LDS copy below)
 #pragma unroll
     for (int k = 0; k < MF_ROWS; ++k) {
-      l3[k] = fused ? xs[rc[k]] : v.lift3[rc[k]];     // fused start: u* of the own rows (the LDS copy holds -delta0)
+      // fused start: u* of the own rows (the LDS copy holds -delta0; its Dirichlet rows carry this step's a g from step 1)
+      l3[k] = fused ? xs[rc[k]] : scaled2(ai, v.lift3[rc[k]]);
       ism[k] = v.sdiagM[rc[k]];
       flm |= v.bcu_flag[rc[k]] ? 1u << k : 0u;
     }
@@ -5887,6 +5919,7 @@ struct EvolveArgs {
   int nsteps;
   double *drag, *lift;
   int32_t* iters;
+  const double* inflow_scale;   // [B][nsteps] inflow factors, or null (mdq_ipcs_evolve_inflow)
   hipStream_t st;
 };
 hipError_t part_launch_assembled(int mode, bool k1_lds, bool pg, const EvolveArgs& a);   // modes 0 / 1 (part 1)
@@ -5897,32 +5930,32 @@ hipError_t part_launch_mf(bool k1_lds, const EvolveArgs& a);                    
 hipError_t part_launch_assembled(int mode, bool k1_lds, bool pg, const EvolveArgs& a) {
   if (hipError_t e = upload_tables(); e != hipSuccess) return e;
   if (mode == 1)
-    return k1_lds ? launch_evolve<1, true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st)
-                  : launch_evolve<1, false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st);
-  return pg ? launch_evolve<0, false, true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st)
-            : (k1_lds ? launch_evolve<0, true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st)
-                      : launch_evolve<0, false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st));
+    return k1_lds ? launch_evolve<1, true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st)
+                  : launch_evolve<1, false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st);
+  return pg ? launch_evolve<0, false, true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st)
+            : (k1_lds ? launch_evolve<0, true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st)
+                      : launch_evolve<0, false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st));
 }
 #endif
 #if MDQ_IN_PART(2)
 hipError_t part_launch_tiles(int mode, bool k1_lds, bool pg, const EvolveArgs& a) {
   if (hipError_t e = upload_tables(); e != hipSuccess) return e;
   if (mode == 4)
-    return k1_lds ? launch_evolve_team<true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st)
-                  : launch_evolve_team<false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st);
+    return k1_lds ? launch_evolve_team<true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st)
+                  : launch_evolve_team<false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st);
   if (mode == 7)
-    return k1_lds ? launch_evolve_team_tiles<true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st)
-                  : launch_evolve_team_tiles<false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st);
-  return pg ? launch_evolve<5, false, true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st)
-            : (k1_lds ? launch_evolve<5, true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st)
-                      : launch_evolve<5, false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st));
+    return k1_lds ? launch_evolve_team_tiles<true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st)
+                  : launch_evolve_team_tiles<false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st);
+  return pg ? launch_evolve<5, false, true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st)
+            : (k1_lds ? launch_evolve<5, true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st)
+                      : launch_evolve<5, false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st));
 }
 #endif
 #if MDQ_IN_PART(3)
 hipError_t part_launch_mf(bool k1_lds, const EvolveArgs& a) {
   if (hipError_t e = upload_tables(); e != hipSuccess) return e;
-  return k1_lds ? launch_evolve_mf<true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st)
-                : launch_evolve_mf<false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.st);
+  return k1_lds ? launch_evolve_mf<true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st)
+                : launch_evolve_mf<false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st);
 }
 #endif
 
@@ -6034,22 +6067,27 @@ int mdq_ipcs_setup_matfree(const mdq_ipcs_desc* d, void* stream) {
 }
 
 static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                            void* stream, double* kernel_ms);
+                            const double* inflow_scale, void* stream, double* kernel_ms);
 
 int mdq_ipcs_evolve(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
                     void* stream) {
-  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, stream, nullptr);
+  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, nullptr);
+}
+
+int mdq_ipcs_evolve_inflow(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
+                           const double* inflow_scale, void* stream) {
+  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, inflow_scale, stream, nullptr);
 }
 
 int mdq_ipcs_evolve_timed(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
                           void* stream, double* kernel_ms) {
   if (!kernel_ms) return fail_msg("kernel_ms is required");
   if (d && d->mode != 3 && d->mode != -1) return fail_msg("per-kernel timing exists for the three-kernel mode 3 only");
-  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, stream, kernel_ms);
+  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, kernel_ms);
 }
 
 static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                            void* stream, double* kernel_ms) {
+                            const double* inflow_scale, void* stream, double* kernel_ms) {
   if (int rc = check_desc(d)) return rc;
   if (nsteps <= 0) return fail_msg("nsteps must be positive");
   if (!drag || !lift) return fail_msg("drag/lift output pointers are required");
@@ -6148,9 +6186,9 @@ static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
     for (int step = 0; step < nsteps; ++step) {
       if (kernel_ms) hipEventRecord(ev[0], st);
       if (vel_wg == 768)
-        hipLaunchKernelGGL((at_velocity_kernel<768, 5, 1>), dim3(d->B), dim3(768), lds_v, st, *d, iters);
+        hipLaunchKernelGGL((at_velocity_kernel<768, 5, 1>), dim3(d->B), dim3(768), lds_v, st, *d, iters, inflow_scale, nsteps, step);
       else
-        hipLaunchKernelGGL((at_velocity_kernel<WG, MF_ROWS, AT_PAIR>), dim3(d->B), dim3(WG), lds_v, st, *d, iters);
+        hipLaunchKernelGGL((at_velocity_kernel<WG, MF_ROWS, AT_PAIR>), dim3(d->B), dim3(WG), lds_v, st, *d, iters, inflow_scale, nsteps, step);
       if (kernel_ms) hipEventRecord(ev[1], st);
       if (d->pd_enabled)
         hipLaunchKernelGGL((at_pressure_kernel<false, 1024>), dim3(d->B), dim3(1024), lds_p, st, *d, iters);
@@ -6159,7 +6197,7 @@ static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
       else
         hipLaunchKernelGGL(at_pressure_kernel<false>, dim3(d->B), dim3(WG), lds_p, st, *d, iters);
       if (kernel_ms) hipEventRecord(ev[2], st);
-      hipLaunchKernelGGL(at_correction_kernel, dim3(d->B), dim3(WG), lds_c, st, *d, nsteps, step, drag, lift, iters);
+      hipLaunchKernelGGL(at_correction_kernel, dim3(d->B), dim3(WG), lds_c, st, *d, nsteps, step, drag, lift, iters, inflow_scale);
       if (kernel_ms) {
         hipEventRecord(ev[3], st);
         if ((e = hipEventSynchronize(ev[3])) != hipSuccess) return fail("hipEventSynchronize", e);
@@ -6174,7 +6212,7 @@ static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
       for (int i = 0; i < 4; ++i) hipEventDestroy(ev[i]);
     e = hipGetLastError();
   } else {
-    const EvolveArgs a{d, lds, nsteps, drag, lift, iters, st};
+    const EvolveArgs a{d, lds, nsteps, drag, lift, iters, inflow_scale, st};
     if (mode == 2)
       e = part_launch_mf(k1_lds, a);
     else if (mode == 4 || mode == 5 || mode == 7)

@@ -20,12 +20,14 @@ class FlowLeg:
     NRL = 4032         # row capacity of a chunk's list in the device-built tile maps (the kernels' LDS stage holds 4064 rows)
 
     def __init__(self, device, topo, solver, steps: int, rtol: float, pressure: str = "cg", pcg_degree: int = 0, ftopo=None,
-                 env_phys=None):
+                 env_phys=None, inflow_scale=None):
         """`topo`: the environment's topology engine (host or device); `solver`: mu / rho / dt_value of the flow;
         `ftopo`: the flow stream's own `DeviceTopologyBatch` (flow_only, with the IPCS index data) = overlap mode;
         `env_phys`: device float64 (B, 4) rows mu, rho, dt, 0 - the flow constants per environment (validated by the
         caller, `ipcs_batch.flow_table`; `solver` then carries row 0 for the descriptor's scalars, which are only
-        validated) - or None."""
+        validated) - or None; `inflow_scale`: device float64 (B, steps) inflow factors of the leg's steps (built once by the
+        caller, `inflow.inflow_factors`: the leg always restarts from the last snapshot, so the table is static) - or None,
+        the constant parabola."""
         self.lib, self.device, self.steps, self.pressure = _lib.load(), device, int(steps), pressure
         self.topo, self.ftopo = topo, ftopo
         tp = ftopo if ftopo is not None else topo           # the engine whose index data the descriptor reads
@@ -63,6 +65,10 @@ class FlowLeg:
             if env_phys.shape != (B, 4) or env_phys.dtype != torch.float64 or not env_phys.is_contiguous() or env_phys.device.type != "cuda":
                 raise ValueError(f"env_phys: a contiguous float64 device tensor of shape ({B}, 4)")
             d.env_phys = env_phys.data_ptr()
+        self.inflow_scale = inflow_scale
+        if inflow_scale is not None and (inflow_scale.shape != (B, self.steps) or inflow_scale.dtype != torch.float64 or
+                                         not inflow_scale.is_contiguous() or inflow_scale.device.type != "cuda"):
+            raise ValueError(f"inflow_scale: a contiguous float64 device tensor of shape ({B}, {self.steps})")
         # meshes beyond the LDS-resident modes (auto: the element tiles, modes 5 / 7): the tile maps of every coarsened mesh are
         # built on the device in front of the IPCS step (mdq_ipcs_build_tile_maps: row lists + packed local maps) - without
         # them the element results of every operator application go through 0.6 MB of global scratch per environment
@@ -136,8 +142,13 @@ class FlowLeg:
                        "mdq_ipcs_factorize_pressure")
         if before_evolve is not None:       # (the set-up above reads the mesh only; the warm start is needed from here on)
             before_evolve()
-        _lib.check(self.lib.mdq_ipcs_evolve(C.byref(d), self.steps, out[0].data_ptr(), out[1].data_ptr(),
-                                            self.iters.data_ptr(), _lib.stream_ptr()), "mdq_ipcs_evolve")
+        if self.inflow_scale is None:
+            _lib.check(self.lib.mdq_ipcs_evolve(C.byref(d), self.steps, out[0].data_ptr(), out[1].data_ptr(),
+                                                self.iters.data_ptr(), _lib.stream_ptr()), "mdq_ipcs_evolve")
+        else:
+            _lib.check(self.lib.mdq_ipcs_evolve_inflow(C.byref(d), self.steps, out[0].data_ptr(), out[1].data_ptr(),
+                                                       self.iters.data_ptr(), self.inflow_scale.data_ptr(), _lib.stream_ptr()),
+                       "mdq_ipcs_evolve_inflow")
         self._keep = keep
         return out
 

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .inflow import inflow_spec
 from .io_xdmf import load_mesh
 from .ipcs_batch import IpcsBatch, smooth_coords
 from .probes import DragProbe, LiftProbe
@@ -99,11 +100,11 @@ class FlowSolver(object):
         self.device = torch.device(device)
         # flow_solver.py:70-73: 'constant' = the time independent parabola, anything else = the caller's own profile.  The
         # reference takes a dolfin Expression with a `time` attribute; here: a callable profile(x, y, t) -> x-velocity
-        # at the inlet dof coordinates (every boundary condition of the reference has zero y-velocity)
+        # at the inlet dof coordinates (every boundary condition of the reference has zero y-velocity) - or a schedule dict
+        # (inflow.py: a(t) * the constant parabola, applied inside the evolve kernels: K steps per launch like 'constant')
         inflow = flow_params.get("inflow", "constant")
-        if inflow != "constant" and not callable(inflow):
-            raise TypeError("flow_params['inflow'] must be 'constant' or a callable profile(x, y, t) -> x-velocity")
-        self.inflow_profile = None if inflow == "constant" else inflow
+        self.inflow_profile = inflow if callable(inflow) else None
+        self.inflow_spec = None if callable(inflow) else inflow_spec(inflow)    # (TypeError / ValueError before any device work)
         coords, cells = load_mesh(geometry_params["mesh"])
         self.mesh = Mesh(coords, cells)
         self.smooth = solver_params.get("smooth", False)
@@ -143,7 +144,8 @@ class FlowSolver(object):
         if reassemble:
             self.batch = IpcsBatch([topo], [topo.coords], mu=self.mu, rho=self.rho, dt=self.dt_value,
                                    rtol=self.rtol, device=self.device, mode=self.mode,
-                                   pressure_direct=("device" if self.solver_type == "lu" else False))
+                                   pressure_direct=("device" if self.solver_type == "lu" else False),
+                                   inflow=self.inflow_spec)     # (a new batch starts its schedule's clock at 0, as gtime does)
             self.batch.assemble()
             # solver_type 'lu' = device factorisation of the pressure matrix; a mesh beyond its limits (1024 vertices, 112
             # interior / separator nodes per part) keeps the Jacobi-CG pressure solve (rtol-limited instead of exact): say so
@@ -213,7 +215,7 @@ class FlowSolver(object):
         `nsteps > 1` runs several steps in one kernel launch and returns the last values."""
         if self.batch is None:
             raise RuntimeError("operators are only (re-)assembled in DEPLOY mode after remesh (flow_solver.py:268)")
-        if self.inflow_profile is None:
+        if self.inflow_profile is None:     # constant parabola or a schedule (the batch applies its factors): one launch
             drag, lift = self.batch.evolve(nsteps)
             self.gtime += self.dt_value * nsteps
             d = drag[0].tolist()

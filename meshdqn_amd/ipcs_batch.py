@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .inflow import batch_specs, inflow_factors
 from .topology import conflict_free_cell_order, morton_cell_order, TAG_AIRFOIL, TAG_OUTFLOW, MeshTopology
 
 
@@ -75,13 +76,15 @@ def flow_table(mu, rho, dt, B: int) -> np.ndarray | None:
 
 class IpcsBatch:
     """Device-resident batch of Taylor-Hood IPCS problems.  `mu`, `rho` and `dt` are scalars (one flow condition for the
-    batch) or sequences of length B (one per environment: `self.env_phys`, see `flow_table`)."""
+    batch) or sequences of length B (one per environment: `self.env_phys`, see `flow_table`).  `inflow`: None (the constant
+    parabola), one inflow schedule (inflow.py: a spec or its dict) or a sequence of B of them - `evolve` then scales every
+    environment's inlet values by its own factor a_b(t), step by step, inside the kernels."""
 
     def __init__(self, topos: Sequence[MeshTopology], coords: Sequence[np.ndarray] | None = None,
                  mu=1e-3, rho=1.0, dt=1e-3, rtol: float = 1e-10,
                  maxit=(200, 4000, 200), device: str | torch.device = "cuda", capacities: dict | None = None,
                  mode: int = -1, pressure_direct: bool = True, pressure_parts: int = 16,
-                 cell_order: str = "auto", pcg_degree: int = 0):
+                 cell_order: str = "auto", pcg_degree: int = 0, inflow=None):
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -91,6 +94,7 @@ class IpcsBatch:
         if B == 0:
             raise ValueError("empty batch")
         table = flow_table(mu, rho, dt, B)      # (validated before any device work)
+        self.inflow = batch_specs(inflow, B)    # (likewise) B specs, or None
         if cell_order == "auto":
             # the LDS-resident operator modes (every mesh of the batch within 3 584 velocity dofs): the conflict-free order of the
             # LDS-atomic mode 3; beyond them (element tiles, modes 5 / 7): a spatial order, so that a chunk of 1 024 triangles
@@ -262,6 +266,8 @@ class IpcsBatch:
         self.iters = torch.zeros((B, 3), dtype=torch.int32, device=dev)
         self.status = torch.zeros(B, dtype=torch.int32, device=dev)       # sticky (mdq_ipcs_desc.status, ABI 7): see `check`
         self.env_phys = None if table is None else torch.from_numpy(table).to(dev)    # (B, 4) mu, rho, dt, 0 per environment
+        self.env_phys_host = table      # (the schedules' clocks run on every environment's own dt)
+        self._inflow_keep = None
         self.steps_done = 0
 
         d = _lib.IpcsDesc()
@@ -462,8 +468,35 @@ class IpcsBatch:
         d.pd_enabled = 1
         self.pds = pds
 
-    def evolve(self, nsteps: int = 1, stream=None, out=None):
-        """Advance all environments `nsteps` IPCS steps; returns (drag, lift) (B,nsteps) device tensors."""
+    def _inflow_table(self, nsteps: int, inflow_scale, stream):
+        """The device table [B][nsteps] of `mdq_ipcs_evolve_inflow` for the next `nsteps` steps: the caller's own factors
+        (a recorded series; shape and finiteness checked here - the library cannot read a device table) or the batch's
+        schedules at steps steps_done + 1 .. steps_done + nsteps on every environment's own dt; None without either."""
+        if inflow_scale is None:
+            if self.inflow is None:
+                return None
+            dt = self.env_phys_host[:, 2] if self.env_phys_host is not None else self.dt
+            f = torch.from_numpy(inflow_factors(self.inflow, dt, self.steps_done, nsteps))
+        else:
+            f = inflow_scale.detach() if isinstance(inflow_scale, torch.Tensor) else torch.from_numpy(
+                np.ascontiguousarray(inflow_scale, dtype=np.float64))
+            if tuple(f.shape) != (self.B, int(nsteps)):
+                raise ValueError(f"inflow_scale must have shape ({self.B}, {int(nsteps)}) (one factor per environment and step), "
+                                 f"got {tuple(f.shape)}")
+            if not bool(torch.isfinite(f).all()):
+                raise ValueError("inflow_scale must be finite")
+            f = f.to(torch.float64).contiguous()
+        if f.is_cuda:
+            return f
+        # asynchronous upload on the launch stream: page-locked staging, the copy is ordered in front of the kernels
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        with torch.cuda.stream(s):
+            return f.pin_memory().to(self.device, non_blocking=True)
+
+    def evolve(self, nsteps: int = 1, stream=None, out=None, inflow_scale=None):
+        """Advance all environments `nsteps` IPCS steps; returns (drag, lift) (B,nsteps) device tensors.  `inflow_scale`:
+        explicit (B, nsteps) inflow factors for these steps (tensor or array) in place of the batch's schedules."""
+        ftab = self._inflow_table(nsteps, inflow_scale, stream)       # (validated before anything is launched)
         if not self.assembled:
             self.assemble(stream)
         if out is None:
@@ -471,9 +504,15 @@ class IpcsBatch:
             lift = torch.empty_like(drag)
         else:
             drag, lift = out
-        rc = self.lib.mdq_ipcs_evolve(C.byref(self.desc), int(nsteps), drag.data_ptr(), lift.data_ptr(),
-                                      self.iters.data_ptr(), _lib.stream_ptr(stream))
-        _lib.check(rc, "mdq_ipcs_evolve")
+        if ftab is None:
+            rc = self.lib.mdq_ipcs_evolve(C.byref(self.desc), int(nsteps), drag.data_ptr(), lift.data_ptr(),
+                                          self.iters.data_ptr(), _lib.stream_ptr(stream))
+            _lib.check(rc, "mdq_ipcs_evolve")
+        else:
+            rc = self.lib.mdq_ipcs_evolve_inflow(C.byref(self.desc), int(nsteps), drag.data_ptr(), lift.data_ptr(),
+                                                 self.iters.data_ptr(), ftab.data_ptr(), _lib.stream_ptr(stream))
+            _lib.check(rc, "mdq_ipcs_evolve_inflow")
+            self._inflow_keep = ftab        # (the launch reads it: alive until the next one replaces it)
         self.steps_done += nsteps
         return drag, lift
 
@@ -490,6 +529,8 @@ class IpcsBatch:
     def evolve_timed(self, nsteps: int = 1, stream=None, out=None):
         """`evolve` with HIP events around every kernel (mode 3): returns (drag, lift, ms) where ms[3] are the
         accumulated durations of the velocity / pressure / correction kernels over the nsteps."""
+        if self.inflow is not None:     # (mdq_ipcs_evolve_timed takes no table: it would step under the constant parabola)
+            raise _lib.MeshDQNHipError("evolve_timed does not apply inflow schedules (measurement aid of the constant inflow)")
         if not self.assembled:
             self.assemble(stream)
         if out is None:

@@ -29,6 +29,7 @@ import torch
 from . import _lib
 from .env import Env2DAirfoil
 from .flow_leg import FlowLeg, check_flow_forces
+from .inflow import inflow_factors, spec_table
 from .ipcs_batch import flow_table
 from .mesh_ops import (DeviceTopologyBatch, HostTopologyBatch, remesh_batch, remesh_batch_gpu, remesh_workspace, smooth_batch_gpu,
                        smooth_env_gpu)
@@ -55,6 +56,8 @@ _PER_AIRFOIL_KEYS = {("flow_config", "geometry_params", "mesh")} | {
 # ... and, in a mixed-FLOW batch (opt-in: a typo in a yaml stays an error), the flow constants
 _PER_FLOW_KEYS = {("flow_config", "flow_params", "mu"), ("flow_config", "flow_params", "rho"),
                   ("flow_config", "solver_params", "dt")}
+# ... and, in a mixed-INFLOW batch (its own opt-in), the inflow schedule (inflow.py)
+_PER_INFLOW_KEYS = {("flow_config", "flow_params", "inflow")}
 
 
 def _same_value(a, b) -> bool:
@@ -81,18 +84,20 @@ def _diff_keys(a, b, path=(), allowed=_PER_AIRFOIL_KEYS):
     return [] if _same_value(a, b) else [path]
 
 
-def check_airfoil_configs(configs, mixed_flow: bool = False):
+def check_airfoil_configs(configs, mixed_flow: bool = False, mixed_inflow: bool = False):
     """A batch over several airfoils: the configs may differ only in the mesh path, gt_drag / gt_lift / gt_time, u / p and
-    plot_dir - and, with `mixed_flow`, in flow_params.mu / .rho and solver_params.dt (two configs may then name the same
-    mesh).  Raises ValueError naming the first offending key."""
-    allowed = _PER_AIRFOIL_KEYS | _PER_FLOW_KEYS if mixed_flow else _PER_AIRFOIL_KEYS
+    plot_dir - and, with `mixed_flow`, in flow_params.mu / .rho and solver_params.dt, with `mixed_inflow` in
+    flow_params.inflow (two configs may then name the same mesh).  Raises ValueError naming the first offending key."""
+    allowed = _PER_AIRFOIL_KEYS | (_PER_FLOW_KEYS if mixed_flow else set()) | (_PER_INFLOW_KEYS if mixed_inflow else set())
     for i, c in enumerate(configs[1:], 1):
         bad = _diff_keys(configs[0], c, allowed=allowed)
         if bad:
             raise ValueError(f"configs 0 and {i} of a mixed-airfoil batch differ in `{'.'.join(map(str, bad[0]))}` (only the mesh, "
                              "gt_drag, gt_lift, gt_time, u, p and plot_dir may differ between airfoils"
-                             + ("; mu, rho and dt as well in a mixed-flow batch)" if mixed_flow else
-                                "; mixed_flow=True / --mixed-flow also admits mu, rho and dt)"))
+                             + ("; mu, rho and dt as well in a mixed-flow batch" if mixed_flow else
+                                "; mixed_flow=True / --mixed-flow also admits mu, rho and dt")
+                             + ("; the inflow schedule as well in a mixed-inflow batch)" if mixed_inflow else
+                                "; mixed_inflow=True / --mixed-inflow also admits flow_params.inflow)"))
 
 
 def airfoil_assignment(num_envs: int, n_airfoils: int, first_env: int = 0) -> np.ndarray:
@@ -108,18 +113,21 @@ class VecEnv2DAirfoil:
                  auto_reset: bool = True, emax: int = 1536, flow_steps: int = 0, flow_rtol: float = 1e-10,
                  gpu_smoothing: bool = True, gpu_topology: bool = True, gpu_remesh: bool = True,
                  flow_overlap: bool = False, flow_pressure: str = "cg", flow_pcg_degree: int = 0, airfoil_of_env=None,
-                 mixed_flow: bool = False):
+                 mixed_flow: bool = False, mixed_inflow: bool = False):
         """`config`: one config dict, or a list of A of them (a batch over A airfoils, see `check_airfoil_configs`);
         `base_env`: an `Env2DAirfoil` or a list of A of them (None: built from the configs); `airfoil_of_env` (B,) ints in
         [0, A): the airfoil of every environment (default b mod A); `mixed_flow`: the configs may also differ in mu, rho
-        and dt (one batch over several Reynolds numbers: `self.flow_of_env`), also on one and the same mesh."""
+        and dt (one batch over several Reynolds numbers: `self.flow_of_env`), also on one and the same mesh;
+        `mixed_inflow`: the configs may also differ in flow_params.inflow, the inflow schedule (inflow.py:
+        `self.inflow_of_env`, (B, 4) rows amplitude, pulsation, frequency, phase - set for a single scheduled config as well)."""
         self.lib = _lib.load()
         self.B = int(num_envs)
         configs = list(config) if isinstance(config, (list, tuple)) else [config]
         if not configs:
             raise ValueError("config: an empty list")
         self.mixed_flow = bool(mixed_flow)
-        check_airfoil_configs(configs, mixed_flow=self.mixed_flow)
+        self.mixed_inflow = bool(mixed_inflow)
+        check_airfoil_configs(configs, mixed_flow=self.mixed_flow, mixed_inflow=self.mixed_inflow)
         self.A = A = len(configs)
         if base_env is None:
             bases = [Env2DAirfoil(c, compute_device=compute_device) for c in configs]
@@ -197,6 +205,22 @@ class VecEnv2DAirfoil:
         # environment 0's config, which need not be configs[0] (`airfoil_of_env`, `airfoil_assignment` on a rank > 0)
         self._flow0 = base.flow_solver if self.flow_of_env is None else SimpleNamespace(
             mu=float(self.flow_of_env[0, 0]), rho=float(self.flow_of_env[0, 1]), dt_value=float(self.flow_of_env[0, 2]))
+        # inflow schedules (inflow.py): every config's base environment computed its ground truth and snapshots under its own,
+        # and the per-airfoil source tables carry them per environment - S1 needs nothing else.  The S3 flow leg always
+        # restarts from the last snapshot, at time solver_steps * dt_b: environment b's factors are a_b((solver_steps + s) dt_b),
+        # s = 1 .. flow_steps - a static table, built once
+        specs = [getattr(bb.flow_solver, "inflow_spec", None) for bb in bases]
+        if not self.mixed_inflow and any(s_ != specs[0] for s_ in specs):
+            raise ValueError("flow_params: the inflow schedule must agree across the airfoils (mixed_inflow=True admits one "
+                             "per config)")
+        tab = spec_table(specs)
+        self.inflow_of_env = None if tab is None else tab[self.airfoil]                                 # (B, 4)
+        self._flow_inflow = None
+        if tab is not None and self.flow_steps > 0:
+            dts = (self.flow_of_env[:, 2] if self.flow_of_env is not None else
+                   np.array([bb.flow_solver.dt_value for bb in bases], np.float64)[self.airfoil])
+            f = inflow_factors([specs[a] for a in self.airfoil], dts, int(base.solver_steps), self.flow_steps)
+            self._flow_inflow = torch.from_numpy(f).to(self.device)
         # per airfoil (index a): ground truth, initial mesh, polygon, interpolation source; one airfoil keeps the arrays of
         # the single-airfoil batch (gt_drag (S,), x0 (NV, 2), ...)
         self.gt_drags = np.stack([np.asarray(bb.gt_drag, dtype=np.float64) for bb in bases])            # (A, S)
@@ -285,7 +309,8 @@ class VecEnv2DAirfoil:
         self._flow_tile_maps = False
         if self.flow_steps > 0:
             fl = self.flow = FlowLeg(self.device, self.dtopo if self.gpu_topology else self.topo, self._flow0, self.flow_steps,
-                                     self.flow_rtol, self.flow_pressure, self.flow_pcg_degree, ftopo, env_phys=self.env_phys)
+                                     self.flow_rtol, self.flow_pressure, self.flow_pcg_degree, ftopo, env_phys=self.env_phys,
+                                     inflow_scale=self._flow_inflow)
             self.flow_t, self.flow_iters, self.flow_status, self.flow_pd_status = fl.t, fl.iters, fl.status, fl.pd_status
             self._flow_tile_maps = fl.tile_maps
             self.flow_drag = np.zeros((B, self.flow_steps))

@@ -30,6 +30,10 @@ def main():
     ap.add_argument("--mixed-flow", action="store_true",
                     help="with several --config: they may also differ in flow_params.mu / .rho and solver_params.dt (ONE policy "
                          "over several Reynolds numbers, also on one and the same mesh); without it such a difference is an error")
+    ap.add_argument("--mixed-inflow", action="store_true",
+                    help="with several --config: they may also differ in flow_params.inflow, the inflow schedule "
+                         "(inflow: {amplitude: 0.5, pulsation: 0.2, frequency: 2.0}; ONE policy over several inflows, also on "
+                         "one and the same mesh); without it such a difference is an error")
     ap.add_argument("--gpus", type=int, default=0,
                     help="N > 1 without a launcher (WORLD_SIZE unset): this process becomes the parent of N rank processes "
                          "(meshdqn_amd/launcher.py: 127.0.0.1 rendezvous, every rank watched, a dying rank ends the job)")
@@ -73,7 +77,7 @@ def main():
     import torch
     torch.set_num_threads(1)   # (many-core hosts under a CPU quota: the CPU-side tensor ops are tiny, no intra-op pool)
     cfgs = [yaml.safe_load(open(path)) for path in args.config]
-    check_airfoil_configs(cfgs, mixed_flow=args.mixed_flow)     # (before any device work: a typo in a yaml ends the run here)
+    check_airfoil_configs(cfgs, mixed_flow=args.mixed_flow, mixed_inflow=args.mixed_inflow)     # (before any device work: a typo in a yaml ends the run here)
     cfg = cfgs[0]
     ctx = DistContext()
     opt = cfg.get("optimizer", {})          # reference yaml sections: optimizer / epsilon (configs/ray_ys930.yaml)
@@ -106,7 +110,7 @@ def main():
         venv = VecEnv2DAirfoil(cfgs, args.envs, compute_device=ctx.device, base_env=bases, flow_steps=args.flow_steps,
                                flow_overlap=args.flow_steps > 0,
                                airfoil_of_env=airfoil_assignment(args.envs, len(cfgs), ctx.rank * args.envs),
-                               mixed_flow=args.mixed_flow)
+                               mixed_flow=args.mixed_flow, mixed_inflow=args.mixed_inflow)
     log = TrainingLog(args.save_dir, restart=args.restart, restart_num=restart_num) if ctx.rank == 0 else None
 
     def checkpoint(step, steps_done):
