@@ -874,11 +874,13 @@ __device__ __forceinline__ ElemIdx load_dofs(const EnvView& v, int e) {
 }
 
 // element loops of the three right-hand sides: one thread per triangle, results to the
-// per-environment scratch (slot = cell*6+i / cell*3+j) that the dof-gather passes read
+// per-environment scratch (slot = cell*6+i / cell*3+j) that the dof-gather passes read.  (first, stride): the triangles of
+// this thread - the workgroup's by default, the team's in the two-workgroup kernels.  a = rho / dt and mu come from the
+// caller, which knows where it keeps them (scalar registers; see uniform_double).
 __device__ inline void rhs1_elements(const EnvView& v, const mdq_ipcs_desc& d, const double2* __restrict__ u,
-                                     const double* __restrict__ p, double2* __restrict__ escr) {
-  const double a = v.rho / v.dt;
-  for (int e = threadIdx.x; e < v.nt; e += WG) {
+                                     const double* __restrict__ p, double2* __restrict__ escr, double a, double mu,
+                                     int first = threadIdx.x, int stride = WG) {
+  for (int e = first; e < v.nt; e += stride) {
     const ElemIdx E = load_dofs(v, e);
     const Geo g = load_geo(v, e);
     double2 ue[6];
@@ -888,12 +890,12 @@ __device__ inline void rhs1_elements(const EnvView& v, const mdq_ipcs_desc& d, c
 #pragma unroll
     for (int i = 0; i < 3; ++i) pe[i] = p[E.dof[i]];
     double2 r[6];
-    elem_rhs1_vol(g, a, v.mu, v.rho, ue, pe, r);
+    elem_rhs1_vol(g, a, mu, v.rho, ue, pe, r);
     const int ko = v.cell_outflow[e];
     if (ko >= 0) {
       double X[3][2];
       load_cell_coords(v, e, X);
-      elem_outflow_add(g, X, ko, 0.5 * v.mu, ue, r);  // + mu/2 <nabla_grad(u_n) n, v>
+      elem_outflow_add(g, X, ko, 0.5 * mu, ue, r);  // + mu/2 <nabla_grad(u_n) n, v>
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) escr[e * 6 + i] = r[i];
@@ -902,9 +904,10 @@ __device__ inline void rhs1_elements(const EnvView& v, const mdq_ipcs_desc& d, c
 
 template <int NTH = WG>
 __device__ inline void rhs2_elements(const EnvView& v, const mdq_ipcs_desc& d, const double2* __restrict__ u,
-                                     const double* __restrict__ p, double* __restrict__ escr) {
+                                     const double* __restrict__ p, double* __restrict__ escr, int first = threadIdx.x,
+                                     int stride = NTH) {
   const double idt = 1.0 / v.dt;
-  for (int e = threadIdx.x; e < v.nt; e += NTH) {
+  for (int e = first; e < v.nt; e += stride) {
     const ElemIdx E = load_dofs(v, e);
     const Geo g = load_geo(v, e);
     double2 ue[6];
@@ -960,8 +963,8 @@ __device__ inline void rhs2_accumulate_lds(const EnvView& v, const mdq_ipcs_desc
 
 __device__ inline void rhs3_elements(const EnvView& v, const mdq_ipcs_desc& d, const double2* __restrict__ u,
                                      const double* __restrict__ pnew, const double* __restrict__ pold,
-                                     double2* __restrict__ escr) {
-  for (int e = threadIdx.x; e < v.nt; e += WG) {
+                                     double2* __restrict__ escr, int first = threadIdx.x, int stride = WG) {
+  for (int e = first; e < v.nt; e += stride) {
     const ElemIdx E = load_dofs(v, e);
     const Geo g = load_geo(v, e);
     double2 ue[6];
@@ -1362,18 +1365,35 @@ __device__ __forceinline__ void spmv_sell(const int32_t* sl_off, const int32_t* 
 //
 // MODE 0: assembled SELL operators, gather vectors in global memory (any mesh size)
 // MODE 1: assembled SELL operators, gather vectors p / r resident in LDS
-// MODE 2: matrix-free element-tile operators (x staged in LDS, tile of element results in LDS)
+// MODE 5: element-tile operators (tile of element results in LDS, gather vectors in global memory)
+//
+// The three evolve kernels (one workgroup per environment, and the two team kernels further down) run the SAME solvers and
+// the same row phases of the time step.  What differs between them is a ROW GROUP: which rows of a vector pass a thread
+// walks, what the barrier between a producer and a consumer phase is, and how a sum over all rows is formed -
+//   rows(n, f)       f(i) for the rows of this thread among 0 .. n
+//   sync()           the barrier that separates a producer phase from a consumer phase
+//   sum(acc, red)    the deterministic reduction; every thread of the group receives the same bits
+// - and the operator application, a callable (const double2* gx, Epi epi) that gathers from gx and hands every row of the
+// group to epi(row, y0, y1) once.  WgRows is one workgroup; TeamRows (behind `Team`) is the two workgroups of a team.
+struct WgRows {
+  template <class F>
+  __device__ __forceinline__ void rows(int n, F f) const {
+    for (int i = threadIdx.x; i < n; i += WG) f(i);
+  }
+  __device__ __forceinline__ void sync() const { __syncthreads(); }
+  template <int N>
+  __device__ __forceinline__ void sum(double (&acc)[N], double* red) const { block_sum<N>(acc, red); }
+};
 
 struct VelCtx {
   double2* x;    // solution (own rows)
-  double2* r;    // residual / s (own rows)
+  double2* r;    // residual / s (own rows); SpMV #2 gathers s from it
   double2* rh;   // shadow residual (own rows)
-  double2* p;    // search direction (own rows)
+  double2* p;    // search direction (own rows); SpMV #1 gathers p from it
   double2* vv;   // A p (own rows)
   double2* t;    // A s (own rows)
-  double2* gp;   // where SpMV #1 gathers p from   (MODE 2: the LDS stage buffer)
-  double2* gr;   // where SpMV #2 gathers s from   (MODE 2: the same LDS stage buffer)
-  double2* es;   // MODE 2 / 5: LDS element tile
+  // read by apply_velocity<MODE> only:
+  double2* es;   // MODE 5: LDS element tile
   double2* yt;   // MODE 5: accumulation vector (global, own rows)
   bool packed;   // MODE 5: mf_scat holds packed words
   double a, mu;
@@ -1403,13 +1423,15 @@ __device__ __forceinline__ void apply_velocity(const EnvView& v, const VelCtx& c
 
 // BiCGStab on the row-scaled velocity system  (D^-1 A1_bc) x = D^-1 b.
 // Entry: c.r holds the initial residual r0 = D^-1 (b - A x0) (zero on constrained dofs because x0
-// already satisfies the Dirichlet values), bb = |D^-1 b|^2 and rr0 = |r0|^2 are workgroup-uniform.
+// already satisfies the Dirichlet values), bb = |D^-1 b|^2 and rr0 = |r0|^2 are group-uniform.
 // Every Krylov vector therefore vanishes on constrained dofs and the eliminated operator equals the
-// plain element operator on them.  Exit: c.x holds the solution.
-template <int MODE>
-__device__ inline int bicgstab_velocity(const EnvView& v, const VelCtx& c, double rtol, int maxit, double bb,
-                                        double rr0, double* red) {
-  const int n = v.n2, tid = threadIdx.x;
+// plain element operator on them.  Exit: c.x holds the solution on the rows of their owners - the barrier that
+// publishes it is the caller's (one barrier there, not two: a team barrier is a spin and cache maintenance).
+// Every exit is group-uniform: it tests sums that every thread of the group holds with the same bits.
+template <class RG, class Op>
+__device__ __forceinline__ int bicgstab_velocity(const RG& rg, const Op& apply, const EnvView& v, const VelCtx& c, double rtol,
+                                                 int maxit, double bb, double rr0, double* red) {
+  const int n = v.n2;
   const double tol2 = rtol * rtol * bb;
   double rr = rr0;
   if (!(rr > tol2) || bb == 0.0) return 0;
@@ -1418,65 +1440,61 @@ __device__ inline int bicgstab_velocity(const EnvView& v, const VelCtx& c, doubl
   while (it < maxit) {
     ++it;
     const double beta = (rho / rho_old) * (alpha / omega);
-    for (int i = tid; i < n; i += WG) {
+    rg.rows(n, [&](int i) {
       const double2 ri = c.r[i], pi = c.p[i], vi = c.vv[i];
-      const double2 pn = make_double2(ri.x + beta * (pi.x - omega * vi.x), ri.y + beta * (pi.y - omega * vi.y));
-      c.p[i] = pn;
-      if (MODE == 2) c.gp[i] = pn;     // (mode 5: gp IS p)
-    }
-    __syncthreads();
+      c.p[i] = make_double2(ri.x + beta * (pi.x - omega * vi.x), ri.y + beta * (pi.y - omega * vi.y));
+    });
+    rg.sync();
     double a1[1] = {0.0};
-    apply_velocity<MODE>(v, c, c.gp, [&](int row, double y0, double y1) {
+    apply(c.p, [&](int row, double y0, double y1) {
       c.vv[row] = make_double2(y0, y1);
       const double2 h = c.rh[row];
       a1[0] += h.x * y0 + h.y * y1;
     });
-    block_sum<1>(a1, red);
+    rg.sum(a1, red);
     if (a1[0] == 0.0) break;  // breakdown
     alpha = rho / a1[0];
     double a2[1] = {0.0};
-    for (int i = tid; i < n; i += WG) {
+    rg.rows(n, [&](int i) {
       const double2 ri = c.r[i], vi = c.vv[i];
       const double2 sv = make_double2(ri.x - alpha * vi.x, ri.y - alpha * vi.y);
       c.r[i] = sv;
-      if (MODE == 2) c.gr[i] = sv;
       a2[0] += sv.x * sv.x + sv.y * sv.y;
-    }
-    block_sum<1>(a2, red);  // (its barriers also publish s)
+    });
+    rg.sum(a2, red);  // (its barriers also publish s)
     if (!(a2[0] > tol2)) {
-      for (int i = tid; i < n; i += WG) {
+      rg.rows(n, [&](int i) {
         const double2 xi = c.x[i], pi = c.p[i];
         c.x[i] = make_double2(xi.x + alpha * pi.x, xi.y + alpha * pi.y);
-      }
+      });
       break;
     }
     double a3[2] = {0.0, 0.0};
-    apply_velocity<MODE>(v, c, c.gr, [&](int row, double y0, double y1) {
+    apply(c.r, [&](int row, double y0, double y1) {
       c.t[row] = make_double2(y0, y1);
       const double2 sv = c.r[row];
       a3[0] += y0 * sv.x + y1 * sv.y;
       a3[1] += y0 * y0 + y1 * y1;
     });
-    block_sum<2>(a3, red);
+    rg.sum(a3, red);
     if (a3[1] == 0.0) break;
     omega = a3[0] / a3[1];
     double a4[2] = {0.0, 0.0};
-    for (int i = tid; i < n; i += WG) {
+    rg.rows(n, [&](int i) {
       const double2 ti = c.t[i], xi = c.x[i], pi = c.p[i], si = c.r[i], hi = c.rh[i];
       c.x[i] = make_double2(xi.x + alpha * pi.x + omega * si.x, xi.y + alpha * pi.y + omega * si.y);
       const double2 rn = make_double2(si.x - omega * ti.x, si.y - omega * ti.y);
       c.r[i] = rn;
       a4[0] += rn.x * rn.x + rn.y * rn.y;
       a4[1] += hi.x * rn.x + hi.y * rn.y;
-    }
-    block_sum<2>(a4, red);
+    });
+    rg.sum(a4, red);
     rr = a4[0];
     if (!(rr > tol2)) break;
     rho_old = rho;
     rho = a4[1];
     if (rho == 0.0 || omega == 0.0) break;
   }
-  __syncthreads();
   return it;
 }
 
@@ -1485,8 +1503,9 @@ struct MassCtx {
   double2* r;   // residual (own rows)
   double2* p;   // search direction (own rows)
   double2* q;   // M p (own rows)
-  double2* gp;  // where the SpMV gathers p from
-  double2* es;  // MODE 2 / 5: LDS element tile
+  double2* gp;  // where the SpMV gathers from: p itself, or (tile operators) the staged copy S^-1 p
+  // read by apply_mass<MODE> only:
+  double2* es;  // MODE 5: LDS element tile
   double2* yt;  // MODE 5: accumulation vector (global, own rows)
   bool packed;
 };
@@ -1510,11 +1529,12 @@ __device__ __forceinline__ void apply_mass(const EnvView& v, const MassCtx& c, c
 }
 
 // CG on the symmetrically scaled mass system, both velocity components at once.
-// Entry: c.r = r0 = S^-1 (b - M S^-1 x0) with zeros on constrained dofs, c.p = r0 (and its staged copy).
-template <int MODE>
-__device__ inline int cg_mass(const EnvView& v, const MassCtx& c, double rtol, int maxit, double bb, double rr0,
-                              double* red) {
-  const int n = v.n2, tid = threadIdx.x;
+// Entry: c.r = r0 = S^-1 (b - M S^-1 x0) with zeros on constrained dofs, c.p = r0 (and, STAGED, c.gp = S^-1 r0: the tile
+// operators apply the plain element mass matrix to a gathered S^-1 p).  Exit: as bicgstab_velocity - no barrier.
+template <bool STAGED, class RG, class Op>
+__device__ __forceinline__ int cg_mass(const RG& rg, const Op& apply, const EnvView& v, const MassCtx& c, double rtol, int maxit,
+                                       double bb, double rr0, double* red) {
+  const int n = v.n2;
   const double tol2 = rtol * rtol * bb;
   double rr = rr0;
   if (!(rr > tol2) || bb == 0.0) return 0;
@@ -1522,39 +1542,38 @@ __device__ inline int cg_mass(const EnvView& v, const MassCtx& c, double rtol, i
   while (it < maxit) {
     ++it;
     double a1[1] = {0.0};
-    apply_mass<MODE>(v, c, c.gp, [&](int row, double y0, double y1) {
+    apply(c.gp, [&](int row, double y0, double y1) {
       c.q[row] = make_double2(y0, y1);
       const double2 pi = c.p[row];
       a1[0] += pi.x * y0 + pi.y * y1;
     });
-    block_sum<1>(a1, red);
+    rg.sum(a1, red);
     if (!(a1[0] > 0.0)) break;
     const double alpha = rr / a1[0];
     double a2[1] = {0.0};
-    for (int i = tid; i < n; i += WG) {
+    rg.rows(n, [&](int i) {
       const double2 xi = c.x[i], pi = c.p[i], ri = c.r[i], qi = c.q[i];
       c.x[i] = make_double2(xi.x + alpha * pi.x, xi.y + alpha * pi.y);
       const double2 rn = make_double2(ri.x - alpha * qi.x, ri.y - alpha * qi.y);
       c.r[i] = rn;
       a2[0] += rn.x * rn.x + rn.y * rn.y;
-    }
-    block_sum<1>(a2, red);
+    });
+    rg.sum(a2, red);
     const double rr_new = a2[0];
     if (!(rr_new > tol2)) break;
     const double beta = rr_new / rr;
     rr = rr_new;
-    for (int i = tid; i < n; i += WG) {
+    rg.rows(n, [&](int i) {
       const double2 ri = c.r[i], pi = c.p[i];
       const double2 pn = make_double2(ri.x + beta * pi.x, ri.y + beta * pi.y);
       c.p[i] = pn;
-      if (MODE == 2 || MODE == 5) {
+      if (STAGED) {
         const double is = 1.0 / v.sdiagM[i];
         c.gp[i] = make_double2(pn.x * is, pn.y * is);
       }
-    }
-    __syncthreads();
+    });
+    rg.sync();
   }
-  __syncthreads();
   return it;
 }
 
@@ -2957,7 +2976,7 @@ static __global__ __launch_bounds__(WG) void probe_kernel(mdq_ipcs_desc d, int n
 #endif
 
 // dynamic LDS: [red 64 doubles][union: velocity stage (MODE 1: p,r  double2[N2p] each;
-//                                          MODE 2: x stage double2[N2p] + element tile double2[6*WG])
+//                                          evolve_mf_kernel: x stage double2[N2p] + element tile double2[6*WG])
 //                                  | pressure: 4 vectors [NVp] + K1 in SELL form (values, columns, slice offsets)]
 struct LdsPlan {
   int N2p, NVp;
@@ -2974,6 +2993,230 @@ __host__ __device__ inline LdsPlan lds_plan(int N2, int NV, int NSE1) {
   P.prs_mat_bytes = sizeof(double) * (size_t)(NSE1 > WG ? NSE1 : WG) + sizeof(int32_t) * ((size_t)NSE1 + (NSE1 & 1)) +
                     sizeof(int32_t) * (size_t)(((NV / 64 + 2) + 1) & ~1);
   return P;
+}
+
+// ------------------------------------------------------------------ the row phases of a time step
+//
+// Written once over a row group and an operator application (see "Krylov solvers"): evolve_kernel and the two team
+// kernels call them.  What stays with each kernel: its row ranges and barriers (the group), who runs the pressure solve,
+// where it keeps rho / dt, mu and the inflow factor, and - team kernels - the time-out handling.
+
+// the last five tentative velocities (h1 = newest) and their count, in the environment's workspace slab
+struct VelHist {
+  double2 *h1, *h2, *h3, *h4, *h5;
+  double* cnt;   // [0]: tentative velocities stored  ([1]: evolve_mf_kernel's corrections stored)
+};
+__device__ __forceinline__ VelHist vel_hist(const mdq_ipcs_desc& d, double* w) {
+  VelHist H;
+  H.h1 = reinterpret_cast<double2*>(w + work_hist_offset(d.NV, d.NT, d.NE));
+  H.h2 = H.h1 + d.N2;
+  H.h3 = H.h2 + d.N2;
+  H.h4 = H.h3 + d.N2;
+  H.h5 = H.h4 + d.N2;
+  H.cnt = reinterpret_cast<double*>(H.h5 + d.N2);
+  return H;
+}
+
+// initial guess of the velocity solve in row i: polynomial extrapolation in time of the previous tentative velocities
+// h1 = u*_n .. h5 (the correction solve re-uses xs, so the history is kept separately; see at_velocity_kernel), `un` = u_n
+// while there is no history
+__device__ __forceinline__ double2 extrapolate_x0(int nhist, double2 un, const VelHist& H, int i) {
+  double2 x0 = un;
+  if (nhist >= 2) {
+    const double2 us1 = H.h1[i], us2 = H.h2[i];
+    x0 = make_double2(2.0 * us1.x - us2.x, 2.0 * us1.y - us2.y);
+    if (nhist >= 3) {
+      const double2 us3 = H.h3[i];
+      x0 = make_double2(3.0 * (us1.x - us2.x) + us3.x, 3.0 * (us1.y - us2.y) + us3.y);
+      if (nhist >= 4) {
+        const double2 us4 = H.h4[i];
+        x0 = make_double2(4.0 * (us1.x + us3.x) - 6.0 * us2.x - us4.x, 4.0 * (us1.y + us3.y) - 6.0 * us2.y - us4.y);
+        if (nhist >= 5) {
+          const double2 us5 = H.h5[i];
+          x0 = make_double2(5.0 * (us1.x - us4.x) - 10.0 * (us2.x - us3.x) + us5.x,
+                            5.0 * (us1.y - us4.y) - 10.0 * (us2.y - us3.y) + us5.y);
+        }
+      }
+    }
+  }
+  return x0;
+}
+// shift the history of row i, newest first: h1 = u* of this step (xs)
+__device__ __forceinline__ void history_shift(int nhist, const VelHist& H, const double2* xs, int i) {
+  if (nhist >= 4) H.h5[i] = H.h4[i];
+  if (nhist >= 3) H.h4[i] = H.h3[i];
+  if (nhist >= 2) H.h3[i] = H.h2[i];
+  if (nhist >= 1) H.h2[i] = H.h1[i];
+  H.h1[i] = xs[i];
+}
+
+// row i of an element right-hand side: the sum of its slots of the element scratch, in list order
+__device__ __forceinline__ double2 gather_slots2(const EnvView& v, const double2* escr2, int i) {
+  double2 f = make_double2(0.0, 0.0);
+  for (int s = v.g2_ptr[i]; s < v.g2_ptr[i + 1]; ++s) {
+    const double2 c = escr2[v.g2_src[s]];
+    f.x += c.x;
+    f.y += c.y;
+  }
+  return f;
+}
+
+// Step 1 behind the element loop: right-hand side rows b = D^-1 (f - ai lift1) (Dirichlet rows: ai g), initial guess x0 in
+// c.x, initial residual r0 = b - (D^-1 A) x0 in c.r / c.rh, p = v = 0; acc = { |b|^2, |r0|^2 } on exit.
+// TILE: the operator is the full element operator (no lifting vector: x0 carries the Dirichlet values), so the residual
+// is seeded with D^-1 f and zeros on constrained rows; |b|^2 is the assembled modes' either way.
+template <bool TILE, class RG, class Op>
+__device__ __forceinline__ void velocity_rhs(const RG& rg, const Op& apply, const EnvView& v, const VelCtx& c, double ai,
+                                             const double2* escr2, int nhist, const VelHist& H, double* red, double (&acc)[2]) {
+  rg.rows(v.n2, [&](int i) {
+    const double2 f = gather_slots2(v, escr2, i);
+    const double2 l = scaled2(ai, v.lift1[i]), id = v.idiag1[i];
+    const bool fl = v.bcu_flag[i] != 0;
+    const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
+    const double2 bi = fl ? g : make_double2((f.x - l.x) * id.x, (f.y - l.y) * id.y);
+    double2 x0 = extrapolate_x0(nhist, v.u_n[i], H, i);
+    if (fl) x0 = g;   // Dirichlet values hold
+    c.x[i] = x0;
+    if (TILE)
+      c.r[i] = fl ? make_double2(0.0, 0.0) : make_double2(f.x * id.x, f.y * id.y);
+    else
+      c.r[i] = bi;
+    acc[0] += bi.x * bi.x + bi.y * bi.y;
+  });
+  rg.sync();
+  apply(c.x, [&](int row, double y0, double y1) {
+    const double2 bi = c.r[row];
+    const double2 r0 = make_double2(bi.x - y0, bi.y - y1);
+    c.r[row] = r0;
+    c.rh[row] = r0;
+    c.p[row] = make_double2(0.0, 0.0);
+    c.vv[row] = make_double2(0.0, 0.0);
+    acc[1] += r0.x * r0.x + r0.y * r0.y;
+  });
+  rg.sum(acc, red);
+}
+
+// the pressure vectors and the K1 stage of the kernels' LDS union (see LdsPlan)
+struct PrsLds {
+  double *x, *r, *p, *q, *lK;   // lK [NSE1] (K1_LDS; the direct solver's scratch vector otherwise)
+  int32_t *lci, *lso;           // [NSE1], [NV/64+2]
+};
+__device__ __forceinline__ PrsLds prs_lds(double* U, const LdsPlan& P, const mdq_ipcs_desc& d) {
+  PrsLds L;
+  L.x = U;
+  L.r = L.x + P.NVp;
+  L.p = L.r + P.NVp;
+  L.q = L.p + P.NVp;
+  L.lK = L.q + P.NVp;
+  L.lci = reinterpret_cast<int32_t*>(L.lK + d.NSE1);
+  L.lso = L.lci + d.NSE1 + (d.NSE1 & 1);
+  return L;
+}
+
+// what pressure_krylov_lds takes behind its vectors: each kernel's own (scratch room, tables, the on-chip solver's union)
+struct KrylovLds {
+  size_t scratch_bytes;
+  double* extra;
+  size_t extra_bytes;
+  double* U;
+  size_t U_bytes;
+  int NVp;
+};
+
+// Step 2 behind the element loop, by ONE workgroup: K1 into LDS (K1_LDS), right-hand side rows and the scaled start vector,
+// the direct solve where this environment has factors (DIRECT) or the Krylov solve (its iterations are returned),
+// pnew = S^-1 x.  `stamp`: the profile build's phase stamps 3 / 4.  (`red` is a plain argument, not a member of a struct:
+// the out-of-line pressure solvers are compiled knowing that it is the start of the LDS only while every caller hands the
+// constant down through arguments.)
+template <bool K1_LDS, bool DIRECT, class Stamp>
+__device__ __forceinline__ int pressure_solve(const EnvView& v, const mdq_ipcs_desc& d, int b, const double* escr1, const PrsLds& L,
+                                              double* pnew, const KrylovLds& ka, double* red, const Stamp& stamp) {
+  const int tid = threadIdx.x, nv = v.nv;
+  const int nsl1 = (nv + 63) >> 6;
+  const int32_t* so1 = K1_LDS ? L.lso : v.sl1_off;
+  const int32_t* ci1 = K1_LDS ? L.lci : v.sl1_col;
+  const double* K1 = K1_LDS ? L.lK : v.K1s;
+  int it = 0;
+  if (K1_LDS && !d.pd_enabled) {
+    const int ne1 = v.sl1_off[nsl1];
+    for (int k = tid; k < ne1; k += WG) {
+      L.lK[k] = v.K1s[k];
+      L.lci[k] = v.sl1_col[k];
+    }
+    for (int k = tid; k <= nsl1; k += WG) L.lso[k] = v.sl1_off[k];
+  }
+  for (int i = tid; i < nv; i += WG) {
+    double bsum = 0.0;
+    for (int s = v.g1_ptr[i]; s < v.g1_ptr[i + 1]; ++s) bsum += escr1[v.g1_src[s]];
+    const double sd = v.sdiagK[i];
+    L.r[i] = v.bcp_flag[i] ? 0.0 : bsum / sd;
+    L.x[i] = v.p_n[i] * sd;
+  }
+  stamp(3);
+  if (DIRECT && d.pd_enabled && d.pd_hdr[4 * (int64_t)b + 2] > 0) {   // (nparts = 0: no factors for this environment -> Krylov)
+    const PdView pd = pd_view(d, b);
+    pressure_direct(pd, nv, L.r, L.x, L.p, L.q, L.lK);
+  } else {
+    it = pressure_krylov_lds(d, K1_LDS, nv, so1, ci1, K1, v.coords, L.x, L.r, L.p, L.q, ka.scratch_bytes, ka.extra, ka.extra_bytes, red,
+                             ka.U, ka.U_bytes, ka.NVp);
+  }
+  stamp(4);
+  for (int i = tid; i < nv; i += WG) pnew[i] = L.x[i] / v.sdiagK[i];
+  return it;
+}
+
+// Step 3 behind the element loop: right-hand side rows b = S^-1 (f - ai lift3) (Dirichlet rows: ai g), the scaled unknown
+// S x0 in c.x, r0 = b - (S^-1 M S^-1)(S x0) in c.r, p0 = r0; am = { |b|^2, |r0|^2 } on exit.  TILE: as in velocity_rhs, and
+// the operator gathers S^-1 (.) from the stage c.gp: x0 for the residual, then S^-1 p0 for the solver (staged behind the
+// reduction's barrier: every gather of x0 is complete).
+template <bool TILE, class RG, class Op>
+__device__ __forceinline__ void correction_rhs(const RG& rg, const Op& apply, const EnvView& v, const MassCtx& c, double ai,
+                                               const double2* escr2, double* red, double (&am)[2]) {
+  rg.rows(v.n2, [&](int i) {
+    const double2 f = gather_slots2(v, escr2, i);
+    const double2 l = scaled2(ai, v.lift3[i]);
+    const double sd = v.sdiagM[i];
+    const bool fl = v.bcu_flag[i] != 0;
+    const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
+    const double2 bi = fl ? g : make_double2((f.x - l.x) / sd, (f.y - l.y) / sd);
+    double2 x0 = c.x[i];
+    if (fl) x0 = g;   // (not `fl ? g : c.x[i]`: a choice between two objects keeps g in scratch memory)
+    c.x[i] = make_double2(x0.x * sd, x0.y * sd);  // scaled unknown S x
+    if (TILE) {
+      c.gp[i] = x0;  // S^-1 (S x0)
+      c.r[i] = fl ? make_double2(0.0, 0.0) : make_double2(f.x / sd, f.y / sd);
+    } else {
+      c.r[i] = bi;
+    }
+    am[0] += bi.x * bi.x + bi.y * bi.y;
+  });
+  rg.sync();
+  apply(TILE ? c.gp : c.x, [&](int row, double y0, double y1) {
+    const double2 bi = c.r[row];
+    const double2 r0 = make_double2(bi.x - y0, bi.y - y1);
+    c.r[row] = r0;
+    c.p[row] = r0;
+    am[1] += r0.x * r0.x + r0.y * r0.y;
+  });
+  rg.sum(am, red);
+  if (TILE) {
+    rg.rows(v.n2, [&](int i) {
+      const double is = 1.0 / v.sdiagM[i];
+      const double2 p0 = c.p[i];
+      c.gp[i] = make_double2(p0.x * is, p0.y * is);
+    });
+    rg.sync();
+  }
+}
+
+// u_n = S^-1 (S x) on the group's rows
+template <class RG>
+__device__ __forceinline__ void update_velocity(const RG& rg, const EnvView& v, const double2* xs) {
+  rg.rows(v.n2, [&](int i) {
+    const double sd = v.sdiagM[i];
+    const double2 x = xs[i];
+    v.u_n[i] = make_double2(x.x / sd, x.y / sd);
+  });
 }
 
 // PG: the four pressure CG vectors live in the workspace slab as well (they alias the velocity Krylov vectors, idle during
@@ -3001,20 +3244,16 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
   double2* vp = vh + d.N2;
   double2* vv = vp + d.N2;
   double2* vt = vv + d.N2;
-  // pressure view of the union (PG: of the idle velocity vectors; 2 N2 doubles each >= NV)
-  double* px = PG ? reinterpret_cast<double*>(vr) : U;
-  double* pr = PG ? reinterpret_cast<double*>(vh) : px + P.NVp;
-  double* pp = PG ? reinterpret_cast<double*>(vp) : pr + P.NVp;
-  double* pq = PG ? reinterpret_cast<double*>(vv) : pp + P.NVp;
-  double* lK = pq + P.NVp;                                            // [NSE1]   (K1_LDS only)
-  int32_t* lci = reinterpret_cast<int32_t*>(lK + d.NSE1);            // [NSE1]
-  int32_t* lso = lci + d.NSE1 + (d.NSE1 & 1);                         // [NV/64+2]
-  double2* h1 = reinterpret_cast<double2*>(w + work_hist_offset(d.NV, d.NT, d.NE));  // u* history of the velocity solve
-  double2* h2 = h1 + d.N2;
-  double2* h3 = h2 + d.N2;
-  double2* h4 = h3 + d.N2;
-  double2* h5 = h4 + d.N2;
-  double* hcnt = reinterpret_cast<double*>(h5 + d.N2);
+  // pressure view of the union (PG: the vectors are the idle velocity vectors; 2 N2 doubles each >= NV)
+  PrsLds L = prs_lds(U, P, d);
+  if (PG) {
+    L.x = reinterpret_cast<double*>(vr);
+    L.r = reinterpret_cast<double*>(vh);
+    L.p = reinterpret_cast<double*>(vp);
+    L.q = reinterpret_cast<double*>(vv);
+  }
+  const VelHist H = vel_hist(d, w);  // u* history of the velocity solve
+  double* hcnt = H.cnt;
   double* pnew = reinterpret_cast<double*>(vt + d.N2);
   // velocity view of the union
   double2* L0 = reinterpret_cast<double2*>(U);
@@ -3027,24 +3266,13 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
   vc.t = vt;
   vc.a = v.rho / v.dt;
   vc.mu = v.mu;
-  // MF: the element-tile operators (mode 5; the MODE == 2 branches of this kernel are the same formulas with an LDS stage)
-  constexpr bool MF = MODE == 2 || MODE == 5;
+  constexpr bool MF = MODE == 5;   // the element-tile operators
   double2* ytmp = reinterpret_cast<double2*>(w + work_ytmp_offset(d.NV, d.NT, d.NE));   // mode 5: accumulation vector
-  double2* stage = MODE == 5 ? vh : L0;   // where the mass solve stages S^-1 p for the gathers (mode 5: vh is free there)
   vc.es = MODE == 5 ? L0 : L1;
   vc.yt = ytmp;
   vc.packed = d.N2 <= 4096;
-  if (MODE == 1) {
-    vc.p = vc.gp = L0;
-    vc.r = vc.gr = L1;
-  } else if (MODE == 2) {
-    vc.p = vp;
-    vc.r = vr;
-    vc.gp = vc.gr = L0;
-  } else {                       // modes 0 / 5: the gathers read the Krylov vectors themselves (global memory)
-    vc.p = vc.gp = vp;
-    vc.r = vc.gr = vr;
-  }
+  vc.p = MODE == 1 ? L0 : vp;    // (modes 0 / 5: the gathers read the Krylov vectors themselves, in global memory)
+  vc.r = MODE == 1 ? L1 : vr;
   MassCtx mc;
   mc.x = xs;
   mc.r = vr;
@@ -3052,17 +3280,20 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
   mc.es = MODE == 5 ? L0 : L1;
   mc.yt = ytmp;
   mc.packed = d.N2 <= 4096;
-  if (MF) {
-    mc.p = vp;
-    mc.gp = stage;
-  } else {
-    mc.p = mc.gp = (MODE == 1) ? L0 : vp;
-  }
+  mc.p = MODE == 1 ? L0 : vp;
+  mc.gp = MF ? vh : mc.p;   // (mode 5 stages S^-1 p for the gathers: vh is free in the mass solve)
 
-  const int nsl1 = (nv + 63) >> 6;
-  const int32_t* so1 = K1_LDS ? lso : v.sl1_off;
-  const int32_t* ci1 = K1_LDS ? lci : v.sl1_col;
-  const double* K1 = K1_LDS ? lK : v.K1s;
+  // (PG: vectors in the slab - L.p is a 2 N2-double vector there -, the preconditioner's tables in the LDS they leave free;
+  //  the matrix on the chip: the tile modes only)
+  const KrylovLds ka =
+      PG ? KrylovLds{2 * sizeof(double) * (size_t)d.N2, U,
+                     MODE == 5 ? sizeof(double2) * 6 * MF_CH : tl_extra_bytes(d.NV) + sizeof(double) * NAG * NAG, nullptr, 0, 0}
+         : KrylovLds{2 * sizeof(double) * (size_t)P.NVp, L.lK, sizeof(double) * (size_t)P.NVp, MODE == 5 ? U : nullptr,
+                     max(P.prs_vec_bytes + (K1_LDS ? P.prs_mat_bytes : 0), MODE == 5 ? tile_lds_bytes(d) : (size_t)0), P.NVp};
+
+  const WgRows rg;
+  auto op_vel = [&](const double2* gx, auto epi) { apply_velocity<MODE>(v, vc, gx, epi); };
+  auto op_mass = [&](const double2* gx, auto epi) { apply_mass<MODE>(v, mc, gx, epi); };
 
   int it_u = 0, it_p = 0, it_m = 0;
   const double* frow = PG ? inflow_row_lane(inflow_scale, b, nsteps) : nullptr;
@@ -3070,12 +3301,13 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
   long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   long long tprev = __builtin_amdgcn_s_memtime();
 #endif
+  auto stamp = [&](int k) { MDQ_STAMP(k) };
   __syncthreads();
 
   for (int step = 0; step < nsteps; ++step) {
     // ---------------- step 1: tentative velocity  (flow_solver.py:106-112, solve 1 of :378-380)
     MDQ_STAMP(7)
-    rhs1_elements(v, d, v.u_n, v.p_n, escr2);
+    rhs1_elements(v, d, v.u_n, v.p_n, escr2, v.rho / v.dt, v.mu);
     __syncthreads();
     MDQ_STAMP(0)
     double acc[2] = {0.0, 0.0};
@@ -3083,105 +3315,18 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
     // (the step's inflow factor is loaded where it is used, here and in front of the correction's rows, rather than held
     //  across the two solves between them)
     double ai = PG ? (frow ? frow[step] : 1.0) : inflow_factor(inflow_scale, b, nsteps, step);
-    for (int i = tid; i < n2; i += WG) {
-      double2 f = make_double2(0.0, 0.0);
-      for (int s = v.g2_ptr[i]; s < v.g2_ptr[i + 1]; ++s) {
-        const double2 c = escr2[v.g2_src[s]];
-        f.x += c.x;
-        f.y += c.y;
-      }
-      const double2 l = scaled2(ai, v.lift1[i]), id = v.idiag1[i];
-      const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
-      const double2 bi = fl ? g : make_double2((f.x - l.x) * id.x, (f.y - l.y) * id.y);
-      // initial guess: polynomial extrapolation in time of the previous tentative velocities h1 = u*_n .. h5 (the
-      // correction solve re-uses xs, so the history is kept separately; see at_velocity_kernel), u_n while there is
-      // no history; Dirichlet values hold
-      double2 x0 = v.u_n[i];
-      if (nhist >= 2) {
-        const double2 us1 = h1[i], us2 = h2[i];
-        x0 = make_double2(2.0 * us1.x - us2.x, 2.0 * us1.y - us2.y);
-        if (nhist >= 3) {
-          const double2 us3 = h3[i];
-          x0 = make_double2(3.0 * (us1.x - us2.x) + us3.x, 3.0 * (us1.y - us2.y) + us3.y);
-          if (nhist >= 4) {
-            const double2 us4 = h4[i];
-            x0 = make_double2(4.0 * (us1.x + us3.x) - 6.0 * us2.x - us4.x, 4.0 * (us1.y + us3.y) - 6.0 * us2.y - us4.y);
-            if (nhist >= 5) {
-              const double2 us5 = h5[i];
-              x0 = make_double2(5.0 * (us1.x - us4.x) - 10.0 * (us2.x - us3.x) + us5.x,
-                                5.0 * (us1.y - us4.y) - 10.0 * (us2.y - us3.y) + us5.y);
-            }
-          }
-        }
-      }
-      if (fl) x0 = g;
-      xs[i] = x0;
-      if (MF) {
-        if (MODE == 2) L0[i] = x0;
-        vc.r[i] = fl ? make_double2(0.0, 0.0) : make_double2(f.x * id.x, f.y * id.y);
-      } else {
-        vc.r[i] = bi;
-      }
-      acc[0] += bi.x * bi.x + bi.y * bi.y;
-    }
-    __syncthreads();
-    apply_velocity<MODE>(v, vc, MODE == 2 ? L0 : xs, [&](int row, double y0, double y1) {   // (mode 5 gathers x0 from xs)
-      const double2 bi = vc.r[row];
-      const double2 r0 = make_double2(bi.x - y0, bi.y - y1);
-      vc.r[row] = r0;
-      vc.rh[row] = r0;
-      vc.p[row] = make_double2(0.0, 0.0);
-      vc.vv[row] = make_double2(0.0, 0.0);
-      acc[1] += r0.x * r0.x + r0.y * r0.y;
-    });
-    block_sum<2>(acc, red);
+    velocity_rhs<MF>(rg, op_vel, v, vc, ai, escr2, nhist, H, red, acc);   // (mode 5 gathers x0 from xs)
     MDQ_STAMP(1)
-    it_u += bicgstab_velocity<MODE>(v, vc, d.rtol, d.maxit_u, acc[0], acc[1], red);
+    it_u += bicgstab_velocity(rg, op_vel, v, vc, d.rtol, d.maxit_u, acc[0], acc[1], red);
     __syncthreads();
-    for (int i = tid; i < n2; i += WG) {  // shift the history, newest first: h1 = u* of this step
-      if (nhist >= 4) h5[i] = h4[i];
-      if (nhist >= 3) h4[i] = h3[i];
-      if (nhist >= 2) h3[i] = h2[i];
-      if (nhist >= 1) h2[i] = h1[i];
-      h1[i] = xs[i];
-    }
+    rg.rows(n2, [&](int i) { history_shift(nhist, H, xs, i); });
     if (tid == 0) hcnt[0] = (double)(nhist < 5 ? nhist + 1 : 5);
     MDQ_STAMP(2)
 
     // ---------------- step 2: pressure  (flow_solver.py:115-116)
-    if (K1_LDS && !d.pd_enabled) {
-      const int ne1 = v.sl1_off[nsl1];
-      for (int k = tid; k < ne1; k += WG) {
-        lK[k] = v.K1s[k];
-        lci[k] = v.sl1_col[k];
-      }
-      for (int k = tid; k <= nsl1; k += WG) lso[k] = v.sl1_off[k];
-    }
     rhs2_elements(v, d, xs, v.p_n, escr1);
     __syncthreads();
-    for (int i = tid; i < nv; i += WG) {
-      double bsum = 0.0;
-      for (int s = v.g1_ptr[i]; s < v.g1_ptr[i + 1]; ++s) bsum += escr1[v.g1_src[s]];
-      const double sd = v.sdiagK[i];
-      pr[i] = v.bcp_flag[i] ? 0.0 : bsum / sd;
-      px[i] = v.p_n[i] * sd;
-    }
-    MDQ_STAMP(3)
-    if (!PG && d.pd_enabled && d.pd_hdr[4 * (int64_t)b + 2] > 0) {   // (nparts = 0: no factors for this environment -> Krylov)
-      const PdView pd = pd_view(d, b);
-      pressure_direct(pd, nv, pr, px, pp, pq, lK);
-    } else {
-      if constexpr (PG)      // (vectors in the slab - pp is a 2 N2-double vector there -, the preconditioner's tables in the LDS they leave free)
-        it_p += pressure_krylov_lds(d, false, nv, so1, ci1, K1, v.coords, px, pr, pp, pq, 2 * sizeof(double) * (size_t)d.N2, U,
-                                    MODE == 5 ? sizeof(double2) * 6 * MF_CH : tl_extra_bytes(d.NV) + sizeof(double) * NAG * NAG, red);
-      else
-        it_p += pressure_krylov_lds(d, K1_LDS, nv, so1, ci1, K1, v.coords, px, pr, pp, pq, 2 * sizeof(double) * (size_t)P.NVp, lK,
-                                    sizeof(double) * (size_t)P.NVp, red, MODE == 5 ? U : nullptr,     // (matrix on the chip: the tile modes only)
-                                    max(P.prs_vec_bytes + (K1_LDS ? P.prs_mat_bytes : 0), MODE == 5 ? tile_lds_bytes(d) : (size_t)0), P.NVp);
-    }
-    MDQ_STAMP(4)
-    for (int i = tid; i < nv; i += WG) pnew[i] = px[i] / v.sdiagK[i];
+    it_p += pressure_solve<K1_LDS, !PG>(v, d, b, escr1, L, pnew, ka, red, stamp);
     __syncthreads();
 
     // ---------------- step 3: velocity correction  (flow_solver.py:119-120)
@@ -3189,56 +3334,13 @@ __global__ __launch_bounds__(WG) void evolve_kernel(mdq_ipcs_desc d, int nsteps,
     __syncthreads();
     double am[2] = {0.0, 0.0};
     ai = PG ? (frow ? frow[step] : 1.0) : inflow_factor(inflow_scale, b, nsteps, step);
-    for (int i = tid; i < n2; i += WG) {
-      double2 f = make_double2(0.0, 0.0);
-      for (int s = v.g2_ptr[i]; s < v.g2_ptr[i + 1]; ++s) {
-        const double2 c = escr2[v.g2_src[s]];
-        f.x += c.x;
-        f.y += c.y;
-      }
-      const double2 l = scaled2(ai, v.lift3[i]);
-      const double sd = v.sdiagM[i];
-      const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
-      const double2 bi = fl ? g : make_double2((f.x - l.x) / sd, (f.y - l.y) / sd);
-      const double2 x0 = fl ? g : xs[i];
-      xs[i] = make_double2(x0.x * sd, x0.y * sd);  // scaled unknown S x
-      if (MF) {
-        stage[i] = x0;  // S^-1 (S x0)
-        mc.r[i] = fl ? make_double2(0.0, 0.0) : make_double2(f.x / sd, f.y / sd);
-      } else {
-        mc.r[i] = bi;
-      }
-      am[0] += bi.x * bi.x + bi.y * bi.y;
-    }
-    __syncthreads();
-    apply_mass<MODE>(v, mc, MF ? stage : xs, [&](int row, double y0, double y1) {
-      const double2 bi = mc.r[row];
-      const double2 r0 = make_double2(bi.x - y0, bi.y - y1);
-      mc.r[row] = r0;
-      mc.p[row] = r0;
-      am[1] += r0.x * r0.x + r0.y * r0.y;
-    });
-    block_sum<2>(am, red);
-    if (MF) {
-      // stage S^-1 p0 (own rows; the apply above is complete: block_sum barriers passed)
-      for (int i = tid; i < n2; i += WG) {
-        const double is = 1.0 / v.sdiagM[i];
-        const double2 p0 = mc.p[i];
-        stage[i] = make_double2(p0.x * is, p0.y * is);
-      }
-      __syncthreads();
-    }
+    correction_rhs<MF>(rg, op_mass, v, mc, ai, escr2, red, am);
     MDQ_STAMP(5)
-    it_m += cg_mass<MODE>(v, mc, d.rtol, d.maxit_m, am[0], am[1], red);
+    it_m += cg_mass<MF>(rg, op_mass, v, mc, d.rtol, d.maxit_m, am[0], am[1], red);   // (the update below reads own rows: no barrier)
     MDQ_STAMP(6)
 
     // ---------------- update state + probes  (flow_solver.py:382-389)
-    for (int i = tid; i < n2; i += WG) {
-      const double sd = v.sdiagM[i];
-      const double2 x = xs[i];
-      v.u_n[i] = make_double2(x.x / sd, x.y / sd);
-    }
+    update_velocity(rg, v, xs);
     for (int i = tid; i < nv; i += WG) v.p_n[i] = pnew[i];
     __syncthreads();
     double dr, li;
@@ -3284,7 +3386,10 @@ static hipError_t launch_evolve(const mdq_ipcs_desc* d, size_t lds, int nsteps, 
 // acquire - correct for any placement of the two workgroups (cdna_hip_programming.md, Guideline 16).  Reductions: each
 // workgroup's deterministic block sum goes to the team's slot array and both workgroups add the two partials in rank
 // order: every thread of the team sees the same bits.  The pressure solve (3 322 unknowns, LDS-resident vectors, direct
-// factors or CG) stays with rank 0.  Same arithmetic as evolve_kernel<0> except for the association of the reductions.
+// factors or CG) stays with rank 0.  Same arithmetic as evolve_kernel<0> except for the association of the reductions - by
+// construction: the step phases and the two Krylov solvers ARE evolve_kernel's code (velocity_rhs, bicgstab_velocity,
+// pressure_solve, correction_rhs, cg_mass, update_velocity), instantiated for the team's row group (TeamRows) and the SELL
+// products over the team's slices.  The kernel keeps its row ranges, the time-out handling (team_failed) and rank 0's solve.
 constexpr int TEAM = 2;
 struct Team {
   int rank;
@@ -3360,6 +3465,19 @@ __device__ __forceinline__ void team_sum(double (&v)[N], double* red, Team& t) {
   for (int n = 0; n < N; ++n) v[n] = s0[n] + s0[4 + n];
   t.par ^= 1;
 }
+// the row group of a team (see "Krylov solvers"): this thread's rows are first, first + stride, .. below `end` - dealt out
+// over the 2 WG threads of the team (mode 4) or the workgroup's contiguous half (mode 7) -, barriers and sums are the team's
+struct TeamRows {
+  Team& T;
+  int first, end, stride;
+  template <class F>
+  __device__ __forceinline__ void rows(int n, F f) const {
+    for (int i = first; i < min(end, n); i += stride) f(i);
+  }
+  __device__ __forceinline__ void sync() const { team_sync(T); }
+  template <int N>
+  __device__ __forceinline__ void sum(double (&acc)[N], double* red) const { team_sum<N>(acc, red, T); }
+};
 
 // A bounded spin of this team ran out in this launch (the partner workgroup was not resident for ~2^22 polls: another process
 // or another stream held its CU).  Read by every thread behind a team barrier.  The step that sees it does NOT advance u_n / p_n,
@@ -3420,13 +3538,7 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
   const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
   double* red = smem;
   double* U = smem + 64;
-  double* px = U;
-  double* pr = px + P.NVp;
-  double* pp = pr + P.NVp;
-  double* pq = pp + P.NVp;
-  double* lK = pq + P.NVp;
-  int32_t* lci = reinterpret_cast<int32_t*>(lK + d.NSE1);
-  int32_t* lso = lci + d.NSE1 + (d.NSE1 & 1);
+  const PrsLds L = prs_lds(U, P, d);
   double* w = v.work;
   double2* escr2 = reinterpret_cast<double2*>(w);
   double* escr1 = w;
@@ -3436,12 +3548,8 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
   double2* vp = vh + d.N2;
   double2* vv = vp + d.N2;
   double2* vt = vv + d.N2;
-  double2* h1 = reinterpret_cast<double2*>(w + work_hist_offset(d.NV, d.NT, d.NE));
-  double2* h2 = h1 + d.N2;
-  double2* h3 = h2 + d.N2;
-  double2* h4 = h3 + d.N2;
-  double2* h5 = h4 + d.N2;
-  double* hcnt = reinterpret_cast<double*>(h5 + d.N2);
+  const VelHist H = vel_hist(d, w);
+  double* hcnt = H.cnt;
   double* pnew = reinterpret_cast<double*>(vt + d.N2);
   double* spare = pnew + d.NV;
   Team T;
@@ -3450,12 +3558,12 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
   T.slot = spare + 9;
   T.epoch = 0;
   T.par = 0;
-  const int nsl1 = (nv + 63) >> 6;
-  const int32_t* so1 = K1_LDS ? lso : v.sl1_off;
-  const int32_t* ci1 = K1_LDS ? lci : v.sl1_col;
-  const double* K1 = K1_LDS ? lK : v.K1s;
+  const KrylovLds ka{2 * sizeof(double) * (size_t)P.NVp, L.lK, sizeof(double) * (size_t)P.NVp, nullptr, 0, 0};
   const double a = v.rho / v.dt;
   int it_u = 0, it_p = 0, it_m = 0;
+  const TeamRows rg{T, gt, n2, GS};
+  const VelCtx vc{xs, vr, vh, vp, vv, vt};
+  const MassCtx mc{xs, vr, vp, vv, vp};
   const int lane = tid & 63, gw = rank * NWAVE + (tid >> 6);
   constexpr int GW = TEAM * NWAVE;
   // SELL operator applications over the team's slices
@@ -3500,276 +3608,28 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
   for (int step = 0; step < nsteps; ++step) {
     const double ai = inflow_factor(inflow_scale, b, nsteps, step);
     // ---------------- step 1: tentative velocity
-    for (int e = gt; e < v.nt; e += GS) {
-      const ElemIdx E = load_dofs(v, e);
-      const Geo g = load_geo(v, e);
-      double2 ue[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) ue[i] = v.u_n[E.dof[i]];
-      double pe[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) pe[i] = v.p_n[E.dof[i]];
-      double2 rr_[6];
-      elem_rhs1_vol(g, a, v.mu, v.rho, ue, pe, rr_);
-      const int ko = v.cell_outflow[e];
-      if (ko >= 0) {
-        double X[3][2];
-        load_cell_coords(v, e, X);
-        elem_outflow_add(g, X, ko, 0.5 * v.mu, ue, rr_);
-      }
-#pragma unroll
-      for (int i = 0; i < 6; ++i) escr2[e * 6 + i] = rr_[i];
-    }
+    rhs1_elements(v, d, v.u_n, v.p_n, escr2, a, v.mu, gt, GS);
     team_sync(T);
     double acc[2] = {0.0, 0.0};
     const int nhist = (int)hcnt[0];
-    for (int i = gt; i < n2; i += GS) {
-      double2 f = make_double2(0.0, 0.0);
-      for (int s_ = v.g2_ptr[i]; s_ < v.g2_ptr[i + 1]; ++s_) {
-        const double2 c = escr2[v.g2_src[s_]];
-        f.x += c.x;
-        f.y += c.y;
-      }
-      const double2 l = scaled2(ai, v.lift1[i]), id = v.idiag1[i];
-      const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
-      const double2 bi = fl ? g : make_double2((f.x - l.x) * id.x, (f.y - l.y) * id.y);
-      double2 x0 = v.u_n[i];
-      if (nhist >= 2) {
-        const double2 us1 = h1[i], us2 = h2[i];
-        x0 = make_double2(2.0 * us1.x - us2.x, 2.0 * us1.y - us2.y);
-        if (nhist >= 3) {
-          const double2 us3 = h3[i];
-          x0 = make_double2(3.0 * (us1.x - us2.x) + us3.x, 3.0 * (us1.y - us2.y) + us3.y);
-          if (nhist >= 4) {
-            const double2 us4 = h4[i];
-            x0 = make_double2(4.0 * (us1.x + us3.x) - 6.0 * us2.x - us4.x, 4.0 * (us1.y + us3.y) - 6.0 * us2.y - us4.y);
-            if (nhist >= 5) {
-              const double2 us5 = h5[i];
-              x0 = make_double2(5.0 * (us1.x - us4.x) - 10.0 * (us2.x - us3.x) + us5.x,
-                                5.0 * (us1.y - us4.y) - 10.0 * (us2.y - us3.y) + us5.y);
-            }
-          }
-        }
-      }
-      if (fl) x0 = g;
-      xs[i] = x0;
-      vr[i] = bi;
-      acc[0] += bi.x * bi.x + bi.y * bi.y;
-    }
+    velocity_rhs<false>(rg, spmv_vel, v, vc, ai, escr2, nhist, H, red, acc);
+    it_u += bicgstab_velocity(rg, spmv_vel, v, vc, d.rtol, d.maxit_u, acc[0], acc[1], red);
     team_sync(T);
-    spmv_vel(xs, [&](int row, double y0, double y1) {
-      const double2 bi = vr[row];
-      const double2 r0 = make_double2(bi.x - y0, bi.y - y1);
-      vr[row] = r0;
-      vh[row] = r0;
-      vp[row] = make_double2(0.0, 0.0);
-      vv[row] = make_double2(0.0, 0.0);
-      acc[1] += r0.x * r0.x + r0.y * r0.y;
-    });
-    team_sum<2>(acc, red, T);
-    {  // BiCGStab (bicgstab_velocity<0>, rows and slices over the team)
-      const double bb = acc[0], tol2 = d.rtol * d.rtol * bb;
-      double rr = acc[1];
-      if (rr > tol2 && bb != 0.0) {
-        double rho = rr, rho_old = 1.0, alpha = 1.0, omega = 1.0;
-        int it = 0;
-        while (it < d.maxit_u) {
-          ++it;
-          const double beta = (rho / rho_old) * (alpha / omega);
-          for (int i = gt; i < n2; i += GS) {
-            const double2 ri = vr[i], pi = vp[i], vi = vv[i];
-            vp[i] = make_double2(ri.x + beta * (pi.x - omega * vi.x), ri.y + beta * (pi.y - omega * vi.y));
-          }
-          team_sync(T);
-          double a1[1] = {0.0};
-          spmv_vel(vp, [&](int row, double y0, double y1) {
-            vv[row] = make_double2(y0, y1);
-            const double2 h = vh[row];
-            a1[0] += h.x * y0 + h.y * y1;
-          });
-          team_sum<1>(a1, red, T);
-          if (a1[0] == 0.0) break;
-          alpha = rho / a1[0];
-          double a2[1] = {0.0};
-          for (int i = gt; i < n2; i += GS) {
-            const double2 ri = vr[i], vi = vv[i];
-            const double2 sv = make_double2(ri.x - alpha * vi.x, ri.y - alpha * vi.y);
-            vr[i] = sv;
-            a2[0] += sv.x * sv.x + sv.y * sv.y;
-          }
-          team_sum<1>(a2, red, T);       // (its team barrier also publishes s)
-          if (!(a2[0] > tol2)) {
-            for (int i = gt; i < n2; i += GS) {
-              const double2 xi = xs[i], pi = vp[i];
-              xs[i] = make_double2(xi.x + alpha * pi.x, xi.y + alpha * pi.y);
-            }
-            break;
-          }
-          double a3[2] = {0.0, 0.0};
-          spmv_vel(vr, [&](int row, double y0, double y1) {
-            vt[row] = make_double2(y0, y1);
-            const double2 sv = vr[row];
-            a3[0] += y0 * sv.x + y1 * sv.y;
-            a3[1] += y0 * y0 + y1 * y1;
-          });
-          team_sum<2>(a3, red, T);
-          if (a3[1] == 0.0) break;
-          omega = a3[0] / a3[1];
-          double a4[2] = {0.0, 0.0};
-          for (int i = gt; i < n2; i += GS) {
-            const double2 ti = vt[i], xi = xs[i], pi = vp[i], si = vr[i], hi = vh[i];
-            xs[i] = make_double2(xi.x + alpha * pi.x + omega * si.x, xi.y + alpha * pi.y + omega * si.y);
-            const double2 rn = make_double2(si.x - omega * ti.x, si.y - omega * ti.y);
-            vr[i] = rn;
-            a4[0] += rn.x * rn.x + rn.y * rn.y;
-            a4[1] += hi.x * rn.x + hi.y * rn.y;
-          }
-          team_sum<2>(a4, red, T);
-          rr = a4[0];
-          if (!(rr > tol2)) break;
-          rho_old = rho;
-          rho = a4[1];
-          if (rho == 0.0 || omega == 0.0) break;
-        }
-        it_u += it;
-      }
-    }
-    team_sync(T);
-    for (int i = gt; i < n2; i += GS) {  // history, newest first
-      if (nhist >= 4) h5[i] = h4[i];
-      if (nhist >= 3) h4[i] = h3[i];
-      if (nhist >= 2) h3[i] = h2[i];
-      if (nhist >= 1) h2[i] = h1[i];
-      h1[i] = xs[i];
-    }
+    rg.rows(n2, [&](int i) { history_shift(nhist, H, xs, i); });
     // ---------------- step 2: pressure (element loop by the team, the solve by rank 0)
-    {
-      const double idt = 1.0 / v.dt;
-      for (int e = gt; e < v.nt; e += GS) {
-        const ElemIdx E = load_dofs(v, e);
-        const Geo g = load_geo(v, e);
-        double2 ue[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) ue[i] = xs[E.dof[i]];
-        double pe[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) pe[i] = v.p_n[E.dof[i]];
-        double r3[3];
-        elem_rhs2(g, idt, ue, pe, r3);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) escr1[e * 3 + j] = r3[j];
-      }
-    }
+    rhs2_elements(v, d, xs, v.p_n, escr1, gt, GS);
     team_sync(T);
     if (rank == 0) {
       if (tid == 0) hcnt[0] = (double)(nhist < 5 ? nhist + 1 : 5);
-      if (K1_LDS && !d.pd_enabled) {
-        const int ne1 = v.sl1_off[nsl1];
-        for (int k = tid; k < ne1; k += WG) {
-          lK[k] = v.K1s[k];
-          lci[k] = v.sl1_col[k];
-        }
-        for (int k = tid; k <= nsl1; k += WG) lso[k] = v.sl1_off[k];
-      }
-      for (int i = tid; i < nv; i += WG) {
-        double bsum = 0.0;
-        for (int s_ = v.g1_ptr[i]; s_ < v.g1_ptr[i + 1]; ++s_) bsum += escr1[v.g1_src[s_]];
-        const double sd = v.sdiagK[i];
-        pr[i] = v.bcp_flag[i] ? 0.0 : bsum / sd;
-        px[i] = v.p_n[i] * sd;
-      }
-      if (d.pd_enabled && d.pd_hdr[4 * (int64_t)b + 2] > 0) {
-        const PdView pd = pd_view(d, b);
-        pressure_direct(pd, nv, pr, px, pp, pq, lK);
-      } else {
-        it_p += pressure_krylov_lds(d, K1_LDS, nv, so1, ci1, K1, v.coords, px, pr, pp, pq, 2 * sizeof(double) * (size_t)P.NVp, lK,
-                                    sizeof(double) * (size_t)P.NVp, red);
-      }
-      for (int i = tid; i < nv; i += WG) pnew[i] = px[i] / v.sdiagK[i];
+      it_p += pressure_solve<K1_LDS, true>(v, d, b, escr1, L, pnew, ka, red, [](int) {});
     }
     team_sync(T);
     // ---------------- step 3: velocity correction
-    for (int e = gt; e < v.nt; e += GS) {
-      const ElemIdx E = load_dofs(v, e);
-      const Geo g = load_geo(v, e);
-      double2 ue[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) ue[i] = xs[E.dof[i]];
-      double dp[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) dp[i] = pnew[E.dof[i]] - v.p_n[E.dof[i]];
-      double2 rr_[6];
-      elem_rhs3(g, v.dt, ue, dp, rr_);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) escr2[e * 6 + i] = rr_[i];
-    }
+    rhs3_elements(v, d, xs, pnew, v.p_n, escr2, gt, GS);
     team_sync(T);
     double am[2] = {0.0, 0.0};
-    for (int i = gt; i < n2; i += GS) {
-      double2 f = make_double2(0.0, 0.0);
-      for (int s_ = v.g2_ptr[i]; s_ < v.g2_ptr[i + 1]; ++s_) {
-        const double2 c = escr2[v.g2_src[s_]];
-        f.x += c.x;
-        f.y += c.y;
-      }
-      const double2 l = scaled2(ai, v.lift3[i]);
-      const double sd = v.sdiagM[i];
-      const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
-      const double2 bi = fl ? g : make_double2((f.x - l.x) / sd, (f.y - l.y) / sd);
-      const double2 x0 = fl ? g : xs[i];
-      xs[i] = make_double2(x0.x * sd, x0.y * sd);
-      vr[i] = bi;
-      am[0] += bi.x * bi.x + bi.y * bi.y;
-    }
-    team_sync(T);
-    spmv_mass(xs, [&](int row, double y0, double y1) {
-      const double2 bi = vr[row];
-      const double2 r0 = make_double2(bi.x - y0, bi.y - y1);
-      vr[row] = r0;
-      vp[row] = r0;
-      am[1] += r0.x * r0.x + r0.y * r0.y;
-    });
-    team_sum<2>(am, red, T);
-    {  // CG on the mass system (cg_mass<0>)
-      const double bb = am[0], tol2 = d.rtol * d.rtol * bb;
-      double rr = am[1];
-      if (rr > tol2 && bb != 0.0) {
-        int it = 0;
-        while (it < d.maxit_m) {
-          ++it;
-          double a1[1] = {0.0};
-          spmv_mass(vp, [&](int row, double y0, double y1) {
-            vv[row] = make_double2(y0, y1);
-            const double2 pi = vp[row];
-            a1[0] += pi.x * y0 + pi.y * y1;
-          });
-          team_sum<1>(a1, red, T);
-          if (!(a1[0] > 0.0)) break;
-          const double alpha = rr / a1[0];
-          double a2[1] = {0.0};
-          for (int i = gt; i < n2; i += GS) {
-            const double2 xi = xs[i], pi = vp[i], ri = vr[i], qi = vv[i];
-            xs[i] = make_double2(xi.x + alpha * pi.x, xi.y + alpha * pi.y);
-            const double2 rn = make_double2(ri.x - alpha * qi.x, ri.y - alpha * qi.y);
-            vr[i] = rn;
-            a2[0] += rn.x * rn.x + rn.y * rn.y;
-          }
-          team_sum<1>(a2, red, T);
-          const double rr_new = a2[0];
-          if (!(rr_new > tol2)) break;
-          const double beta = rr_new / rr;
-          rr = rr_new;
-          for (int i = gt; i < n2; i += GS) {
-            const double2 ri = vr[i], pi = vp[i];
-            vp[i] = make_double2(ri.x + beta * pi.x, ri.y + beta * pi.y);
-          }
-          team_sync(T);
-        }
-        it_m += it;
-      }
-    }
+    correction_rhs<false>(rg, spmv_mass, v, mc, ai, escr2, red, am);
+    it_m += cg_mass<false>(rg, spmv_mass, v, mc, d.rtol, d.maxit_m, am[0], am[1], red);
     team_sync(T);
     // ---------------- update state + probes
     if (team_failed(T)) {       // (see team_failed: the state stays the last good one, NaN forces from here on)
@@ -3780,11 +3640,7 @@ __global__ __launch_bounds__(WG) void evolve_team_kernel(mdq_ipcs_desc d, int ns
       }
       break;
     }
-    for (int i = gt; i < n2; i += GS) {
-      const double sd = v.sdiagM[i];
-      const double2 x = xs[i];
-      v.u_n[i] = make_double2(x.x / sd, x.y / sd);
-    }
+    update_velocity(rg, v, xs);
     for (int i = gt; i < nv; i += GS) v.p_n[i] = pnew[i];
     team_sync(T);
     if (rank == 0) {
@@ -3857,7 +3713,9 @@ static hipError_t launch_evolve_team(const mdq_ipcs_desc* d, size_t lds, int nst
 // vector pass - add the two partial sums in rank order and run the caller's epilogue.  Bitwise reproducible run to run;
 // NOT bitwise mode 5: a row's sum is (chunks 0, 2, 4, ..) + (chunks 1, 3, 5, ..) instead of chunk after chunk.  Without
 // tile maps (index data built on the device) the element results go to the slab's element scratch, triangles and rows
-// dealt out over the team.  Right-hand sides, the pressure solve (rank 0) and the probes: as in mode 4.
+// dealt out over the team.  Right-hand sides, the pressure solve (rank 0) and the probes: as in mode 4, and the step phases
+// and solvers are the same code as evolve_kernel<5>'s (tile forms of velocity_rhs / correction_rhs, the staged cg_mass),
+// instantiated for the team's row group over each workgroup's contiguous half of the rows and tile_apply_team.
 // Which rows a workgroup's chunks touch (t0 / t1: one byte per row) and which entries of its chunks' row lists are the first
 // touch of their row in the workgroup's walk (first: one byte per entry) - built once per launch from the row lists: a
 // tile application then neither zero-fills the two accumulation vectors nor reads a partial sum that does not exist
@@ -3963,13 +3821,7 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
   double* red = smem;
   double* U = smem + 64;
   // pressure view of the union (rank 0 only) | velocity view: the element tile (+ the staged rows of a chunk)
-  double* px = U;
-  double* pr = px + P.NVp;
-  double* pp = pr + P.NVp;
-  double* pq = pp + P.NVp;
-  double* lK = pq + P.NVp;
-  int32_t* lci = reinterpret_cast<int32_t*>(lK + d.NSE1);
-  int32_t* lso = lci + d.NSE1 + (d.NSE1 & 1);
+  const PrsLds L = prs_lds(U, P, d);
   double2* es = reinterpret_cast<double2*>(U);
   double* w = v.work;
   double2* escr2 = reinterpret_cast<double2*>(w);
@@ -3980,12 +3832,8 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
   double2* vp = vh + d.N2;
   double2* vv = vp + d.N2;
   double2* vt = vv + d.N2;
-  double2* h1 = reinterpret_cast<double2*>(w + work_hist_offset(d.NV, d.NT, d.NE));
-  double2* h2 = h1 + d.N2;
-  double2* h3 = h2 + d.N2;
-  double2* h4 = h3 + d.N2;
-  double2* h5 = h4 + d.N2;
-  double* hcnt = reinterpret_cast<double*>(h5 + d.N2);
+  const VelHist H = vel_hist(d, w);
+  double* hcnt = H.cnt;
   double2* y0v = reinterpret_cast<double2*>(w + work_ytmp_offset(d.NV, d.NT, d.NE));   // the workgroups' accumulation vectors
   double2* y1v = y0v + d.N2 + 1;
   TeamTouch tt;
@@ -4012,13 +3860,14 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
     T.rbeg = rank ? split : 0;
     T.rend = rank ? n2 : split;
   }
-  const int nsl1 = (nv + 63) >> 6;
-  const int32_t* so1 = K1_LDS ? lso : v.sl1_off;
-  const int32_t* ci1 = K1_LDS ? lci : v.sl1_col;
-  const double* K1 = K1_LDS ? lK : v.K1s;
+  const KrylovLds ka{2 * sizeof(double) * (size_t)P.NVp, L.lK, sizeof(double) * (size_t)P.NVp, U,
+                     max(P.prs_vec_bytes + (K1_LDS ? P.prs_mat_bytes : 0), tile_lds_bytes(d)), P.NVp};
   const double a = v.rho / v.dt, mu = v.mu;
   const bool packed = d.N2 <= 4096;
   int it_u = 0, it_p = 0, it_m = 0;
+  const TeamRows rg{T, T.rbeg + tid, T.rend, WG};
+  const VelCtx vc{xs, vr, vh, vp, vv, vt};
+  const MassCtx mc{xs, vr, vp, vv, stage};
   // y = D^-1 A x (0 on constrained rows) / y = S^-1 M x' on the team's rows
   auto apply_vel = [&](const double2* gx, auto epi) {
     tile_apply_team(
@@ -4045,287 +3894,28 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
   for (int step = 0; step < nsteps; ++step) {
     const double ai = inflow_factor(inflow_scale, b, nsteps, step);
     // ---------------- step 1: tentative velocity
-    for (int e = gt; e < v.nt; e += GS) {
-      const ElemIdx E = load_dofs(v, e);
-      const Geo g = load_geo(v, e);
-      double2 ue[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) ue[i] = v.u_n[E.dof[i]];
-      double pe[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) pe[i] = v.p_n[E.dof[i]];
-      double2 rr_[6];
-      elem_rhs1_vol(g, a, mu, v.rho, ue, pe, rr_);
-      const int ko = v.cell_outflow[e];
-      if (ko >= 0) {
-        double X[3][2];
-        load_cell_coords(v, e, X);
-        elem_outflow_add(g, X, ko, 0.5 * mu, ue, rr_);
-      }
-#pragma unroll
-      for (int i = 0; i < 6; ++i) escr2[e * 6 + i] = rr_[i];
-    }
+    rhs1_elements(v, d, v.u_n, v.p_n, escr2, a, mu, gt, GS);
     team_sync(T);
     double acc[2] = {0.0, 0.0};
     const int nhist = (int)hcnt[0];
-    for (int i = T.rbeg + tid; i < T.rend; i += WG) {
-      double2 f = make_double2(0.0, 0.0);
-      for (int s_ = v.g2_ptr[i]; s_ < v.g2_ptr[i + 1]; ++s_) {
-        const double2 c = escr2[v.g2_src[s_]];
-        f.x += c.x;
-        f.y += c.y;
-      }
-      const double2 l = scaled2(ai, v.lift1[i]), id = v.idiag1[i];
-      const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
-      const double2 bi = fl ? g : make_double2((f.x - l.x) * id.x, (f.y - l.y) * id.y);
-      double2 x0 = v.u_n[i];
-      if (nhist >= 2) {
-        const double2 us1 = h1[i], us2 = h2[i];
-        x0 = make_double2(2.0 * us1.x - us2.x, 2.0 * us1.y - us2.y);
-        if (nhist >= 3) {
-          const double2 us3 = h3[i];
-          x0 = make_double2(3.0 * (us1.x - us2.x) + us3.x, 3.0 * (us1.y - us2.y) + us3.y);
-          if (nhist >= 4) {
-            const double2 us4 = h4[i];
-            x0 = make_double2(4.0 * (us1.x + us3.x) - 6.0 * us2.x - us4.x, 4.0 * (us1.y + us3.y) - 6.0 * us2.y - us4.y);
-            if (nhist >= 5) {
-              const double2 us5 = h5[i];
-              x0 = make_double2(5.0 * (us1.x - us4.x) - 10.0 * (us2.x - us3.x) + us5.x,
-                                5.0 * (us1.y - us4.y) - 10.0 * (us2.y - us3.y) + us5.y);
-            }
-          }
-        }
-      }
-      if (fl) x0 = g;
-      xs[i] = x0;
-      vr[i] = fl ? make_double2(0.0, 0.0) : make_double2(f.x * id.x, f.y * id.y);   // (full operator on x0: no lifting vector)
-      acc[0] += bi.x * bi.x + bi.y * bi.y;
-    }
+    velocity_rhs<true>(rg, apply_vel, v, vc, ai, escr2, nhist, H, red, acc);
+    it_u += bicgstab_velocity(rg, apply_vel, v, vc, d.rtol, d.maxit_u, acc[0], acc[1], red);
     team_sync(T);
-    apply_vel(xs, [&](int row, double y0, double y1) {
-      const double2 bi = vr[row];
-      const double2 r0 = make_double2(bi.x - y0, bi.y - y1);
-      vr[row] = r0;
-      vh[row] = r0;
-      vp[row] = make_double2(0.0, 0.0);
-      vv[row] = make_double2(0.0, 0.0);
-      acc[1] += r0.x * r0.x + r0.y * r0.y;
-    });
-    team_sum<2>(acc, red, T);
-    {  // BiCGStab (bicgstab_velocity<5>, rows and chunks over the team)
-      const double bb = acc[0], tol2 = d.rtol * d.rtol * bb;
-      double rr = acc[1];
-      if (rr > tol2 && bb != 0.0) {
-        double rho = rr, rho_old = 1.0, alpha = 1.0, omega = 1.0;
-        int it = 0;
-        while (it < d.maxit_u) {
-          ++it;
-          const double beta = (rho / rho_old) * (alpha / omega);
-          for (int i = T.rbeg + tid; i < T.rend; i += WG) {
-            const double2 ri = vr[i], pi = vp[i], vi = vv[i];
-            vp[i] = make_double2(ri.x + beta * (pi.x - omega * vi.x), ri.y + beta * (pi.y - omega * vi.y));
-          }
-          team_sync(T);
-          double a1[1] = {0.0};
-          apply_vel(vp, [&](int row, double y0, double y1) {
-            vv[row] = make_double2(y0, y1);
-            const double2 h = vh[row];
-            a1[0] += h.x * y0 + h.y * y1;
-          });
-          team_sum<1>(a1, red, T);
-          if (a1[0] == 0.0) break;
-          alpha = rho / a1[0];
-          double a2[1] = {0.0};
-          for (int i = T.rbeg + tid; i < T.rend; i += WG) {
-            const double2 ri = vr[i], vi = vv[i];
-            const double2 sv = make_double2(ri.x - alpha * vi.x, ri.y - alpha * vi.y);
-            vr[i] = sv;
-            a2[0] += sv.x * sv.x + sv.y * sv.y;
-          }
-          team_sum<1>(a2, red, T);       // (its team barrier also publishes s)
-          if (!(a2[0] > tol2)) {
-            for (int i = T.rbeg + tid; i < T.rend; i += WG) {
-              const double2 xi = xs[i], pi = vp[i];
-              xs[i] = make_double2(xi.x + alpha * pi.x, xi.y + alpha * pi.y);
-            }
-            break;
-          }
-          double a3[2] = {0.0, 0.0};
-          apply_vel(vr, [&](int row, double y0, double y1) {
-            vt[row] = make_double2(y0, y1);
-            const double2 sv = vr[row];
-            a3[0] += y0 * sv.x + y1 * sv.y;
-            a3[1] += y0 * y0 + y1 * y1;
-          });
-          team_sum<2>(a3, red, T);
-          if (a3[1] == 0.0) break;
-          omega = a3[0] / a3[1];
-          double a4[2] = {0.0, 0.0};
-          for (int i = T.rbeg + tid; i < T.rend; i += WG) {
-            const double2 ti = vt[i], xi = xs[i], pi = vp[i], si = vr[i], hi = vh[i];
-            xs[i] = make_double2(xi.x + alpha * pi.x + omega * si.x, xi.y + alpha * pi.y + omega * si.y);
-            const double2 rn = make_double2(si.x - omega * ti.x, si.y - omega * ti.y);
-            vr[i] = rn;
-            a4[0] += rn.x * rn.x + rn.y * rn.y;
-            a4[1] += hi.x * rn.x + hi.y * rn.y;
-          }
-          team_sum<2>(a4, red, T);
-          rr = a4[0];
-          if (!(rr > tol2)) break;
-          rho_old = rho;
-          rho = a4[1];
-          if (rho == 0.0 || omega == 0.0) break;
-        }
-        it_u += it;
-      }
-    }
-    team_sync(T);
-    for (int i = T.rbeg + tid; i < T.rend; i += WG) {  // history, newest first
-      if (nhist >= 4) h5[i] = h4[i];
-      if (nhist >= 3) h4[i] = h3[i];
-      if (nhist >= 2) h3[i] = h2[i];
-      if (nhist >= 1) h2[i] = h1[i];
-      h1[i] = xs[i];
-    }
+    rg.rows(n2, [&](int i) { history_shift(nhist, H, xs, i); });
     // ---------------- step 2: pressure (element loop by the team, the solve by rank 0)
-    {
-      const double idt = 1.0 / v.dt;
-      for (int e = gt; e < v.nt; e += GS) {
-        const ElemIdx E = load_dofs(v, e);
-        const Geo g = load_geo(v, e);
-        double2 ue[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) ue[i] = xs[E.dof[i]];
-        double pe[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) pe[i] = v.p_n[E.dof[i]];
-        double r3[3];
-        elem_rhs2(g, idt, ue, pe, r3);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) escr1[e * 3 + j] = r3[j];
-      }
-    }
+    rhs2_elements(v, d, xs, v.p_n, escr1, gt, GS);
     team_sync(T);
     if (rank == 0) {
       if (tid == 0) hcnt[0] = (double)(nhist < 5 ? nhist + 1 : 5);
-      if (K1_LDS && !d.pd_enabled) {
-        const int ne1 = v.sl1_off[nsl1];
-        for (int k = tid; k < ne1; k += WG) {
-          lK[k] = v.K1s[k];
-          lci[k] = v.sl1_col[k];
-        }
-        for (int k = tid; k <= nsl1; k += WG) lso[k] = v.sl1_off[k];
-      }
-      for (int i = tid; i < nv; i += WG) {
-        double bsum = 0.0;
-        for (int s_ = v.g1_ptr[i]; s_ < v.g1_ptr[i + 1]; ++s_) bsum += escr1[v.g1_src[s_]];
-        const double sd = v.sdiagK[i];
-        pr[i] = v.bcp_flag[i] ? 0.0 : bsum / sd;
-        px[i] = v.p_n[i] * sd;
-      }
-      if (d.pd_enabled && d.pd_hdr[4 * (int64_t)b + 2] > 0) {
-        const PdView pd = pd_view(d, b);
-        pressure_direct(pd, nv, pr, px, pp, pq, lK);
-      } else {
-        it_p += pressure_krylov_lds(d, K1_LDS, nv, so1, ci1, K1, v.coords, px, pr, pp, pq, 2 * sizeof(double) * (size_t)P.NVp, lK,
-                                    sizeof(double) * (size_t)P.NVp, red, U,
-                                    max(P.prs_vec_bytes + (K1_LDS ? P.prs_mat_bytes : 0), tile_lds_bytes(d)), P.NVp);
-      }
-      for (int i = tid; i < nv; i += WG) pnew[i] = px[i] / v.sdiagK[i];
+      it_p += pressure_solve<K1_LDS, true>(v, d, b, escr1, L, pnew, ka, red, [](int) {});
     }
     team_sync(T);
     // ---------------- step 3: velocity correction
-    for (int e = gt; e < v.nt; e += GS) {
-      const ElemIdx E = load_dofs(v, e);
-      const Geo g = load_geo(v, e);
-      double2 ue[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) ue[i] = xs[E.dof[i]];
-      double dp[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) dp[i] = pnew[E.dof[i]] - v.p_n[E.dof[i]];
-      double2 rr_[6];
-      elem_rhs3(g, v.dt, ue, dp, rr_);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) escr2[e * 6 + i] = rr_[i];
-    }
+    rhs3_elements(v, d, xs, pnew, v.p_n, escr2, gt, GS);
     team_sync(T);
     double am[2] = {0.0, 0.0};
-    for (int i = T.rbeg + tid; i < T.rend; i += WG) {
-      double2 f = make_double2(0.0, 0.0);
-      for (int s_ = v.g2_ptr[i]; s_ < v.g2_ptr[i + 1]; ++s_) {
-        const double2 c = escr2[v.g2_src[s_]];
-        f.x += c.x;
-        f.y += c.y;
-      }
-      const double2 l = scaled2(ai, v.lift3[i]);
-      const double sd = v.sdiagM[i];
-      const bool fl = v.bcu_flag[i] != 0;
-      const double2 g = make_double2(ai * v.bcu_gx[i], 0.0);
-      const double2 bi = fl ? g : make_double2((f.x - l.x) / sd, (f.y - l.y) / sd);
-      const double2 x0 = fl ? g : xs[i];
-      xs[i] = make_double2(x0.x * sd, x0.y * sd);   // scaled unknown S x
-      stage[i] = x0;                                 // S^-1 (S x0)
-      vr[i] = fl ? make_double2(0.0, 0.0) : make_double2(f.x / sd, f.y / sd);
-      am[0] += bi.x * bi.x + bi.y * bi.y;
-    }
-    team_sync(T);
-    apply_mass(stage, [&](int row, double y0, double y1) {
-      const double2 bi = vr[row];
-      const double2 r0 = make_double2(bi.x - y0, bi.y - y1);
-      vr[row] = r0;
-      vp[row] = r0;
-      am[1] += r0.x * r0.x + r0.y * r0.y;
-    });
-    team_sum<2>(am, red, T);          // (every gather of x0 from `stage` is behind its team barrier)
-    for (int i = T.rbeg + tid; i < T.rend; i += WG) {
-      const double is = 1.0 / v.sdiagM[i];
-      const double2 p0 = vp[i];
-      stage[i] = make_double2(p0.x * is, p0.y * is);
-    }
-    team_sync(T);
-    {  // CG on the mass system (cg_mass<5>)
-      const double bb = am[0], tol2 = d.rtol * d.rtol * bb;
-      double rr = am[1];
-      if (rr > tol2 && bb != 0.0) {
-        int it = 0;
-        while (it < d.maxit_m) {
-          ++it;
-          double a1[1] = {0.0};
-          apply_mass(stage, [&](int row, double y0, double y1) {
-            vv[row] = make_double2(y0, y1);
-            const double2 pi = vp[row];
-            a1[0] += pi.x * y0 + pi.y * y1;
-          });
-          team_sum<1>(a1, red, T);
-          if (!(a1[0] > 0.0)) break;
-          const double alpha = rr / a1[0];
-          double a2[1] = {0.0};
-          for (int i = T.rbeg + tid; i < T.rend; i += WG) {
-            const double2 xi = xs[i], pi = vp[i], ri = vr[i], qi = vv[i];
-            xs[i] = make_double2(xi.x + alpha * pi.x, xi.y + alpha * pi.y);
-            const double2 rn = make_double2(ri.x - alpha * qi.x, ri.y - alpha * qi.y);
-            vr[i] = rn;
-            a2[0] += rn.x * rn.x + rn.y * rn.y;
-          }
-          team_sum<1>(a2, red, T);
-          const double rr_new = a2[0];
-          if (!(rr_new > tol2)) break;
-          const double beta = rr_new / rr;
-          rr = rr_new;
-          for (int i = T.rbeg + tid; i < T.rend; i += WG) {
-            const double2 ri = vr[i], pi = vp[i];
-            const double2 pn = make_double2(ri.x + beta * pi.x, ri.y + beta * pi.y);
-            vp[i] = pn;
-            const double is = 1.0 / v.sdiagM[i];
-            stage[i] = make_double2(pn.x * is, pn.y * is);
-          }
-          team_sync(T);
-        }
-        it_m += it;
-      }
-    }
+    correction_rhs<true>(rg, apply_mass, v, mc, ai, escr2, red, am);
+    it_m += cg_mass<true>(rg, apply_mass, v, mc, d.rtol, d.maxit_m, am[0], am[1], red);
     team_sync(T);
     // ---------------- update state + probes
     if (team_failed(T)) {       // (see team_failed: the state stays the last good one, NaN forces from here on)
@@ -4336,11 +3926,7 @@ __global__ __launch_bounds__(WG) void evolve_team_tiles_kernel(mdq_ipcs_desc d, 
       }
       break;
     }
-    for (int i = T.rbeg + tid; i < T.rend; i += WG) {
-      const double sd = v.sdiagM[i];
-      const double2 x = xs[i];
-      v.u_n[i] = make_double2(x.x / sd, x.y / sd);
-    }
+    update_velocity(rg, v, xs);
     for (int i = gt; i < nv; i += GS) v.p_n[i] = pnew[i];
     team_sync(T);
     if (rank == 0) {
@@ -4442,12 +4028,8 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
   // initial guesses extrapolated in time: the last five tentative velocities (same slots and counter as evolve_kernel:
   // h1 = newest) and a ring of the last three velocity corrections u_{n+1} - u*.  Every row is read and written by its
   // owner only.
-  double2* h1 = reinterpret_cast<double2*>(w + work_hist_offset(d.NV, d.NT, d.NE));
-  double2* h2 = h1 + d.N2;
-  double2* h3 = h2 + d.N2;
-  double2* h4 = h3 + d.N2;
-  double2* h5 = h4 + d.N2;
-  double* hcnt = reinterpret_cast<double*>(h5 + d.N2);   // [0]: tentative velocities stored, [1]: corrections stored
+  const VelHist H = vel_hist(d, w);
+  double* hcnt = H.cnt;   // [0]: tentative velocities stored, [1]: corrections stored
   double2* c1 = xs + 2 * (int64_t)d.N2;                  // newest correction
   double2* c2 = c1 + d.N2;
   double2* c3 = c2 + d.N2;
@@ -4483,24 +4065,7 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
     // formulas); it satisfies the Dirichlet values
 #pragma unroll 1
     for (int row = tid; row < n2; row += WG) {
-      double2 x0 = v.u_n[row];
-      if (nhist >= 2) {
-        const double2 us1 = h1[row], us2 = h2[row];
-        x0 = make_double2(2.0 * us1.x - us2.x, 2.0 * us1.y - us2.y);
-        if (nhist >= 3) {
-          const double2 us3 = h3[row];
-          x0 = make_double2(3.0 * (us1.x - us2.x) + us3.x, 3.0 * (us1.y - us2.y) + us3.y);
-          if (nhist >= 4) {
-            const double2 us4 = h4[row];
-            x0 = make_double2(4.0 * (us1.x + us3.x) - 6.0 * us2.x - us4.x, 4.0 * (us1.y + us3.y) - 6.0 * us2.y - us4.y);
-            if (nhist >= 5) {
-              const double2 us5 = h5[row];
-              x0 = make_double2(5.0 * (us1.x - us4.x) - 10.0 * (us2.x - us3.x) + us5.x,
-                                5.0 * (us1.y - us4.y) - 10.0 * (us2.y - us3.y) + us5.y);
-            }
-          }
-        }
-      }
+      double2 x0 = extrapolate_x0(nhist, v.u_n[row], H, row);
       if (v.bcu_flag[row] != 0) x0 = make_double2(ai * v.bcu_gx[row], 0.0);
       xs[row] = x0;
       stage[row] = x0;
@@ -4677,13 +4242,7 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
       }
     }
 #pragma unroll 1
-    for (int row = tid; row < n2; row += WG) {   // shift the history, newest first: h1 = u* of this step (own rows)
-      if (nhist >= 4) h5[row] = h4[row];
-      if (nhist >= 3) h4[row] = h3[row];
-      if (nhist >= 2) h3[row] = h2[row];
-      if (nhist >= 1) h2[row] = h1[row];
-      h1[row] = xs[row];
-    }
+    for (int row = tid; row < n2; row += WG) history_shift(nhist, H, xs, row);   // (own rows)
     if (tid == 0) hcnt[0] = (double)(nhist < 5 ? nhist + 1 : 5);
     if (tid == 0 && iters) iters[3 * b + 0] += it_u;
   } else if constexpr (PHASE == 2) {
@@ -4981,13 +4540,8 @@ __device__ __forceinline__ void atomic_accumulate(const EnvView& v, double* Yd, 
         if (e < v.nt) {
 #pragma unroll
           for (int i = 0; i < 6; ++i) {
-#ifdef MDQ_AT_U64HACK   // timing experiment only (wrong numerics): 64-bit integer atomics instead of fp64 ones
-            atomicAdd(reinterpret_cast<unsigned long long*>(Yd) + 2 * dof[j][i], (unsigned long long)__double_as_longlong(ye[j][i].x) >> 40);
-            atomicAdd(reinterpret_cast<unsigned long long*>(Yd) + 2 * dof[j][i] + 1, (unsigned long long)__double_as_longlong(ye[j][i].y) >> 40);
-#else
             unsafeAtomicAdd(Yd + 2 * dof[j][i], ye[j][i].x);
             unsafeAtomicAdd(Yd + 2 * dof[j][i] + 1, ye[j][i].y);
-#endif
           }
         }
       }
@@ -5006,13 +4560,8 @@ __device__ __forceinline__ void atomic_accumulate(const EnvView& v, double* Yd, 
           op(e, gj, E, ((wj[0] >> 28) & 3) - 1, ye);
 #pragma unroll
           for (int i = 0; i < 6; ++i) {
-#ifdef MDQ_AT_U64HACK
-            atomicAdd(reinterpret_cast<unsigned long long*>(Yd) + 2 * E.dof[i], (unsigned long long)__double_as_longlong(ye[i].x) >> 40);
-            atomicAdd(reinterpret_cast<unsigned long long*>(Yd) + 2 * E.dof[i] + 1, (unsigned long long)__double_as_longlong(ye[i].y) >> 40);
-#else
             unsafeAtomicAdd(Yd + 2 * E.dof[i], ye[i].x);
             unsafeAtomicAdd(Yd + 2 * E.dof[i] + 1, ye[i].y);
-#endif
           }
         }
       }
