@@ -292,6 +292,16 @@ MDQ_API int mdq_ipcs_evolve_inflow(const mdq_ipcs_desc* d, int32_t nsteps, doubl
                     int32_t* iters, const double* inflow_scale, void* stream);
 
 /*
+ * mdq_ipcs_reset_history(d, iters) followed by mdq_ipcs_evolve_inflow(...) without the reset launch where the mode allows
+ * it (appended within ABI 8).  Mode 3: the three kernels of the launch's FIRST step take the history as empty (no stored
+ * tentative velocities, an empty correction ring, no lagged |b|), assign the iteration words instead of adding to them and
+ * write the counters they write anyway - one launch and its gap less on the flow chain of every S3 env step.  Every other
+ * mode: the reset kernel is launched in front of the evolve kernel, as the two calls would.
+ */
+MDQ_API int mdq_ipcs_evolve_fresh(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift,
+                    int32_t* iters, const double* inflow_scale, void* stream);
+
+/*
  * Same as mdq_ipcs_evolve (`FlowSolver.evolve`, flow_solver.py:362-396) for the three-kernel mode 3, with HIP events recorded on `stream` around every
  * kernel launch; the accumulated durations (milliseconds over all nsteps) of the velocity / pressure /
  * correction kernels are returned in host array kernel_ms[3].  Synchronises the stream (measurement aid).

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdlib>
 
 #include "../../include/meshdqn_hip.h"
 #include "mdq_internal.h"
@@ -790,6 +791,7 @@ __global__ __launch_bounds__(WGT) void gcn_embed_kernel(mdq_gcn_net net, int NMA
 
 // ------------------------------------------------------------------ MLP head on the matrix cores
 typedef float floatx16 __attribute__((ext_vector_type(16)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // OUT[32][ncols] = act( IN[32][K] * W[K][ncols] + bias ), IN / OUT in LDS (row-major), W in global
 // (row-major [K][ncols] = transposed torch weight).  4 waves, one 32x32 block each per pass.
@@ -835,6 +837,7 @@ __device__ inline void head_layer(const float* in, int in_stride, int K, const f
   }
 }
 
+template <int ROWS = 32, int NTH = WGH>
 __device__ __forceinline__ void head_store(const mdq_gcn_net& net, int B, int g0, const float* a3, int OUTP, float* out);
 
 __global__ __launch_bounds__(WGH) void mlp_head_kernel(mdq_gcn_net net, int B, const float* emb, float* out) {
@@ -901,10 +904,11 @@ __device__ __forceinline__ void head_mma(const float* in, int in_stride, const f
   }
 }
 
+template <int ROWS, int NTH>
 __device__ __forceinline__ void head_store(const mdq_gcn_net& net, int B, int g0, const float* a3, int OUTP, float* out) {
   const int tid = threadIdx.x, OUT = net.out_dim;
   const int lane = tid & 63, wave = tid >> 6;
-  for (int r = wave; r < 32; r += WGH / 64) {
+  for (int r = wave; r < ROWS; r += NTH / 64) {
     if (g0 + r >= B) continue;
     const float* row = a3 + r * OUTP;
     if (net.softmax) {
@@ -963,6 +967,89 @@ __global__ __launch_bounds__(WGH) void mlp_head_c128_kernel(mdq_gcn_net net, int
   head_store(net, B, g0, a3, OUTP, out);
 }
 
+// The C = 128 head on tiles of 16 graphs: (B + 15) / 16 workgroups of 8 waves instead of (B + 31) / 32 of 4 (4 workgroups for
+// the 128 graphs of an env step, on a chain where every other kernel has 128), and v_mfma_f32_16x16x4_f32 instead of
+// 32x32x2: the same sequential fma chain over k per output (tools/micro/mfma_exact.hip), so the outputs are bitwise those of
+// mlp_head_c128_kernel, at half the latency per dependent instruction and half the instructions per layer - 64 + 32 + 2 x 16
+// dependent MFMAs on the critical path instead of 128 + 64 + 2 x 32.  Wave w owns the 16-column blocks w, w + 8, ... of a
+// layer and loads all their weights up front (128 values per lane).  Row strides = 4 mod 64 floats: the A-operand reads (16
+// rows x 4 consecutive k) and the result writes (4 x 4 rows x 16 columns) each touch 64 distinct banks.
+constexpr int WGH16 = 512;
+
+template <int KQ>
+__device__ __forceinline__ void head16_wload(const float* __restrict__ W, int ncols, int blk, float (&bv)[KQ]) {
+  const int lane = threadIdx.x & 63, kq = lane >> 4;
+  const int col = min(blk * 16 + (lane & 15), ncols - 1);   // (columns past ncols: any valid address, never stored)
+#pragma unroll
+  for (int u = 0; u < KQ; ++u) bv[u] = W[(size_t)(4 * u + kq) * ncols + col];
+}
+
+template <int KQ>
+__device__ __forceinline__ void head16_mma(const float* in, int in_stride, const float (&bv)[KQ], float bc, int ncols, int blk,
+                                           float* out, int out_stride, bool relu) {
+  const int lane = threadIdx.x & 63, kq = lane >> 4, col = blk * 16 + (lane & 15);
+  floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+  constexpr int KU = 16;
+#pragma unroll
+  for (int u0 = 0; u0 < KQ; u0 += KU) {
+    float a[KU];
+#pragma unroll
+    for (int u = 0; u < KU; ++u) a[u] = in[(lane & 15) * in_stride + 4 * (u0 + u) + kq];
+#pragma unroll
+    for (int u = 0; u < KU; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], bv[u0 + u], acc, 0, 0, 0);
+  }
+  if (col < ncols) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float v = acc[r] + bc;
+      if (relu) v = v > 0.f ? v : 0.f;
+      out[(4 * kq + r) * out_stride + col] = v;
+    }
+  }
+}
+
+__global__ __launch_bounds__(WGH16) void mlp_head_c128_t16_kernel(mdq_gcn_net net, int B, const float* emb, float* out) {
+  extern __shared__ __align__(16) float sm[];
+  constexpr int K1 = 256, S0 = K1 + 4, S1 = 128 + 4, S2 = 64 + 4;
+  const int tid = threadIdx.x, OUT = net.out_dim, lane = tid & 63, wave = tid >> 6;
+  const int nblk3 = (OUT + 15) / 16, OUTP = 16 * nblk3;     // (OUT <= 256: at most two blocks per wave)
+  float* a0 = sm;               // [16][S0]
+  float* a1 = a0 + 16 * S0;     // [16][S1]
+  float* a2 = a1 + 16 * S1;     // [16][S2]
+  float* a3 = a2 + 16 * S2;     // [16][OUTP]
+  const int g0 = blockIdx.x * 16;
+  // every weight this wave will use (wave-uniform branches)
+  float w1[64], w2[32], w3a[16], w3b[16];
+  float b1, b2 = 0.f, b3a = 0.f, b3b = 0.f;
+  head16_wload<64>(net.lin1_w, 128, wave, w1);
+  b1 = net.lin1_b[wave * 16 + (lane & 15)];
+  if (wave < 4) {
+    head16_wload<32>(net.lin2_w, 64, wave, w2);
+    b2 = net.lin2_b[wave * 16 + (lane & 15)];
+  }
+  if (wave < nblk3) {
+    head16_wload<16>(net.lin3_w, OUT, wave, w3a);
+    b3a = net.lin3_b[min(wave * 16 + (lane & 15), OUT - 1)];
+  }
+  if (wave + 8 < nblk3) {
+    head16_wload<16>(net.lin3_w, OUT, wave + 8, w3b);
+    b3b = net.lin3_b[min((wave + 8) * 16 + (lane & 15), OUT - 1)];
+  }
+  for (int idx = tid; idx < 16 * K1; idx += WGH16) {
+    const int r = idx / K1, c = idx - r * K1;
+    a0[r * S0 + c] = (g0 + r < B) ? emb[(size_t)(g0 + r) * K1 + c] : 0.f;
+  }
+  __syncthreads();
+  head16_mma<64>(a0, S0, w1, b1, 128, wave, a1, S1, true);
+  __syncthreads();
+  if (wave < 4) head16_mma<32>(a1, S1, w2, b2, 64, wave, a2, S2, true);
+  __syncthreads();
+  if (wave < nblk3) head16_mma<16>(a2, S2, w3a, b3a, OUT, wave, a3, OUTP, false);
+  if (wave + 8 < nblk3) head16_mma<16>(a2, S2, w3b, b3b, OUT, wave + 8, a3, OUTP, false);
+  __syncthreads();
+  head_store<16, WGH16>(net, B, g0, a3, OUTP, out);
+}
+
 }  // namespace mdq_gcn
 
 extern "C" int mdq_gcn_forward(const mdq_gcn_net* net, int32_t B, int32_t NMAX, int32_t EMAX, const float* x,
@@ -1017,9 +1104,23 @@ static int gcn_forward_impl(const mdq_gcn_net* net, int32_t B, int32_t NMAX, int
                      edge_ptr, edge_cnt, emb, perm, status);
   e = hipGetLastError();
   if (e != hipSuccess) return mdq_set_error(hipGetErrorString(e));
+  const bool c128 = C == 128 && net->out_dim <= 256;   // the reference's width: all weights of a wave loaded up front
+  // (MDQ_HEAD_TILES=32: the 32-graph tiles of mlp_head_c128_kernel - A / B switch and the reference of the 16-graph kernel's
+  //  test, read at every call)
+  const char* tiles = c128 ? std::getenv("MDQ_HEAD_TILES") : nullptr;
+  if (c128 && !(tiles && std::atoi(tiles) == 32)) {
+    // (a constant, and at most 16 x 724 floats = 46 KB: the attribute is set once per process)
+    static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_c128_t16_kernel),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    if (attr_err != hipSuccess) return mdq_set_error(hipGetErrorString(attr_err));
+    const size_t lds16 = sizeof(float) * 16 * ((size_t)260 + 132 + 68 + 16 * ((net->out_dim + 15) / 16));
+    hipLaunchKernelGGL(mlp_head_c128_t16_kernel, dim3((B + 15) / 16), dim3(WGH16), lds16, st, *net, B, emb, out);
+    e = hipGetLastError();
+    if (e != hipSuccess) return mdq_set_error(hipGetErrorString(e));
+    return 0;
+  }
   const int OUTP = (net->out_dim + 31) & ~31;
   size_t lds2 = sizeof(float) * 32 * ((size_t)2 * C + 1 + 129 + 65 + OUTP);
-  const bool c128 = C == 128 && net->out_dim <= 256;   // the reference's width: all weights of a wave loaded up front
   e = hipFuncSetAttribute(c128 ? reinterpret_cast<const void*>(&mlp_head_c128_kernel) : reinterpret_cast<const void*>(&mlp_head_kernel),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
   if (e != hipSuccess) return mdq_set_error(hipGetErrorString(e));

@@ -4654,7 +4654,7 @@ __device__ __forceinline__ void outflow_entries_add(const EnvView& v, const BoEn
 // loop then runs without spill reloads; state is handed over through global memory as before) ----
 template <int TW, int TROWS, int TPAIR>
 __global__ __launch_bounds__(TW) void at_velocity_kernel(mdq_ipcs_desc d, int32_t* iters, const double* inflow_scale, int nsteps,
-                                                         int step) {
+                                                         int step, int fresh) {
   extern __shared__ __align__(16) double smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const EnvView v = env_view(d, b);
@@ -4683,7 +4683,9 @@ __global__ __launch_bounds__(TW) void at_velocity_kernel(mdq_ipcs_desc d, int32_
   double2* hist3 = xs + 4 * (int64_t)d.N2;                            // and one more (slot 3 holds the counter)
   double2* hist4 = xs + 5 * (int64_t)d.N2;
   double* histc = reinterpret_cast<double*>(xs + 3 * (int64_t)d.N2);  // [0]: tentative velocities stored so far
-  const int nhist = (int)histc[0];
+  // `fresh` (all three kernels, step 0 of mdq_ipcs_evolve_fresh): a new mesh - the stored history counts as empty and the
+  // iteration words are assigned, what a reset_history_kernel launch in front of this one would have left
+  const int nhist = (fresh && step == 0) ? 0 : (int)histc[0];
 #ifdef MDQ_AT_TRACE
   long long tq_ = __builtin_amdgcn_s_memtime();
 #endif
@@ -4991,16 +4993,19 @@ __global__ __launch_bounds__(TW) void at_velocity_kernel(mdq_ipcs_desc d, int32_
   }
   if (tid == 0) {
     histc[0] = (double)(nhist < 5 ? nhist + 1 : 5);
-    if (iters) iters[3 * b + 0] += it_u;
+    if (iters) iters[3 * b + 0] = ((fresh && step == 0) ? 0 : iters[3 * b + 0]) + it_u;
   }
 }
 
 // NTH = 1024 for the direct solver (its dense phases are latency-bound streams of 0.8 MB of factors: twice the loads
 // in flight per CU); the CG variant keeps the 512-thread shape its reductions are written for.
 template <bool K1_LDS, int NTH = WG>
-__global__ __launch_bounds__(NTH) void at_pressure_kernel(mdq_ipcs_desc d, int32_t* iters) {
+__global__ __launch_bounds__(NTH) void at_pressure_kernel(mdq_ipcs_desc d, int32_t* iters, int fresh) {
   extern __shared__ __align__(16) double smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
+  // (`fresh`: the first step of mdq_ipcs_evolve_fresh - the iteration word starts from zero; cleared HERE by the thread that
+  //  adds to it at the end, so that the flag is not live across the solve: this kernel sits at its register cap)
+  if (fresh && tid == 0 && iters) iters[3 * b + 1] = 0;
   const EnvView v = env_view(d, b);
   const int n2 = v.n2, nv = v.nv;
   const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
@@ -5105,11 +5110,13 @@ __global__ __launch_bounds__(NTH) void at_pressure_kernel(mdq_ipcs_desc d, int32
 
 #if MDQ_IN_PART(0)
 static __global__ __launch_bounds__(WG) void at_correction_kernel(mdq_ipcs_desc d, int nsteps, int step, double* drag,
-                                                            double* lift, int32_t* iters, const double* inflow_scale) {
+                                                            double* lift, int32_t* iters, const double* inflow_scale,
+                                                            int fresh) {
   extern __shared__ __align__(16) double smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const EnvView v = env_view(d, b);
   const double ai = inflow_factor(inflow_scale, b, nsteps, step);
+  const bool fresh0 = fresh && step == 0;
   const int n2 = v.n2, nv = v.nv;
   const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
   const double a = v.rho / v.dt, mu = v.mu;
@@ -5130,7 +5137,7 @@ static __global__ __launch_bounds__(WG) void at_correction_kernel(mdq_ipcs_desc 
   // ring of the last three corrections u_{n+1} - u* (in the slab region the assembled modes use for their history)
   double2* cring = reinterpret_cast<double2*>(w + work_hist_offset(d.NV, d.NT, d.NE));
   double* ccnt = reinterpret_cast<double*>(cring + 3 * (int64_t)d.N2);  // [0]: corrections stored, [1]: ring position
-  const int nc = (int)ccnt[0], rp = (int)ccnt[1];
+  const int nc = fresh0 ? 0 : (int)ccnt[0], rp = fresh0 ? 0 : (int)ccnt[1];
 #ifdef MDQ_AT_TRACE
   long long tq_ = __builtin_amdgcn_s_memtime();
 #endif
@@ -5182,8 +5189,8 @@ static __global__ __launch_bounds__(WG) void at_correction_kernel(mdq_ipcs_desc 
     // lifting vector (delta0 vanishes on the Dirichlet rows).  What it cannot give is |b| of the stopping test
     // rtol |b|, which needs f3 itself: the value of the last exact start is used (it changes by < 1e-3 per step);
     // every 16th step, and while the ring fills, the exact two-loop start runs and refreshes it.
-    const double bb_lag = ccnt[2];
-    const int cstep = (int)ccnt[3];
+    const double bb_lag = fresh0 ? 0.0 : ccnt[2];
+    const int cstep = fresh0 ? 0 : (int)ccnt[3];
     const bool fused = nc >= 3 && bb_lag > 0.0 && (cstep & 15) != 0;
     {
       // operator input (u*, or -delta0) and p_new - p_n staged in LDS: the element loop gathers from LDS, not L2
@@ -5392,6 +5399,10 @@ static __global__ __launch_bounds__(WG) void at_correction_kernel(mdq_ipcs_desc 
       ccnt[0] = (double)(nc < 3 ? nc + 1 : 3);
       ccnt[1] = (double)((rp + 1) % 3);
       ccnt[3] = (double)((cstep + 1) & 1023);
+      if (fresh0) {   // the history counters of the other operator modes, as reset_history_kernel leaves them
+        double* hcnt = reinterpret_cast<double*>(cring + 5 * (int64_t)d.N2);
+        hcnt[0] = hcnt[1] = 0.0;
+      }
     }
     for (int i = tid; i < nv; i += WG) v.p_n[i] = pnew[i];
     __syncthreads();
@@ -5404,7 +5415,7 @@ static __global__ __launch_bounds__(WG) void at_correction_kernel(mdq_ipcs_desc 
       lift[(int64_t)b * nsteps + step] = li;
     }
   }
-  if (tid == 0 && iters) iters[3 * b + 2] += it_m;
+  if (tid == 0 && iters) iters[3 * b + 2] = (fresh0 ? 0 : iters[3 * b + 2]) + it_m;
 }
 #endif
 
@@ -5616,7 +5627,7 @@ int mdq_ipcs_setup_matfree(const mdq_ipcs_desc* d, void* stream) {
 }
 
 static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                            const double* inflow_scale, void* stream, double* kernel_ms);
+                            const double* inflow_scale, void* stream, double* kernel_ms, int fresh = 0);
 
 int mdq_ipcs_evolve(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
                     void* stream) {
@@ -5628,6 +5639,11 @@ int mdq_ipcs_evolve_inflow(const mdq_ipcs_desc* d, int32_t nsteps, double* drag,
   return ipcs_evolve_impl(d, nsteps, drag, lift, iters, inflow_scale, stream, nullptr);
 }
 
+int mdq_ipcs_evolve_fresh(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
+                          const double* inflow_scale, void* stream) {
+  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, inflow_scale, stream, nullptr, 1);
+}
+
 int mdq_ipcs_evolve_timed(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
                           void* stream, double* kernel_ms) {
   if (!kernel_ms) return fail_msg("kernel_ms is required");
@@ -5636,7 +5652,7 @@ int mdq_ipcs_evolve_timed(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, 
 }
 
 static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                            const double* inflow_scale, void* stream, double* kernel_ms) {
+                            const double* inflow_scale, void* stream, double* kernel_ms, int fresh) {
   if (int rc = check_desc(d)) return rc;
   if (nsteps <= 0) return fail_msg("nsteps must be positive");
   if (!drag || !lift) return fail_msg("drag/lift output pointers are required");
@@ -5677,6 +5693,11 @@ static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
     }
   }
   if (kernel_ms && mode != 3) return fail_msg("per-kernel timing exists for the three-kernel mode 3 only");
+  // a fresh history: mode 3 drops it inside the kernels of its first step; the one-kernel modes take the reset launch
+  if (fresh && mode != 3) {
+    hipLaunchKernelGGL(reset_history_kernel, dim3((d->B + 63) / 64), dim3(64), 0, (hipStream_t)stream, *d, iters);
+    if (hipError_t e_ = hipGetLastError(); e_ != hipSuccess) return fail("reset_history_kernel launch", e_);
+  }
   if (mode == 3 && (red_bytes + P.vel3_bytes > LDS_MAX || d->N2 > MF_ROWS * WG))
     return fail_msg("mode 3 needs N2 <= 3584 and three velocity vectors in LDS");
   if (mode == 2 && (red_bytes + P.vel2_bytes > LDS_MAX || d->N2 > MF_ROWS * WG))
@@ -5735,18 +5756,18 @@ static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
     for (int step = 0; step < nsteps; ++step) {
       if (kernel_ms) hipEventRecord(ev[0], st);
       if (vel_wg == 768)
-        hipLaunchKernelGGL((at_velocity_kernel<768, 5, 1>), dim3(d->B), dim3(768), lds_v, st, *d, iters, inflow_scale, nsteps, step);
+        hipLaunchKernelGGL((at_velocity_kernel<768, 5, 1>), dim3(d->B), dim3(768), lds_v, st, *d, iters, inflow_scale, nsteps, step, fresh);
       else
-        hipLaunchKernelGGL((at_velocity_kernel<WG, MF_ROWS, AT_PAIR>), dim3(d->B), dim3(WG), lds_v, st, *d, iters, inflow_scale, nsteps, step);
+        hipLaunchKernelGGL((at_velocity_kernel<WG, MF_ROWS, AT_PAIR>), dim3(d->B), dim3(WG), lds_v, st, *d, iters, inflow_scale, nsteps, step, fresh);
       if (kernel_ms) hipEventRecord(ev[1], st);
       if (d->pd_enabled)
-        hipLaunchKernelGGL((at_pressure_kernel<false, 1024>), dim3(d->B), dim3(1024), lds_p, st, *d, iters);
+        hipLaunchKernelGGL((at_pressure_kernel<false, 1024>), dim3(d->B), dim3(1024), lds_p, st, *d, iters, fresh && step == 0);
       else if (k1_lds)
-        hipLaunchKernelGGL(at_pressure_kernel<true>, dim3(d->B), dim3(WG), lds_p, st, *d, iters);
+        hipLaunchKernelGGL(at_pressure_kernel<true>, dim3(d->B), dim3(WG), lds_p, st, *d, iters, fresh && step == 0);
       else
-        hipLaunchKernelGGL(at_pressure_kernel<false>, dim3(d->B), dim3(WG), lds_p, st, *d, iters);
+        hipLaunchKernelGGL(at_pressure_kernel<false>, dim3(d->B), dim3(WG), lds_p, st, *d, iters, fresh && step == 0);
       if (kernel_ms) hipEventRecord(ev[2], st);
-      hipLaunchKernelGGL(at_correction_kernel, dim3(d->B), dim3(WG), lds_c, st, *d, nsteps, step, drag, lift, iters, inflow_scale);
+      hipLaunchKernelGGL(at_correction_kernel, dim3(d->B), dim3(WG), lds_c, st, *d, nsteps, step, drag, lift, iters, inflow_scale, fresh);
       if (kernel_ms) {
         hipEventRecord(ev[3], st);
         if ((e = hipEventSynchronize(ev[3])) != hipSuccess) return fail("hipEventSynchronize", e);

@@ -124,12 +124,6 @@ class FlowLeg:
         self._in.append({k: torch.zeros_like(a) for k, a in self._in[0].items()})
 
     # ------------------------------------------------------------------ one leg
-    def _reset(self):
-        # no initial-guess history on a new mesh: the counters inside the workspace (not a fill of its 100 MB) + the
-        # iteration counters, one small launch
-        _lib.check(self.lib.mdq_ipcs_reset_history(C.byref(self.desc), self.iters.data_ptr(), _lib.stream_ptr()),
-                   "mdq_ipcs_reset_history")
-
     def _launch(self, keep, out, before_evolve=None):
         """Operator set-up on the meshes the descriptor points at, then the IPCS steps; `out` = (drag, lift) tensors the
         kernels write (page-locked host tensors are written over the bus directly)."""
@@ -142,13 +136,12 @@ class FlowLeg:
                        "mdq_ipcs_factorize_pressure")
         if before_evolve is not None:       # (the set-up above reads the mesh only; the warm start is needed from here on)
             before_evolve()
-        if self.inflow_scale is None:
-            _lib.check(self.lib.mdq_ipcs_evolve(C.byref(d), self.steps, out[0].data_ptr(), out[1].data_ptr(),
-                                                self.iters.data_ptr(), _lib.stream_ptr()), "mdq_ipcs_evolve")
-        else:
-            _lib.check(self.lib.mdq_ipcs_evolve_inflow(C.byref(d), self.steps, out[0].data_ptr(), out[1].data_ptr(),
-                                                       self.iters.data_ptr(), self.inflow_scale.data_ptr(), _lib.stream_ptr()),
-                       "mdq_ipcs_evolve_inflow")
+        # a new mesh: no initial-guess history, iteration counters from zero - mode 3 takes both inside the kernels of its
+        # first step (no reset launch on the flow chain), the other modes launch the reset kernel themselves
+        _lib.check(self.lib.mdq_ipcs_evolve_fresh(C.byref(d), self.steps, out[0].data_ptr(), out[1].data_ptr(),
+                                                  self.iters.data_ptr(),
+                                                  None if self.inflow_scale is None else self.inflow_scale.data_ptr(),
+                                                  _lib.stream_ptr()), "mdq_ipcs_evolve_fresh")
         self._keep = keep
         return out
 
@@ -163,7 +156,6 @@ class FlowLeg:
             setattr(d, kk, keep[kk].data_ptr())
         t["u_n"].copy_(u0)
         t["p_n"].copy_(p0)
-        self._reset()
         drag = torch.empty((self.B, self.steps), dtype=torch.float64, device=self.device)
         return self._launch(keep, (drag, torch.empty_like(drag)))
 
@@ -236,7 +228,6 @@ class FlowLeg:
         t["u_n"], t["p_n"] = fin["u_n"], fin["p_n"]
         res = self._res[self._n % 2]
         with torch.cuda.stream(self.stream):
-            self._reset()                        # (behind leg k - 1, in FRONT of the wait for this step's meshes)
             self.stream.wait_event(self._mesh_ready if mesh_early else self._ready)
             if self.events is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -23,14 +23,6 @@ def run(k):
     ex = np.array([rng.random(B) < 0.5 for _ in range(k)]); ra = np.array([rng.integers(0, 181, B) for _ in range(k)])
     return venv.rollout_device(fused, k, ex, ra)
 run(30)
-resets = []
-_orig_reset = venv.flow._reset
-def _reset():
-    ea = torch.cuda.Event(enable_timing=True); ea.record()
-    _orig_reset()
-    eb = torch.cuda.Event(enable_timing=True); eb.record()
-    resets.append((ea, eb))
-venv.flow._reset = _reset
 venv.flow.events = []
 torch.cuda.synchronize(); t0 = time.perf_counter()
 run(50)
@@ -38,12 +30,10 @@ torch.cuda.synchronize(); dt = time.perf_counter() - t0
 legs = np.array([a.elapsed_time(b) for a, b in venv.flow.events]) * 1e3
 ev = venv.flow.events
 venv.flow.events = None
-n = min(len(ev), len(resets))
-wait = np.array([resets[k][1].elapsed_time(ev[k][0]) for k in range(5, n)]) * 1e3        # after the reset .. leg start = wait for the meshes
-rst = np.array([resets[k][0].elapsed_time(resets[k][1]) for k in range(5, n)]) * 1e3
-idle = np.array([ev[k - 1][1].elapsed_time(resets[k][0]) for k in range(6, n)]) * 1e3      # end of leg k - 1 .. first launch of step k
+n = len(ev)
+idle = np.array([ev[k - 1][1].elapsed_time(ev[k][0]) for k in range(6, n)]) * 1e3      # end of leg k - 1 .. first launch of leg k
 per = np.array([ev[k - 1][0].elapsed_time(ev[k][0]) for k in range(6, n)]) * 1e3
-print(f"flow stream per step (us, medians): period {np.median(per):.1f} = leg {np.median(legs):.1f} + end-of-leg .. reset launch {np.median(idle):.1f} "
-      f"+ reset {np.median(rst):.1f} + wait for the meshes of the step {np.median(wait):.1f}")
+print(f"flow stream per step (us, medians): period {np.median(per):.1f} = leg {np.median(legs):.1f} + end of leg .. start of the next "
+      f"(wait for the meshes of the step) {np.median(idle):.1f}")
 print(f"B={B}: step {dt / 50 * 1e6:.1f} us; flow leg (topology .. correction, events on the flow stream) median {np.median(legs):.1f} us "
-      f"(min {legs.min():.1f}, max {legs.max():.1f}); the rest of the flow stream's period: history reset + waits + event records")
+      f"(min {legs.min():.1f}, max {legs.max():.1f}); the rest of the flow stream's period: waits + event records")
