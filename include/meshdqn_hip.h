@@ -302,6 +302,38 @@ MDQ_API int mdq_ipcs_evolve_fresh(const mdq_ipcs_desc* d, int32_t nsteps, double
                     int32_t* iters, const double* inflow_scale, void* stream);
 
 /*
+ * A NON-SEPARABLE inflow profile u_x(inlet, t) = profile(x, y, t) for the steps of one call (appended within ABI 8): the
+ * caller evaluates the profile on the host at every environment's inlet dofs for each step and uploads the table once.
+ * All arrays are device arrays; the rows lists come from the cells (meshdqn_amd/inflow.py: inlet_tables, profile_values).
+ */
+typedef struct mdq_inflow_profile {
+  int32_t NIN, NIR;            /* capacities: inlet dofs / inlet-adjacent rows per environment */
+  const int32_t* n_inlet;      /* [B] */
+  const int32_t* inlet_dofs;   /* [B][NIN]  scalar P2 dofs, padded with -1 */
+  const int32_t* n_rows;       /* [B] */
+  const int32_t* rows;         /* [B][NIR]  non-Dirichlet P2 rows that share a cell with an inlet dof */
+  const double*  values;       /* [B][nsteps][NIN]  x-velocity at inlet_dofs for each step of this call */
+} mdq_inflow_profile;
+
+/*
+ * mdq_ipcs_evolve under a per-environment inflow profile that need not be separable (the reference's `inflow_profile`
+ * evaluated per step, flow_solver.py:366-371, for ANY profile of (x, y, t)).
+ *   prof : the tables above.  NULL: exactly mdq_ipcs_evolve.
+ * The symmetric elimination is linear in the Dirichlet vector and only the inlet carries non-zero values, so the inflow of
+ * a step changes bcu_gx at the inlet dofs and lift1 = A1[:, bc] g, lift3 = M[:, bc] g on the rows that share a cell with
+ * an inlet dof - nothing else.  In front of the kernels of step s one small kernel (inflow_lift_kernel, one workgroup per
+ * environment) scatters values[b][s] into bcu_gx and recomputes lift1 / lift3 on `rows` from geom, cell_dofs and the flags
+ * (which set-up or assembly wrote before); idiag1, sdiagM, geom and every other row stay as they are.  No row of `rows`
+ * may be an outflow row (the outflow correction of the lifts is not re-applied; the channel meshes have none).
+ * Operator modes 2 and 3 (one launch sequence per step); the modes that loop over the steps inside one kernel (0, 1, 4, 5,
+ * 7) return an error before anything is launched.  AFTER the call bcu_gx, lift1 and lift3 of the descriptor hold the LAST
+ * step's inflow (what mdq_ipcs_setup_matfree leaves behind for that bcu_gx): a following mdq_ipcs_evolve steps under it.
+ * The entry point cannot read a device table: shapes, dof / row ranges and finiteness are the CALLER's job.
+ */
+MDQ_API int mdq_ipcs_evolve_profile(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift,
+                    int32_t* iters, const mdq_inflow_profile* prof, void* stream);
+
+/*
  * Same as mdq_ipcs_evolve (`FlowSolver.evolve`, flow_solver.py:362-396) for the three-kernel mode 3, with HIP events recorded on `stream` around every
  * kernel launch; the accumulated durations (milliseconds over all nsteps) of the velocity / pressure /
  * correction kernels are returned in host array kernel_ms[3].  Synchronises the stream (measurement aid).

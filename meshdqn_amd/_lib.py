@@ -56,6 +56,13 @@ class IpcsDesc(C.Structure):
     ]
 
 
+class InflowProfile(C.Structure):
+    """Mirror of `mdq_inflow_profile` (appended within ABI 8)."""
+    _fields_ = [("NIN", C.c_int32), ("NIR", C.c_int32),
+                ("n_inlet", C.c_void_p), ("inlet_dofs", C.c_void_p), ("n_rows", C.c_void_p), ("rows", C.c_void_p),
+                ("values", C.c_void_p)]
+
+
 class InterpDesc(C.Structure):
     """Mirror of `mdq_interp_desc`."""
     _fields_ = [
@@ -156,6 +163,8 @@ SYMBOLS = {
                                          C.c_void_p]),
     "mdq_ipcs_evolve_fresh": (C.c_int, [C.POINTER(IpcsDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "mdq_ipcs_evolve_profile": (C.c_int, [C.POINTER(IpcsDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(InflowProfile), C.c_void_p]),
     "mdq_ipcs_evolve_timed": (C.c_int, [C.POINTER(IpcsDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(C.c_double)]),
     "mdq_probe_forces": (C.c_int, [C.POINTER(IpcsDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -4452,9 +4452,14 @@ __global__ __launch_bounds__(WG) void evolve_mf_kernel(mdq_ipcs_desc d, int nste
   }
 }
 
+// the inflow profile of step `step` (mdq_ipcs_evolve_profile) in front of that step's kernels: defined in part 0, which
+// owns inflow_lift_kernel; called from the per-step launch loops of modes 2 and 3
+hipError_t launch_inflow_lift(const mdq_ipcs_desc* d, const mdq_inflow_profile* prof, int nsteps, int step, hipStream_t st);
+
 template <bool K1_LDS>
 static hipError_t launch_evolve_mf(const mdq_ipcs_desc* d, size_t lds, int nsteps, double* drag, double* lift,
-                                   int32_t* iters, const double* inflow_scale, hipStream_t stream) {
+                                   int32_t* iters, const double* inflow_scale, const mdq_inflow_profile* prof,
+                                   hipStream_t stream) {
   static const hipError_t attr = [] {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&evolve_mf_kernel<K1_LDS, 1>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -4473,6 +4478,8 @@ static hipError_t launch_evolve_mf(const mdq_ipcs_desc* d, size_t lds, int nstep
   const size_t lds_p = red_bytes + P.prs_vec_bytes + (K1_LDS ? P.prs_mat_bytes : 0);
   (void)lds;
   for (int step = 0; step < nsteps; ++step) {
+    if (prof)
+      if (hipError_t e = launch_inflow_lift(d, prof, nsteps, step, stream); e != hipSuccess) return e;
     hipLaunchKernelGGL((evolve_mf_kernel<K1_LDS, 1>), dim3(d->B), dim3(WG), lds_v, stream, *d, nsteps, step, drag, lift, iters, inflow_scale);
     hipLaunchKernelGGL((evolve_mf_kernel<K1_LDS, 2>), dim3(d->B), dim3(WG), lds_p, stream, *d, nsteps, step, drag, lift, iters, inflow_scale);
     hipLaunchKernelGGL((evolve_mf_kernel<K1_LDS, 3>), dim3(d->B), dim3(WG), lds_v, stream, *d, nsteps, step, drag, lift, iters, inflow_scale);
@@ -5472,6 +5479,97 @@ static hipError_t upload_tables() {
   return err;
 }
 
+#if MDQ_IN_PART(0)
+// ================================================================== inflow profile (mdq_ipcs_evolve_profile)
+//
+// The inflow of ONE step of a launch sequence: values[b][step] scattered into bcu_gx at the inlet dofs, then lift1 / lift3
+// recomputed on the rows that share a cell with an inlet dof - the three things of the set-up that depend on the Dirichlet
+// vector (the elimination is linear in it and only the inlet is non-zero).  The per-row sums are the "P2 rows" loop of
+// setup_matfree_kernel restated (not shared: that kernel's resource row stays what it is): slots through g2_ptr / g2_src,
+// the cell's geom and cell_dofs, every flagged column j adds bx gx, bz gx, m gx.  A row list is a few dozen rows of ~6 cells, each
+// cell a chain of four dependent loads, so a row is spread over 8 lanes (one slot each) and summed by a fixed shuffle tree:
+// one pass of the workgroup for up to 64 rows, the order fixed, no atomics.  Outflow rows are not in the list (the host
+// refuses such a mesh): their - mu/2 B correction is not re-applied.  Writes bcu_gx[inlet], lift1[rows], lift3[rows] only.
+constexpr int IWG = 512;   // 64 rows x 8 lanes per pass
+static __global__ __launch_bounds__(IWG) void inflow_lift_kernel(mdq_ipcs_desc d, mdq_inflow_profile pr, int nsteps, int step) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const EnvView v = env_view(d, b);
+  const double a = v.rho / v.dt, mu = v.mu;
+  __shared__ double sMhat[6][6];
+  __shared__ double sGhat[2][2][6][6];
+  for (int q = tid; q < 36; q += IWG) sMhat[q / 6][q % 6] = c_tab.Mhat[q / 6][q % 6];
+  for (int q = tid; q < 144; q += IWG) sGhat[q / 72][(q / 36) % 2][(q / 6) % 6][q % 6] = c_tab.Ghat[q / 72][(q / 36) % 2][(q / 6) % 6][q % 6];
+  const int nin = min(pr.n_inlet[b], pr.NIN), nr = min(pr.n_rows[b], pr.NIR);
+  const int32_t* dofs = pr.inlet_dofs + (int64_t)b * pr.NIN;
+  const double* val = pr.values + ((int64_t)b * nsteps + step) * pr.NIN;
+  // (an input of every other entry point, hence const in the descriptor; this one is documented to rewrite its inlet entries)
+  double* gxw = const_cast<double*>(d.bcu_gx) + (int64_t)b * d.N2;
+  for (int k = tid; k < nin; k += IWG) {
+    const int i = dofs[k];
+    if (i >= 0 && i < v.n2) gxw[i] = val[k];
+  }
+  __syncthreads();   // (the new Dirichlet values and the tables are visible to the workgroup)
+  const int32_t* rows = pr.rows + (int64_t)b * pr.NIR;
+  const int sub = tid & 7;
+  for (int base = 0; base < nr; base += IWG / 8) {   // (uniform trip count: every lane takes part in the shuffles)
+    const int q = base + (tid >> 3);
+    const int r = q < nr ? rows[q] : -1;
+    const bool ok = r >= 0 && r < v.n2;
+    double l1x = 0.0, l1y = 0.0, l3x = 0.0;
+    if (ok) {
+      const int s1 = v.g2_ptr[r + 1];
+      for (int s = v.g2_ptr[r] + sub; s < s1; s += 8) {
+        const int slot = v.g2_src[s];
+        const int e = slot / 6, i = slot - e * 6;
+        const Geo g = load_geo(v, e);
+        int cj[6];
+        bool fj[6];
+        double gj[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) cj[j] = v.cell_dofs[j * v.NT + e];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) fj[j] = v.bcu_flag[cj[j]] != 0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) gj[j] = fj[j] ? gxw[cj[j]] : 0.0;
+        const double Ja[2][2] = {{g.j00, g.j01}, {g.j10, g.j11}};
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          if (!fj[j]) continue;
+          const double m = g.det * sMhat[i][j];
+          const double g00 = sGhat[0][0][i][j], g01 = sGhat[0][1][i][j];
+          const double g10 = sGhat[1][0][i][j], g11 = sGhat[1][1][i][j];
+          const double kxx = g.det * (Ja[0][0] * (Ja[0][0] * g00 + Ja[1][0] * g01) + Ja[1][0] * (Ja[0][0] * g10 + Ja[1][0] * g11));
+          const double kxy = g.det * (Ja[0][0] * (Ja[0][1] * g00 + Ja[1][1] * g01) + Ja[1][0] * (Ja[0][1] * g10 + Ja[1][1] * g11));
+          const double kyy = g.det * (Ja[0][1] * (Ja[0][1] * g00 + Ja[1][1] * g01) + Ja[1][1] * (Ja[0][1] * g10 + Ja[1][1] * g11));
+          const double L = kxx + kyy;
+          const double bx = a * m + 0.5 * mu * (L + kxx), bz = 0.5 * mu * kxy;
+          l1x += bx * gj[j];
+          l1y += bz * gj[j];
+          l3x += m * gj[j];
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) {
+      l1x += __shfl_down(l1x, o, 8);
+      l1y += __shfl_down(l1y, o, 8);
+      l3x += __shfl_down(l3x, o, 8);
+    }
+    if (ok && sub == 0) {
+      v.lift1[r] = make_double2(l1x, l1y);
+      v.lift3[r] = make_double2(l3x, 0.0);
+    }
+  }
+}
+#endif  // part 0
+
+#if MDQ_IN_PART(0)
+hipError_t launch_inflow_lift(const mdq_ipcs_desc* d, const mdq_inflow_profile* prof, int nsteps, int step, hipStream_t st) {
+  hipLaunchKernelGGL(inflow_lift_kernel, dim3(d->B), dim3(IWG), 0, st, *d, *prof, nsteps, step);
+  return hipGetLastError();
+}
+#endif
+
 // launchers of the operator modes whose kernels live in the other parts of this file (each uploads its own tables)
 struct EvolveArgs {
   const mdq_ipcs_desc* d;
@@ -5481,6 +5579,7 @@ struct EvolveArgs {
   int32_t* iters;
   const double* inflow_scale;   // [B][nsteps] inflow factors, or null (mdq_ipcs_evolve_inflow)
   hipStream_t st;
+  const mdq_inflow_profile* prof;   // inflow profile of the per-step mode 2, or null (mdq_ipcs_evolve_profile)
 };
 hipError_t part_launch_assembled(int mode, bool k1_lds, bool pg, const EvolveArgs& a);   // modes 0 / 1 (part 1)
 hipError_t part_launch_tiles(int mode, bool k1_lds, bool pg, const EvolveArgs& a);       // modes 5 / 4 (part 2)
@@ -5514,8 +5613,8 @@ hipError_t part_launch_tiles(int mode, bool k1_lds, bool pg, const EvolveArgs& a
 #if MDQ_IN_PART(3)
 hipError_t part_launch_mf(bool k1_lds, const EvolveArgs& a) {
   if (hipError_t e = upload_tables(); e != hipSuccess) return e;
-  return k1_lds ? launch_evolve_mf<true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st)
-                : launch_evolve_mf<false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.st);
+  return k1_lds ? launch_evolve_mf<true>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.prof, a.st)
+                : launch_evolve_mf<false>(a.d, a.lds, a.nsteps, a.drag, a.lift, a.iters, a.inflow_scale, a.prof, a.st);
 }
 #endif
 
@@ -5627,7 +5726,19 @@ int mdq_ipcs_setup_matfree(const mdq_ipcs_desc* d, void* stream) {
 }
 
 static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                            const double* inflow_scale, void* stream, double* kernel_ms, int fresh = 0);
+                            const double* inflow_scale, void* stream, double* kernel_ms, int fresh = 0,
+                            const mdq_inflow_profile* prof = nullptr);
+
+int mdq_ipcs_evolve_profile(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
+                            const mdq_inflow_profile* prof, void* stream) {
+  if (!prof) return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, nullptr);
+  if (prof->NIN <= 0 || prof->NIR <= 0) return fail_msg("mdq_ipcs_evolve_profile: NIN and NIR must be positive");
+  if (!prof->n_inlet || !prof->inlet_dofs || !prof->n_rows || !prof->rows || !prof->values)
+    return fail_msg("mdq_ipcs_evolve_profile: incomplete inflow profile (n_inlet, inlet_dofs, n_rows, rows, values)");
+  if (d && (!d->cell_dofs || !d->g2_ptr || !d->g2_src || !d->bcu_flag || !d->bcu_gx || !d->geom || !d->lift1 || !d->lift3))
+    return fail_msg("mdq_ipcs_evolve_profile: incomplete descriptor (cell_dofs, g2_ptr, g2_src, bcu_flag, bcu_gx, geom, lift1, lift3)");
+  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, nullptr, 0, prof);
+}
 
 int mdq_ipcs_evolve(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
                     void* stream) {
@@ -5652,7 +5763,8 @@ int mdq_ipcs_evolve_timed(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, 
 }
 
 static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                            const double* inflow_scale, void* stream, double* kernel_ms, int fresh) {
+                            const double* inflow_scale, void* stream, double* kernel_ms, int fresh,
+                            const mdq_inflow_profile* prof) {
   if (int rc = check_desc(d)) return rc;
   if (nsteps <= 0) return fail_msg("nsteps must be positive");
   if (!drag || !lift) return fail_msg("drag/lift output pointers are required");
@@ -5693,6 +5805,12 @@ static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
     }
   }
   if (kernel_ms && mode != 3) return fail_msg("per-kernel timing exists for the three-kernel mode 3 only");
+  // an inflow profile is rewritten BETWEEN the steps of a launch sequence: the modes that loop over the steps inside one kernel
+  // have no such place
+  if (prof && mode != 2 && mode != 3)
+    return fail_msg("mdq_ipcs_evolve_profile: operator mode " + std::to_string(mode) + " runs the steps of a call inside one kernel; "
+                    "an inflow profile is served by the per-step path (operator modes 2 and 3, or mdq_ipcs_setup_matfree + "
+                    "mdq_ipcs_evolve one step at a time)");
   // a fresh history: mode 3 drops it inside the kernels of its first step; the one-kernel modes take the reset launch
   if (fresh && mode != 3) {
     hipLaunchKernelGGL(reset_history_kernel, dim3((d->B + 63) / 64), dim3(64), 0, (hipStream_t)stream, *d, iters);
@@ -5754,6 +5872,8 @@ static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
       kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0.0;
     }
     for (int step = 0; step < nsteps; ++step) {
+      if (prof)
+        if ((e = launch_inflow_lift(d, prof, nsteps, step, st)) != hipSuccess) return fail("inflow_lift_kernel launch", e);
       if (kernel_ms) hipEventRecord(ev[0], st);
       if (vel_wg == 768)
         hipLaunchKernelGGL((at_velocity_kernel<768, 5, 1>), dim3(d->B), dim3(768), lds_v, st, *d, iters, inflow_scale, nsteps, step, fresh);
@@ -5782,7 +5902,7 @@ static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
       for (int i = 0; i < 4; ++i) hipEventDestroy(ev[i]);
     e = hipGetLastError();
   } else {
-    const EvolveArgs a{d, lds, nsteps, drag, lift, iters, inflow_scale, st};
+    const EvolveArgs a{d, lds, nsteps, drag, lift, iters, inflow_scale, st, prof};
     if (mode == 2)
       e = part_launch_mf(k1_lds, a);
     else if (mode == 4 || mode == 5 || mode == 7)

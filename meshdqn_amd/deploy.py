@@ -51,16 +51,22 @@ def resimulate_batch(env, meshes):
     """`run_sim` for a list of (coords, cells) meshes at once: one `IpcsBatch` (device assembly, device pressure
     factorisation for solver_type 'lu'), `solver_steps` steps from rest, forces every `save_steps` steps.
     Returns (drags (M, S), lifts (M, S)).  Every mesh is re-simulated under the flow solver's inflow schedule
-    (`flow_params['inflow']` as a dict, inflow.py); a CALLABLE inflow profile is not passed on - as before, the batch
-    then re-simulates under the constant parabola (`batched=False` steps such a profile through the flow solver)."""
+    (`flow_params['inflow']` as a dict, inflow.py) or its CALLABLE inflow profile - the latter where the batch's operator
+    mode launches per step (modes 2 / 3, `IpcsBatch.mode_serves_profile`: every mesh within 3 584 velocity dofs); in the other
+    modes a callable is not passed on and the batch re-simulates under the constant parabola, as before (`batched=False`
+    steps such a profile through the flow solver)."""
     from .ipcs_batch import IpcsBatch
     from .topology import MeshTopology
     fs = env.flow_solver
     topos = [MeshTopology(np.asarray(c, np.float64), np.asarray(t)) for c, t in meshes]
+    mode = getattr(fs, "mode", -1)
+    profile = getattr(fs, "inflow_profile", None)
+    if not IpcsBatch.mode_serves_profile(mode, max(t.np2 for t in topos)):
+        profile = None
     batch = IpcsBatch(topos, [t.coords for t in topos], mu=fs.mu, rho=fs.rho, dt=fs.dt_value, rtol=fs.rtol,
-                      device=fs.device, mode=getattr(fs, "mode", -1),
+                      device=fs.device, mode=mode,
                       pressure_direct=("device" if fs.solver_type == "lu" else False),
-                      inflow=getattr(fs, "inflow_spec", None))
+                      inflow=getattr(fs, "inflow_spec", None), inflow_profile=profile)
     batch.assemble()
     drags, lifts, done = [], [], 0
     while done < env.solver_steps:

@@ -101,7 +101,9 @@ class FlowSolver(object):
         # flow_solver.py:70-73: 'constant' = the time independent parabola, anything else = the caller's own profile.  The
         # reference takes a dolfin Expression with a `time` attribute; here: a callable profile(x, y, t) -> x-velocity
         # at the inlet dof coordinates (every boundary condition of the reference has zero y-velocity) - or a schedule dict
-        # (inflow.py: a(t) * the constant parabola, applied inside the evolve kernels: K steps per launch like 'constant')
+        # (inflow.py: a(t) * the constant parabola, applied inside the evolve kernels: K steps per launch like 'constant').
+        # A callable runs K steps per call as well where the operator mode launches per step (modes 2 / 3: the batch gets it
+        # as `inflow_profile`, evaluated for all K steps up front); in the other modes it is stepped one launch at a time
         inflow = flow_params.get("inflow", "constant")
         self.inflow_profile = inflow if callable(inflow) else None
         self.inflow_spec = None if callable(inflow) else inflow_spec(inflow)    # (TypeError / ValueError before any device work)
@@ -145,7 +147,8 @@ class FlowSolver(object):
             self.batch = IpcsBatch([topo], [topo.coords], mu=self.mu, rho=self.rho, dt=self.dt_value,
                                    rtol=self.rtol, device=self.device, mode=self.mode,
                                    pressure_direct=("device" if self.solver_type == "lu" else False),
-                                   inflow=self.inflow_spec)     # (a new batch starts its schedule's clock at 0, as gtime does)
+                                   inflow=self.inflow_spec,     # (a new batch starts its schedule's clock at 0, as gtime does)
+                                   inflow_profile=(self.inflow_profile if IpcsBatch.mode_serves_profile(self.mode, n2) else None))
             self.batch.assemble()
             # solver_type 'lu' = device factorisation of the pressure matrix; a mesh beyond its limits (1024 vertices, 112
             # interior / separator nodes per part) keeps the Jacobi-CG pressure solve (rtol-limited instead of exact): say so
@@ -220,8 +223,18 @@ class FlowSolver(object):
             self.gtime += self.dt_value * nsteps
             d = drag[0].tolist()
             l = lift[0].tolist()
+        elif self.batch.inflow_profile is not None:
+            # time dependent inflow (flow_solver.py:366-371) in the per-step operator modes: the profile evaluated at the
+            # instants this clock takes (accumulated step by step, as the loop below does), one call, one read-back
+            times = []
+            for _ in range(nsteps):
+                self.gtime += self.dt_value
+                times.append(self.gtime)
+            drag, lift = self.batch.evolve(nsteps, inflow_times=np.array(times, np.float64))
+            d = drag[0].tolist()
+            l = lift[0].tolist()
         else:
-            # time dependent inflow (flow_solver.py:366-371): the clock advances, the profile is evaluated at the new
+            # the modes that loop over the steps inside one kernel: the clock advances, the profile is evaluated at the new
             # time, then the step runs with those boundary values - one launch per step
             d, l = [], []
             for _ in range(nsteps):

@@ -12,8 +12,13 @@ time-dependent inflow: nothing is rebuilt, and K steps run per launch as under t
 
 The factors are built HERE, on the host, in numpy: no trigonometry runs on the device, the factors are bit-equal to what
 a numpy reference computes, and - the library cannot read a device table - this is where they are validated.
-A callable `profile(x, y, t)` (`flow_params['inflow']`, any non-separable profile) is not handled here: it keeps the
-per-step path of `FlowSolver.evolve` / `IpcsBatch.update_inflow`.
+
+A callable `profile(x, y, t)` (`flow_params['inflow']`, any NON-SEPARABLE profile of position and time) is the second kind
+(`IpcsBatch(inflow_profile=...)`, `mdq_ipcs_evolve_profile`): it depends on (x, y, t) only, never on the flow state, so all
+K steps of a call are evaluated here, up front, at the inlet dofs (`profile_values`: a few dozen values per environment and
+step, uploaded once), and a small kernel between the steps rewrites what depends on them - bcu_gx at the inlet dofs and the
+lifting vectors on the rows that share a cell with one (`inlet_tables`).  In the operator modes that loop over the steps
+inside one kernel it keeps the per-step path of `FlowSolver.evolve` / `IpcsBatch.update_inflow`.
 """
 from __future__ import annotations
 
@@ -67,7 +72,7 @@ def batch_specs(inflow, B: int):
         specs = [inflow_spec(inflow)] * int(B)
     else:
         if callable(inflow):
-            raise TypeError("a callable inflow profile is not a schedule (FlowSolver steps it through IpcsBatch.update_inflow)")
+            raise TypeError("a callable inflow profile is not a schedule (it goes to IpcsBatch(inflow_profile=...))")
         specs = [inflow_spec(v) for v in inflow]
         if len(specs) != B:
             raise ValueError(f"inflow must be one schedule or a sequence of length {B} (one per environment), got {len(specs)}")
@@ -103,3 +108,119 @@ def inflow_factors(specs, dt, first_step: int, nsteps: int) -> np.ndarray | None
     t = k[None, :] * dtb[:, None]
     A, eps, f, phi = (tab[:, j:j + 1] for j in range(4))
     return np.ascontiguousarray(A * (1.0 + eps * np.sin(2.0 * np.pi * f * t + phi)))
+
+
+# ------------------------------------------------------------------ non-separable profiles: profile(x, y, t)
+def batch_profiles(inflow_profile, B: int):
+    """The B profiles of a batch from one callable (broadcast) or a sequence of B callables / None (None: that environment
+    keeps the constant parabola); None when there is no callable at all."""
+    if inflow_profile is None:
+        return None
+    if callable(inflow_profile):
+        return [inflow_profile] * int(B)
+    if isinstance(inflow_profile, (str, dict)):
+        raise TypeError(f"inflow_profile must be a callable profile(x, y, t) or a sequence of callables / None, got {inflow_profile!r} "
+                        "(a schedule goes to inflow=)")
+    profs = list(inflow_profile)
+    if len(profs) != B:
+        raise ValueError(f"inflow_profile must be one callable or a sequence of length {B} (one per environment), got {len(profs)}")
+    for b, p in enumerate(profs):
+        if p is not None and not callable(p):
+            raise TypeError(f"inflow_profile of environment {b} must be a callable profile(x, y, t) or None, got {p!r}")
+    return None if all(p is None for p in profs) else profs
+
+
+def inlet_tables(topos, coords_list) -> list:
+    """Per environment what an inflow profile touches, as a dict:
+
+        dofs  int32 (n_inlet,)   the inlet dofs (`MeshTopology.boundary_conditions(...)["inlet_dofs"]`: scalar P2 dofs whose
+                                 value is the profile's - the ones the airfoil / wall conditions do not override), ascending
+        xy    float64 (n_inlet, 2)   their coordinates
+        gx0   float64 (n_inlet,)     their set-up values (the constant parabola, `["bcu_gx"]` at `dofs`)
+        rows  int32 (n_rows,)    the non-Dirichlet P2 rows that share a cell with an inlet dof, ascending: the only rows whose
+                                 lifting vectors A1[:, bc] g and M[:, bc] g depend on the inlet values
+
+    Environments that share a topology object and a coordinate array (one airfoil) share one dict."""
+    cache, out = {}, []
+    for t, x in zip(topos, coords_list):
+        key = (id(t), id(x))
+        if key not in cache:
+            bc = t.boundary_conditions(x)
+            dofs = np.asarray(bc["inlet_dofs"], np.int64)
+            is_inlet = np.zeros(t.np2, bool)
+            is_inlet[dofs] = True
+            cd = np.asarray(t.cell_dofs)                                  # (nt, 6)
+            touched = np.unique(cd[is_inlet[cd].any(axis=1)])             # every dof of a cell that holds an inlet dof
+            rows = touched[bc["bcu_flag"][touched] == 0]
+            cache[key] = dict(dofs=dofs.astype(np.int32), xy=np.ascontiguousarray(t.dof_coords(x)[dofs], np.float64),
+                              gx0=np.asarray(bc["bcu_gx"], np.float64)[dofs].copy(), rows=rows.astype(np.int32))
+        out.append(cache[key])
+    return out
+
+
+def padded(tables, key: str) -> tuple:
+    """(counts int32 (B,), int32 (B, cap) padded with -1) of the per-environment lists `key` ('dofs' / 'rows') of
+    `inlet_tables`; the capacity is at least 1."""
+    n = np.array([len(t[key]) for t in tables], np.int32)
+    out = np.full((len(tables), max(int(n.max(initial=0)), 1)), -1, np.int32)
+    for b, t in enumerate(tables):
+        out[b, :n[b]] = t[key]
+    return n, out
+
+
+def step_times(dt, first_step: int, nsteps: int, B: int) -> np.ndarray:
+    """float64 (B, nsteps): t = (first_step + s) * dt_b, s = 1 .. nsteps - the clock of `inflow_factors` (`dt`: a scalar or
+    (B,)).  Every time depends on its own step index only: the times of (0, 8) are those of (0, 3) followed by those of
+    (3, 5), bit for bit."""
+    dtb = np.broadcast_to(np.asarray(dt, np.float64).reshape(-1), (int(B),))
+    k = (int(first_step) + np.arange(1, int(nsteps) + 1)).astype(np.float64)
+    return np.ascontiguousarray(k[None, :] * dtb[:, None])
+
+
+def profile_values(profiles, inlet, times) -> np.ndarray:
+    """The table `values` of `mdq_inflow_profile`: float64 (B, K, NIN), row [b][s] = profile_b(x, y, times[b, s]) at the
+    inlet dofs of environment b (`inlet`: what `inlet_tables` returned), padded with zeros to NIN = the largest inlet.
+    `profiles`: one callable or a sequence of B callables / None; a None profile yields that environment's set-up values
+    (the constant parabola) at every step.  `times`: (K,) for every environment or (B, K).
+
+    A profile is evaluated once per distinct (callable, inlet point set, time) and the row reused: environments of one
+    airfoil share their inlet points.  The library cannot read a device table, so this is where the values are validated:
+    a result that has not the shape (n_inlet,) or is not finite raises ValueError naming the environment and the step."""
+    B = len(inlet)
+    profs = batch_profiles(profiles, B) or [None] * B
+    times = np.asarray(times, np.float64)
+    if times.ndim == 1:
+        times = np.broadcast_to(times, (B, times.shape[0]))
+    if times.ndim != 2 or times.shape[0] != B or times.shape[1] == 0:
+        raise ValueError(f"inflow times must have shape (nsteps,) or ({B}, nsteps), got {times.shape}")
+    if not np.isfinite(times).all():
+        raise ValueError("inflow times must be finite")
+    K = times.shape[1]
+    NIN = max(max(len(t["dofs"]) for t in inlet), 1)
+    out = np.zeros((B, K, NIN), np.float64)
+    done = {}
+    for b, (p, tab) in enumerate(zip(profs, inlet)):
+        n = len(tab["dofs"])
+        if p is None:
+            out[b, :, :n] = tab["gx0"]
+            continue
+        try:
+            hash(p)
+            pk = p
+        except TypeError:
+            pk = id(p)
+        x, y = tab["xy"][:, 0], tab["xy"][:, 1]
+        pts = tab["xy"].tobytes()
+        for s in range(K):
+            t = float(times[b, s])
+            key = (pk, pts, t)
+            if key not in done:
+                v = np.asarray(p(x, y, t), dtype=np.float64)
+                if v.shape != (n,):
+                    raise ValueError(f"inflow profile of environment {b} at step {s} (t = {t!r}) must return shape ({n},) "
+                                     f"(one x-velocity per inlet dof), got {v.shape}")
+                if not np.isfinite(v).all():
+                    raise ValueError(f"inflow profile of environment {b} at step {s} (t = {t!r}) is not finite")
+                done[key] = v
+            out[b, s, :n] = done[key]
+    return out

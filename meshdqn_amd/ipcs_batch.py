@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .inflow import batch_specs, inflow_factors
+from .inflow import batch_profiles, batch_specs, inflow_factors, inlet_tables, padded, profile_values, step_times
 from .topology import conflict_free_cell_order, morton_cell_order, TAG_AIRFOIL, TAG_OUTFLOW, MeshTopology
 
 
@@ -78,13 +78,16 @@ class IpcsBatch:
     """Device-resident batch of Taylor-Hood IPCS problems.  `mu`, `rho` and `dt` are scalars (one flow condition for the
     batch) or sequences of length B (one per environment: `self.env_phys`, see `flow_table`).  `inflow`: None (the constant
     parabola), one inflow schedule (inflow.py: a spec or its dict) or a sequence of B of them - `evolve` then scales every
-    environment's inlet values by its own factor a_b(t), step by step, inside the kernels."""
+    environment's inlet values by its own factor a_b(t), step by step, inside the kernels.  `inflow_profile`: None, one
+    callable profile(x, y, t) -> x-velocity at the inlet dofs (any non-separable profile) or a sequence of B callables / None -
+    `evolve` then evaluates every step of a call on the host up front and a small kernel rewrites the inlet values and the
+    lifting vectors between the steps (operator modes 2 and 3).  A batch has one kind of time-dependent inflow."""
 
     def __init__(self, topos: Sequence[MeshTopology], coords: Sequence[np.ndarray] | None = None,
                  mu=1e-3, rho=1.0, dt=1e-3, rtol: float = 1e-10,
                  maxit=(200, 4000, 200), device: str | torch.device = "cuda", capacities: dict | None = None,
                  mode: int = -1, pressure_direct: bool = True, pressure_parts: int = 16,
-                 cell_order: str = "auto", pcg_degree: int = 0, inflow=None):
+                 cell_order: str = "auto", pcg_degree: int = 0, inflow=None, inflow_profile=None):
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -95,6 +98,10 @@ class IpcsBatch:
             raise ValueError("empty batch")
         table = flow_table(mu, rho, dt, B)      # (validated before any device work)
         self.inflow = batch_specs(inflow, B)    # (likewise) B specs, or None
+        self.inflow_profile = batch_profiles(inflow_profile, B)     # (likewise) B callables / None, or None
+        if self.inflow is not None and self.inflow_profile is not None:
+            raise ValueError("inflow_profile cannot be combined with inflow schedules (inflow=): a batch has one kind of "
+                             "time-dependent inflow")
         if cell_order == "auto":
             # the LDS-resident operator modes (every mesh of the batch within 3 584 velocity dofs): the conflict-free order of the
             # LDS-atomic mode 3; beyond them (element tiles, modes 5 / 7): a spatial order, so that a chunk of 1 024 triangles
@@ -125,6 +132,16 @@ class IpcsBatch:
         self.maxit = tuple(int(m) for m in maxit)
 
         per = [self._host_arrays(t, x) for t, x in zip(self.topos, coords)]
+        self._prof_tab = self._prof_dev = self._prof_desc = None     # inflow profiles: host tables, device tables, mdq_inflow_profile
+        if self.inflow_profile is not None:
+            # the kernel that rewrites the lifts between the steps does not re-apply the outflow correction (- mu/2 B g on the
+            # outflow rows): a mesh whose inlet-adjacent rows meet its outflow rows is refused
+            self._prof_tab = inlet_tables(self.topos, coords)
+            for b, (tab, p) in enumerate(zip(self._prof_tab, per)):
+                both = np.intersect1d(tab["rows"], p["bo_rows"])
+                if both.size:
+                    raise ValueError(f"inflow_profile: environment {b} has {both.size} row(s) that are inlet-adjacent and outflow rows "
+                                     f"(e.g. dof {int(both[0])}): the inflow kernel does not re-apply the outflow correction of the lifts")
         cap = dict(NV=max(p["nv"] for p in per), NT=max(p["nt"] for p in per), NE=max(p["ne"] for p in per),
                    NNZ2=max(p["colidx2"].size for p in per), NNZ1=max(p["colidx1"].size for p in per),
                    NAF=max(max(p["af"].shape[0] for p in per), 1),
@@ -269,6 +286,16 @@ class IpcsBatch:
         self.env_phys_host = table      # (the schedules' clocks run on every environment's own dt)
         self._inflow_keep = None
         self.steps_done = 0
+        if self._prof_tab is not None:
+            n_in, dofs = padded(self._prof_tab, "dofs")
+            n_rw, rows = padded(self._prof_tab, "rows")
+            assert dofs.max() < N2 and rows.max() < N2
+            self._prof_dev = {k: torch.from_numpy(v).to(dev) for k, v in dict(n_inlet=n_in, inlet_dofs=dofs, n_rows=n_rw, rows=rows).items()}
+            pd_ = _lib.InflowProfile()
+            pd_.NIN, pd_.NIR = dofs.shape[1], rows.shape[1]
+            for k, a in self._prof_dev.items():
+                setattr(pd_, k, a.data_ptr())
+            self._prof_desc = pd_
 
         d = _lib.IpcsDesc()
         d.B, d.NV, d.NT, d.NE, d.N2, d.NNZ2, d.NNZ1, d.NAF = B, NV, NT, NE, N2, NNZ2, NNZ1, NAF
@@ -493,9 +520,47 @@ class IpcsBatch:
         with torch.cuda.stream(s):
             return f.pin_memory().to(self.device, non_blocking=True)
 
-    def evolve(self, nsteps: int = 1, stream=None, out=None, inflow_scale=None):
+    PROFILE_MODES = (2, 3)      # operator modes with one launch sequence per step: what mdq_ipcs_evolve_profile serves
+
+    @classmethod
+    def mode_serves_profile(cls, mode: int, n2: int) -> bool:
+        """Whether a batch of operator mode `mode` whose largest mesh has `n2` velocity dofs takes an inflow profile: modes
+        2 / 3, asked for or what the auto modes -1 / -2 choose for meshes within the LDS-resident vectors (N2 <= 3584, the
+        choice of `ipcs_evolve_impl`)."""
+        mode = int(mode)
+        return mode in cls.PROFILE_MODES or ((mode < 0 or mode > 7) and int(n2) <= 3584)
+
+    def serves_profile(self) -> bool:
+        return self.mode_serves_profile(self.desc.mode, self.N2)
+
+    def _profile_table(self, nsteps: int, inflow_times, stream):
+        """The device table `values` [B][nsteps][NIN] of `mdq_inflow_profile` for the next `nsteps` steps: every profile
+        evaluated on the host (inflow.py: `profile_values`, validated there) at `inflow_times` ((nsteps,) or (B, nsteps)) or,
+        by default, at (steps_done + s) * dt_b, s = 1 .. nsteps - the clock of the schedules."""
+        if inflow_times is None:
+            dt = self.env_phys_host[:, 2] if self.env_phys_host is not None else self.dt
+            times = step_times(dt, self.steps_done, nsteps, self.B)
+        else:
+            times = np.asarray(inflow_times.detach().cpu().numpy() if isinstance(inflow_times, torch.Tensor) else inflow_times,
+                               dtype=np.float64)
+            if times.shape not in ((int(nsteps),), (self.B, int(nsteps))):
+                raise ValueError(f"inflow_times must have shape ({int(nsteps)},) or ({self.B}, {int(nsteps)}), got {times.shape}")
+        vals = torch.from_numpy(profile_values(self.inflow_profile, self._prof_tab, times))
+        assert tuple(vals.shape) == (self.B, int(nsteps), self._prof_desc.NIN)
+        # asynchronous upload on the launch stream: page-locked staging, the copy is ordered in front of the kernels
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        with torch.cuda.stream(s):
+            return vals.pin_memory().to(self.device, non_blocking=True)
+
+    def evolve(self, nsteps: int = 1, stream=None, out=None, inflow_scale=None, inflow_times=None):
         """Advance all environments `nsteps` IPCS steps; returns (drag, lift) (B,nsteps) device tensors.  `inflow_scale`:
-        explicit (B, nsteps) inflow factors for these steps (tensor or array) in place of the batch's schedules."""
+        explicit (B, nsteps) inflow factors for these steps (tensor or array) in place of the batch's schedules.
+        `inflow_times` (a batch with `inflow_profile` only): the times, (nsteps,) or (B, nsteps), at which the profiles are
+        evaluated for these steps in place of (steps_done + s) * dt_b."""
+        if self.inflow_profile is not None:
+            return self._evolve_profile(nsteps, stream, out, inflow_scale, inflow_times)
+        if inflow_times is not None:
+            raise ValueError("inflow_times needs a batch with inflow_profile")
         ftab = self._inflow_table(nsteps, inflow_scale, stream)       # (validated before anything is launched)
         if not self.assembled:
             self.assemble(stream)
@@ -516,6 +581,31 @@ class IpcsBatch:
         self.steps_done += nsteps
         return drag, lift
 
+    def _evolve_profile(self, nsteps, stream, out, inflow_scale, inflow_times):
+        """`evolve` of a batch with inflow profiles: one `mdq_ipcs_evolve_profile` call for all `nsteps` steps."""
+        if inflow_scale is not None:
+            raise ValueError("inflow_scale cannot be combined with inflow_profile: a batch has one kind of time-dependent inflow")
+        if int(nsteps) <= 0:
+            raise ValueError("nsteps must be positive")
+        if not self.serves_profile():       # (the entry point refuses as well - before the assembly is launched, here)
+            raise _lib.MeshDQNHipError(f"operator mode {int(self.desc.mode)} runs the steps of a call inside one kernel: an inflow "
+                                       f"profile is served by the per-step path (modes 2 / 3, or update_inflow + evolve(1))")
+        vals = self._profile_table(nsteps, inflow_times, stream)      # (validated before anything is launched)
+        if not self.assembled:
+            self.assemble(stream)
+        if out is None:
+            drag = torch.empty((self.B, nsteps), dtype=torch.float64, device=self.device)
+            lift = torch.empty_like(drag)
+        else:
+            drag, lift = out
+        self._prof_desc.values = vals.data_ptr()
+        rc = self.lib.mdq_ipcs_evolve_profile(C.byref(self.desc), int(nsteps), drag.data_ptr(), lift.data_ptr(),
+                                              self.iters.data_ptr(), C.byref(self._prof_desc), _lib.stream_ptr(stream))
+        _lib.check(rc, "mdq_ipcs_evolve_profile")
+        self._inflow_keep = vals            # (the launch reads it: alive until the next one replaces it)
+        self.steps_done += nsteps
+        return drag, lift
+
     def check(self):
         """Synchronises and raises if any `evolve` since the last call abandoned a step (status words of the descriptor: the
         two-workgroup operator modes 4 / 7 give a step up when a team barrier times out - csrc/mdq_ipcs.hip `team_failed`; the
@@ -529,8 +619,8 @@ class IpcsBatch:
     def evolve_timed(self, nsteps: int = 1, stream=None, out=None):
         """`evolve` with HIP events around every kernel (mode 3): returns (drag, lift, ms) where ms[3] are the
         accumulated durations of the velocity / pressure / correction kernels over the nsteps."""
-        if self.inflow is not None:     # (mdq_ipcs_evolve_timed takes no table: it would step under the constant parabola)
-            raise _lib.MeshDQNHipError("evolve_timed does not apply inflow schedules (measurement aid of the constant inflow)")
+        if self.inflow is not None or self.inflow_profile is not None:     # (mdq_ipcs_evolve_timed takes no table: it would step under the constant parabola)
+            raise _lib.MeshDQNHipError("evolve_timed does not apply inflow schedules or profiles (measurement aid of the constant inflow)")
         if not self.assembled:
             self.assemble(stream)
         if out is None:
