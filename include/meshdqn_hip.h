@@ -334,6 +334,42 @@ MDQ_API int mdq_ipcs_evolve_profile(const mdq_ipcs_desc* d, int32_t nsteps, doub
                     int32_t* iters, const mdq_inflow_profile* prof, void* stream);
 
 /*
+ * The inlet_dofs / rows tables of a mdq_inflow_profile for meshes whose dofs were numbered ON THE DEVICE (the S3 flow leg:
+ * a new mesh and a new numbering every env step; appended within ABI 8).  Boundary vertices are never removed or moved and
+ * the inlet facets lie on the convex hull, so the inlet POINTS of an environment are those of its original mesh for a whole
+ * episode; the caller evaluates its profile at them once, in a canonical order, and this kernel (inlet_map_kernel, one
+ * workgroup per environment) finds which dof of the current mesh is which point.
+ *   NIN, NIR   : capacities of the lists per environment (NIN <= 64); d->N2 <= 3584 (the meshes of operator mode 3)
+ *   n_ref      : device int32[B]       inlet dofs of the canonical inlet
+ *   inlet_y    : device double[B][NIN] their y, ascending (meshdqn_amd/inflow.py: canonical_inlet)
+ *   n_inlet, inlet_dofs [B][NIN], n_rows, rows [B][NIR] : outputs, laid out as in mdq_inflow_profile; inlet_dofs[b][r] is the
+ *                dof whose y has rank r among the inlet dofs, so values[b][s][r] belongs to inlet_y[b][r]; rows ascending;
+ *                both padded with -1
+ *   map_status : device int32[B], sticky (written only while 0; zero it before the first call): the first failure of an
+ *                environment - 1 inlet count != n_ref[b], 2 a y differs from inlet_y by more than 1e-12 (top - bot),
+ *                3 more than NIR rows, 4 an inlet-adjacent free row is a row of an outflow facet (mdq_ipcs_evolve_profile
+ *                does not re-apply their correction).  A failing environment gets n_inlet = n_rows = 0 and lists of -1 (its
+ *                flow then runs under whatever bcu_gx holds: read map_status before trusting its forces); the other
+ *                environments are not disturbed, and every write stays inside the lists whatever the mesh data hold.
+ * PRECONDITION: bcu_gx is what mdq_env_topology (or the host engine) wrote for this mesh, the constant parabola - the inlet
+ * dofs are the dofs with bcu_flag != 0 && bcu_gx != 0 - so call it before the first mdq_ipcs_evolve_profile /
+ * mdq_ipcs_evolve_fresh_profile on the mesh, which rewrite bcu_gx.  Reads nv, nt, ne, coords, cell_dofs, cell_outflow,
+ * bcu_flag, bcu_gx of the descriptor; needs no set-up and no workspace.
+ */
+MDQ_API int mdq_ipcs_build_inlet_map(const mdq_ipcs_desc* d, int32_t NIN, int32_t NIR,
+                    const int32_t* n_ref, const double* inlet_y,
+                    int32_t* n_inlet, int32_t* inlet_dofs, int32_t* n_rows, int32_t* rows, int32_t* map_status, void* stream);
+
+/*
+ * mdq_ipcs_evolve_fresh under an inflow profile: mdq_ipcs_evolve_profile on a new mesh in the same descriptor, the history
+ * taken as empty the way mdq_ipcs_evolve_fresh does it (appended within ABI 8).  prof = NULL: exactly mdq_ipcs_evolve_fresh
+ * with inflow_scale = NULL.  Same argument checks and the same refusal of every operator mode but 2 and 3, before any launch,
+ * as mdq_ipcs_evolve_profile.
+ */
+MDQ_API int mdq_ipcs_evolve_fresh_profile(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift,
+                    int32_t* iters, const mdq_inflow_profile* prof, void* stream);
+
+/*
  * Same as mdq_ipcs_evolve (`FlowSolver.evolve`, flow_solver.py:362-396) for the three-kernel mode 3, with HIP events recorded on `stream` around every
  * kernel launch; the accumulated durations (milliseconds over all nsteps) of the velocity / pressure /
  * correction kernels are returned in host array kernel_ms[3].  Synchronises the stream (measurement aid).

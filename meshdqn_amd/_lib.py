@@ -165,6 +165,9 @@ SYMBOLS = {
                                         C.c_void_p]),
     "mdq_ipcs_evolve_profile": (C.c_int, [C.POINTER(IpcsDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(InflowProfile), C.c_void_p]),
+    "mdq_ipcs_build_inlet_map": (C.c_int, [C.POINTER(IpcsDesc), C.c_int32, C.c_int32] + [C.c_void_p] * 8),
+    "mdq_ipcs_evolve_fresh_profile": (C.c_int, [C.POINTER(IpcsDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(InflowProfile), C.c_void_p]),
     "mdq_ipcs_evolve_timed": (C.c_int, [C.POINTER(IpcsDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(C.c_double)]),
     "mdq_probe_forces": (C.c_int, [C.POINTER(IpcsDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -20,14 +20,17 @@ class FlowLeg:
     NRL = 4032         # row capacity of a chunk's list in the device-built tile maps (the kernels' LDS stage holds 4064 rows)
 
     def __init__(self, device, topo, solver, steps: int, rtol: float, pressure: str = "cg", pcg_degree: int = 0, ftopo=None,
-                 env_phys=None, inflow_scale=None):
+                 env_phys=None, inflow_scale=None, inflow_profile=None):
         """`topo`: the environment's topology engine (host or device); `solver`: mu / rho / dt_value of the flow;
         `ftopo`: the flow stream's own `DeviceTopologyBatch` (flow_only, with the IPCS index data) = overlap mode;
         `env_phys`: device float64 (B, 4) rows mu, rho, dt, 0 - the flow constants per environment (validated by the
         caller, `ipcs_batch.flow_table`; `solver` then carries row 0 for the descriptor's scalars, which are only
         validated) - or None; `inflow_scale`: device float64 (B, steps) inflow factors of the leg's steps (built once by the
         caller, `inflow.inflow_factors`: the leg always restarts from the last snapshot, so the table is static) - or None,
-        the constant parabola."""
+        the constant parabola; `inflow_profile`: dict(n_ref int32 (B,), inlet_y float64 (B, NIN), values float64
+        (B, steps, NIN)) of device tensors - a non-separable inflow at every environment's canonical inlet
+        (`inflow.leg_profile_table`, static for the same reason); the leg maps the inlet points to the dofs of every new mesh
+        on the device (`mdq_ipcs_build_inlet_map`) - or None.  Not both."""
         self.lib, self.device, self.steps, self.pressure = _lib.load(), device, int(steps), pressure
         self.topo, self.ftopo = topo, ftopo
         tp = ftopo if ftopo is not None else topo           # the engine whose index data the descriptor reads
@@ -69,6 +72,25 @@ class FlowLeg:
         if inflow_scale is not None and (inflow_scale.shape != (B, self.steps) or inflow_scale.dtype != torch.float64 or
                                          not inflow_scale.is_contiguous() or inflow_scale.device.type != "cuda"):
             raise ValueError(f"inflow_scale: a contiguous float64 device tensor of shape ({B}, {self.steps})")
+        # a non-separable inflow: the static tables of the caller, the map of every leg's mesh (owned here, rebuilt by every
+        # leg: NIR = NP cannot overflow, and inflow_lift_kernel loops over n_rows only) and the record the evolve call reads
+        self.inflow_profile = inflow_profile
+        self.map_status = self._prof = None
+        if inflow_profile is not None:
+            check_leg_profile(inflow_profile, inflow_scale, B, self.steps, NP)
+            NIN = int(inflow_profile["inlet_y"].shape[1])
+
+            def zi(*shape):
+                return torch.zeros(shape, dtype=torch.int32, device=dev)
+
+            self.inlet_map = dict(n_inlet=zi(B), inlet_dofs=zi(B, NIN), n_rows=zi(B), rows=zi(B, NP))
+            # sticky like `status`: the first failure of an environment's map (codes: MAP_STATUS), read with it
+            self.map_status = zi(B)
+            pr = self._prof = _lib.InflowProfile()
+            pr.NIN, pr.NIR = NIN, NP
+            for kk, a in self.inlet_map.items():
+                setattr(pr, kk, a.data_ptr())
+            pr.values = inflow_profile["values"].data_ptr()
         # meshes beyond the LDS-resident modes (auto: the element tiles, modes 5 / 7): the tile maps of every coarsened mesh are
         # built on the device in front of the IPCS step (mdq_ipcs_build_tile_maps: row lists + packed local maps) - without
         # them the element results of every operator application go through 0.6 MB of global scratch per environment
@@ -134,10 +156,23 @@ class FlowLeg:
         if self.pressure == "direct":
             _lib.check(self.lib.mdq_ipcs_factorize_pressure(C.byref(d), self.pd_status.data_ptr(), _lib.stream_ptr()),
                        "mdq_ipcs_factorize_pressure")
+        pr = self._prof
+        if pr is not None:                  # which dof of THIS mesh is which inlet point (reads the mesh + the fresh bcu_gx only)
+            ip, m = self.inflow_profile, self.inlet_map
+            _lib.check(self.lib.mdq_ipcs_build_inlet_map(C.byref(d), pr.NIN, pr.NIR, ip["n_ref"].data_ptr(), ip["inlet_y"].data_ptr(),
+                                                         m["n_inlet"].data_ptr(), m["inlet_dofs"].data_ptr(), m["n_rows"].data_ptr(),
+                                                         m["rows"].data_ptr(), self.map_status.data_ptr(), _lib.stream_ptr()),
+                       "mdq_ipcs_build_inlet_map")
         if before_evolve is not None:       # (the set-up above reads the mesh only; the warm start is needed from here on)
             before_evolve()
         # a new mesh: no initial-guess history, iteration counters from zero - mode 3 takes both inside the kernels of its
         # first step (no reset launch on the flow chain), the other modes launch the reset kernel themselves
+        if pr is not None:
+            _lib.check(self.lib.mdq_ipcs_evolve_fresh_profile(C.byref(d), self.steps, out[0].data_ptr(), out[1].data_ptr(),
+                                                              self.iters.data_ptr(), C.byref(pr), _lib.stream_ptr()),
+                       "mdq_ipcs_evolve_fresh_profile")
+            self._keep = keep
+            return out
         _lib.check(self.lib.mdq_ipcs_evolve_fresh(C.byref(d), self.steps, out[0].data_ptr(), out[1].data_ptr(),
                                                   self.iters.data_ptr(),
                                                   None if self.inflow_scale is None else self.inflow_scale.data_ptr(),
@@ -261,7 +296,8 @@ class FlowLeg:
         res["done"].synchronize()
         fd, fl = res["host"][0].numpy().copy(), res["host"][1].numpy().copy()
         if not previous:        # (the read-back of `step_end` does not check the status words)
-            check_flow_forces(fd, fl, "flow_wait", self.status.cpu().numpy())
+            check_flow_forces(fd, fl, "flow_wait", self.status.cpu().numpy(),
+                              None if self.map_status is None else self.map_status.cpu().numpy())
         return fd, fl
 
     def drop_pending(self):
@@ -272,11 +308,59 @@ class FlowLeg:
             self._last = self._reported = None
 
 
-def check_flow_forces(drag, lift, where, status=None):
-    """Raises when a flow leg reported a step it could not take: a set status word (mdq_ipcs_desc.status: the two-workgroup
+def profile_leg_refusal(NP: int):
+    """None when a flow leg on meshes of capacity NP rows can take an inflow profile, else the reason: the profile is
+    rewritten BETWEEN the steps of a launch sequence, which only the leg's mode 3 (NP <= 3584) has - the refined meshes run
+    modes 5 / 7, which loop over the steps inside one kernel."""
+    if int(NP) <= 3584:
+        return None
+    return (f"inflow_profile: a flow leg on meshes of {int(NP)} P2 rows (> 3584) runs the element-tile operator modes 5 / 7, which "
+            "loop over the steps inside one kernel; a non-separable inflow on such meshes is served by the per-step path "
+            "(FlowSolver.evolve / IpcsBatch.update_inflow, one step per call)")
+
+
+def check_leg_profile(inflow_profile, inflow_scale, B: int, steps: int, NP: int):
+    """Argument validation of `FlowLeg(inflow_profile=...)` (needs no device: the tensors are only inspected)."""
+    if inflow_scale is not None:
+        raise ValueError("inflow_profile and inflow_scale are mutually exclusive (a schedule beside a callable goes through the "
+                         "profile's table: inflow.leg_profile_table)")
+    why = profile_leg_refusal(NP)
+    if why is not None:
+        raise ValueError(why)
+    if not isinstance(inflow_profile, dict) or set(inflow_profile) != {"n_ref", "inlet_y", "values"}:
+        raise ValueError("inflow_profile: a dict with the keys n_ref, inlet_y, values")
+    y = inflow_profile["inlet_y"]
+    NIN = int(y.shape[1]) if getattr(y, "ndim", 0) == 2 else -1
+    want = dict(n_ref=((B,), torch.int32), inlet_y=((B, NIN), torch.float64), values=((B, steps, NIN), torch.float64))
+    for k, (shape, dtype) in want.items():
+        a = inflow_profile[k]
+        if (not isinstance(a, torch.Tensor) or NIN < 1 or tuple(a.shape) != shape or a.dtype != dtype or not a.is_contiguous()
+                or a.device.type != "cuda"):
+            raise ValueError(f"inflow_profile[{k!r}]: a contiguous {str(dtype).replace('torch.', '')} device tensor of shape "
+                             f"{shape if NIN >= 1 else '(B, NIN) / (B, steps, NIN)'}")
+    if NIN > 64:
+        raise ValueError(f"inflow_profile: {NIN} inlet dofs per environment (the device's inlet map holds 64)")
+
+
+# map_status of the flow leg's inlet map (mdq_ipcs_build_inlet_map)
+MAP_STATUS = {1: "the mesh's inlet has another number of dofs than the canonical inlet",
+              2: "an inlet dof's y differs from the canonical inlet's",
+              3: "more inlet-adjacent rows than the row list holds",
+              4: "an inlet-adjacent free row is also a row of an outflow facet (the inflow kernel does not re-apply its correction)"}
+
+
+def check_flow_forces(drag, lift, where, status=None, map_status=None):
+    """Raises when the inlet map of a leg under an inflow profile failed (`map_status`, codes MAP_STATUS: that environment ran
+    under the wrong inflow) or when a flow leg reported a step it could not take: a set status word (mdq_ipcs_desc.status: the two-workgroup
     operator modes 4 / 7 abandon a step when a team barrier times out - the partner workgroup was not resident because another
     process or stream held its CU; csrc/mdq_ipcs.hip `team_failed`; u_n / p_n of that environment were not advanced) or
     non-finite drag / lift (the same event seen through the forces, or a solve that diverged)."""
+    ms = None if map_status is None else np.asarray(map_status)
+    if ms is not None and (ms != 0).any():
+        which = np.flatnonzero(ms)
+        raise _lib.MeshDQNHipError(
+            f"{where}: the inlet map of the flow leg's inflow profile failed in environment(s) {which[:8].tolist()}"
+            f"{' ...' if which.size > 8 else ''}: " + "; ".join(f"code {c}: {MAP_STATUS.get(c, 'unknown')}" for c in sorted(set(ms[which].tolist()))))
     bad = ~(np.isfinite(drag) & np.isfinite(lift))
     bad = bad.reshape(bad.shape[0], -1).any(1)
     timed_out = np.zeros_like(bad) if status is None else (np.asarray(status) != 0)

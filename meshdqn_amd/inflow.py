@@ -19,6 +19,11 @@ K steps of a call are evaluated here, up front, at the inlet dofs (`profile_valu
 step, uploaded once), and a small kernel between the steps rewrites what depends on them - bcu_gx at the inlet dofs and the
 lifting vectors on the rows that share a cell with one (`inlet_tables`).  In the operator modes that loop over the steps
 inside one kernel it keeps the per-step path of `FlowSolver.evolve` / `IpcsBatch.update_inflow`.
+
+The S3 flow leg of `VecEnv2DAirfoil` takes a callable as well.  Its meshes are numbered on the device, so the host hands over
+values at the CANONICAL inlet of every config's original mesh (`canonical_inlet`, `leg_profile_table`: the inlet points never
+change during an episode, and the leg always restarts at t = solver_steps * dt) and the device finds the dofs and rows on every
+new mesh (`mdq_ipcs_build_inlet_map`).
 """
 from __future__ import annotations
 
@@ -166,6 +171,49 @@ def padded(tables, key: str) -> tuple:
     for b, t in enumerate(tables):
         out[b, :n[b]] = t[key]
     return n, out
+
+
+def canonical_inlet(topo, coords) -> dict:
+    """The inlet of a base mesh in the order the device's inlet map uses (`mdq_ipcs_build_inlet_map`): `inlet_tables` on the
+    ORIGINAL topology sorted by y - dict(dofs int32 (n,), xy float64 (n, 2), gx0 float64 (n,), y float64 (n,) ascending).
+    Boundary vertices are never removed or moved, so these points are the inlet points of every mesh of an episode; only
+    their dof numbers change."""
+    tab = inlet_tables([topo], [coords])[0]
+    order = np.argsort(tab["xy"][:, 1], kind="stable")
+    xy = np.ascontiguousarray(tab["xy"][order])
+    return dict(dofs=tab["dofs"][order].copy(), xy=xy, gx0=tab["gx0"][order].copy(), y=xy[:, 1].copy())
+
+
+def leg_profile_table(inlets, profiles, specs, dts, airfoil, first_step: int, nsteps: int) -> dict:
+    """The static inflow table of the S3 flow leg, which always restarts at t = first_step * dt_b: per CONFIG a the values of
+    steps first_step + 1 .. first_step + nsteps at its canonical inlet (`inlets[a]`: `canonical_inlet`), gathered by
+    `airfoil` (B,) to the batch.  A config contributes `profiles[a](x, y, t)` at `step_times`, or - the one table serves a
+    batch that mixes the kinds - `inflow_factors(specs[a], ...) * gx0` for a schedule and `gx0` for None.  `dts`: dt per config.
+    Returns dict(n_ref int32 (B,), inlet_y float64 (B, NIN) zero-padded, values float64 (B, nsteps, NIN) zero-padded).
+    Validation as in `profile_values`: a result of another shape or a non-finite one raises ValueError naming the config
+    and the step."""
+    A = len(inlets)
+    if not (len(profiles) == len(specs) == len(dts) == A):
+        raise ValueError(f"leg_profile_table: one profile, one schedule and one dt per config ({A})")
+    NIN = max(max(len(t["y"]) for t in inlets), 1)
+    vals = np.zeros((A, int(nsteps), NIN), np.float64)
+    ys = np.zeros((A, NIN), np.float64)
+    for a, (tab, p, s, dt) in enumerate(zip(inlets, profiles, specs, dts)):
+        n = len(tab["y"])
+        ys[a, :n] = tab["y"]
+        if p is not None:
+            try:
+                vals[a, :, :n] = profile_values([p], [tab], step_times(dt, first_step, nsteps, 1))[0, :, :n]
+            except ValueError as exc:
+                raise ValueError(str(exc).replace("environment 0", f"config {a}")) from None
+        elif s is not None:
+            vals[a, :, :n] = inflow_factors(s, dt, first_step, nsteps)[0][:, None] * tab["gx0"][None, :]
+        else:
+            vals[a, :, :n] = tab["gx0"]
+    airfoil = np.asarray(airfoil, np.int64)
+    n_ref = np.array([len(t["y"]) for t in inlets], np.int32)[airfoil]
+    return dict(n_ref=np.ascontiguousarray(n_ref), inlet_y=np.ascontiguousarray(ys[airfoil]),
+                values=np.ascontiguousarray(vals[airfoil]))
 
 
 def step_times(dt, first_step: int, nsteps: int, B: int) -> np.ndarray:

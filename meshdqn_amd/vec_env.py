@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from .env import Env2DAirfoil
 from .flow_leg import FlowLeg, check_flow_forces
-from .inflow import inflow_factors, spec_table
+from .inflow import canonical_inlet, inflow_factors, leg_profile_table, spec_table
 from .ipcs_batch import flow_table
 from .mesh_ops import (DeviceTopologyBatch, HostTopologyBatch, remesh_batch, remesh_batch_gpu, remesh_workspace, smooth_batch_gpu,
                        smooth_env_gpu)
@@ -119,7 +119,9 @@ class VecEnv2DAirfoil:
         [0, A): the airfoil of every environment (default b mod A); `mixed_flow`: the configs may also differ in mu, rho
         and dt (one batch over several Reynolds numbers: `self.flow_of_env`), also on one and the same mesh;
         `mixed_inflow`: the configs may also differ in flow_params.inflow, the inflow schedule (inflow.py:
-        `self.inflow_of_env`, (B, 4) rows amplitude, pulsation, frequency, phase - set for a single scheduled config as well)."""
+        `self.inflow_of_env`, (B, 4) rows amplitude, pulsation, frequency, phase - set for a single scheduled config as well)
+        or a callable profile(x, y, t) (the S3 flow leg then steps under `self.flow.inflow_profile`, the table of inlet values
+        of every environment; a single config with a callable needs no flag)."""
         self.lib = _lib.load()
         self.B = int(num_envs)
         configs = list(config) if isinstance(config, (list, tuple)) else [config]
@@ -213,10 +215,23 @@ class VecEnv2DAirfoil:
         if not self.mixed_inflow and any(s_ != specs[0] for s_ in specs):
             raise ValueError("flow_params: the inflow schedule must agree across the airfoils (mixed_inflow=True admits one "
                              "per config)")
+        # ... and callables profile(x, y, t), the non-separable kind: the leg's values at every config's canonical inlet (the
+        # inlet points of the original mesh: boundary vertices are never removed or moved) are as static as the factors; the
+        # leg maps the points to the dofs of every new mesh on the device.  A batch that mixes the kinds goes through that one
+        # table (a schedule config: its factors times the parabola, None: the parabola)
+        profs = [getattr(bb.flow_solver, "inflow_profile", None) for bb in bases]
+        if not self.mixed_inflow and any(p_ != profs[0] for p_ in profs):
+            raise ValueError("flow_params: the inflow profile must agree across the airfoils (mixed_inflow=True admits one "
+                             "per config)")
         tab = spec_table(specs)
         self.inflow_of_env = None if tab is None else tab[self.airfoil]                                 # (B, 4)
-        self._flow_inflow = None
-        if tab is not None and self.flow_steps > 0:
+        self._flow_inflow = self._flow_profile = None
+        if any(p_ is not None for p_ in profs) and self.flow_steps > 0:
+            inlets = [canonical_inlet(bb._orig_topo, bb._orig_topo.coords) for bb in bases]
+            ptab = leg_profile_table(inlets, profs, specs, [bb.flow_solver.dt_value for bb in bases], self.airfoil,
+                                     int(base.solver_steps), self.flow_steps)
+            self._flow_profile = {k: torch.from_numpy(v).to(self.device) for k, v in ptab.items()}
+        elif tab is not None and self.flow_steps > 0:
             dts = (self.flow_of_env[:, 2] if self.flow_of_env is not None else
                    np.array([bb.flow_solver.dt_value for bb in bases], np.float64)[self.airfoil])
             f = inflow_factors([specs[a] for a in self.airfoil], dts, int(base.solver_steps), self.flow_steps)
@@ -310,7 +325,7 @@ class VecEnv2DAirfoil:
         if self.flow_steps > 0:
             fl = self.flow = FlowLeg(self.device, self.dtopo if self.gpu_topology else self.topo, self._flow0, self.flow_steps,
                                      self.flow_rtol, self.flow_pressure, self.flow_pcg_degree, ftopo, env_phys=self.env_phys,
-                                     inflow_scale=self._flow_inflow)
+                                     inflow_scale=self._flow_inflow, inflow_profile=self._flow_profile)
             self.flow_t, self.flow_iters, self.flow_status, self.flow_pd_status = fl.t, fl.iters, fl.status, fl.pd_status
             self._flow_tile_maps = fl.tile_maps
             self.flow_drag = np.zeros((B, self.flow_steps))
@@ -1025,6 +1040,8 @@ class VecEnv2DAirfoil:
         parts += [(k, dt.t[k]) for k in ("nsel", "nedges", "ne", "coord_map", "n_closest")]
         if self.flow_steps > 0:
             parts.append(("flow_status", self.flow_status))        # (legs up to the previous step: the last one may still run)
+            if self.flow.map_status is not None:
+                parts.append(("flow_map_status", self.flow.map_status))
         flat = [t.contiguous().view(torch.uint8).reshape(-1) for _, t in parts]
         pad = [(-f.numel()) % 8 for f in flat]                  # (every part starts 8-byte aligned in the packed buffer)
         packed = torch.cat([x for f, p_ in zip(flat, pad) for x in ((f, f.new_zeros(p_)) if p_ else (f,))])
@@ -1044,7 +1061,7 @@ class VecEnv2DAirfoil:
         if int(got["err"][0]) != 0:
             raise _lib.MeshDQNHipError("topology kernel failed inside rollout_device")
         if K:               # a failed flow leg is an ERROR here, not a NaN in what the caller reads later
-            check_flow_forces(got["drag"], got["lift"], "rollout_device", got.get("flow_status"))
+            check_flow_forces(got["drag"], got["lift"], "rollout_device", got.get("flow_status"), got.get("flow_map_status"))
         self.nv[...], self.nt[...], self.offset[...], self.steps[...] = got["nv"], got["nt"], got["offset"], got["steps"]
         for k in ("nsel", "nedges", "ne", "coord_map", "n_closest"):
             h[k][...] = got[k]

@@ -7,7 +7,14 @@
   constant   under the constant inflow (`FlowSolver.evolve(save_steps)`: the yardstick of the same build).
 
 HIP events and wall clock around the whole run, after one warm-up run of each way.
-   python tools/time_inflow_profile.py [steps] [save_steps]"""
+   python tools/time_inflow_profile.py [steps] [save_steps]
+
+S3 case: the batched environment step with its flow leg (`VecEnv2DAirfoil.rollout_device`, flow_steps = 1, overlap mode, B
+ys930 environments) under the constant inflow, under a schedule (one factor per environment and step inside the kernels) and
+under a callable (the leg maps the inlet onto every new mesh - `mdq_ipcs_build_inlet_map` - and rewrites the lifts in front of
+its step: two launches more per leg).  The cases alternate in one process; every window is `steps` batched steps between two
+device synchronisations, after a warm-up rollout of each environment.
+   python tools/time_inflow_profile.py s3 [B] [steps] [repeats] [cases, e.g. constant,schedule]"""
 import os
 import sys
 import time
@@ -22,8 +29,8 @@ import torch  # noqa: E402
 torch.set_num_threads(1)
 from meshdqn_amd.flow_solver import FlowSolver  # noqa: E402
 
-STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
-SAVE = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+STEPS = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1] != "s3" else 1000
+SAVE = int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[1] != "s3" else 200
 G = os.path.join(ROOT, "tests", "golden")
 DT = 1e-3
 
@@ -67,6 +74,62 @@ def timed(make, run):
     e1.synchronize()
     return e0.elapsed_time(e1), 1e3 * (time.perf_counter() - t0), drag
 
+
+def s3_main(argv):
+    from meshdqn_amd.airfoilgcnn import NodeRemovalNet
+    from meshdqn_amd.env import Env2DAirfoil
+    from meshdqn_amd.gcn_fused import FusedGcn
+    from meshdqn_amd.vec_env import VecEnv2DAirfoil
+    nenv = int(argv[0]) if len(argv) > 0 else 128
+    steps = int(argv[1]) if len(argv) > 1 else 40
+    repeats = int(argv[2]) if len(argv) > 2 else 3
+    names = argv[3].split(",") if len(argv) > 3 else ["constant", "schedule", "callable"]
+    inflows = dict(constant="constant", schedule=dict(amplitude=1.0, pulsation=0.5, frequency=125.0), callable=profile)
+    dev = torch.device("cuda")
+    torch.manual_seed(0)
+    net = NodeRemovalNet(181, conv_width=128, topk=0.1)
+    net.set_num_nodes(17)
+    net = net.to(dev)
+    rng = np.random.default_rng(1370)
+    envs = {}
+    for name in names:
+        cfg = dict(flow_config=dict(flow_params=dict(mu=1e-3, rho=1.0, inflow=inflows[name]),
+                                    geometry_params=dict(mesh=os.path.join(G, "ys930.npz")),
+                                    solver_params=dict(dt=DT, solver_type="lu", smooth=True)),
+                   agent_params=dict(solver_steps=20, episodes=10, timesteps=10000, threshold=0.001, N_closest=180, gt_drag=-1,
+                                     gt_time=-1, u=-1, p=-1, time_reward=0.005, save_steps=4, goal_vertices=0.95, plot_dir=""))
+        venv = VecEnv2DAirfoil(cfg, nenv, compute_device=dev, base_env=Env2DAirfoil(cfg, compute_device=dev), flow_steps=1,
+                               flow_rtol=1e-10, flow_overlap=True)
+        fused = FusedGcn(net)
+        venv.calibrate_streams(fused)
+        envs[name] = (venv, fused)
+
+    def window(name, k):
+        venv, fused = envs[name]
+        ex, ra = rng.random((k, nenv)) < 0.5, rng.integers(0, 181, (k, nenv))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        venv.rollout_device(fused, k, ex, ra)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    for name in names:
+        window(name, 8)                       # warm-up
+    rates = {name: [] for name in names}
+    for _ in range(repeats):
+        for name in names:                    # alternating: drift of the machine hits every case alike
+            rates[name].append(nenv * steps / window(name, steps))
+    for name in names:
+        r = rates[name]
+        venv = envs[name][0]
+        kind = "profile table" if getattr(venv.flow, "inflow_profile", None) is not None else ("factors" if venv.flow.inflow_scale is not None else "none")
+        print(f"S3 B = {nenv}, {steps} batched steps per window, {name} (leg's inflow table: {kind}): env steps/s "
+              f"{' '.join(f'{x:.0f}' for x in r)} | median {np.median(r):.0f}, min {min(r):.0f}, max {max(r):.0f}", flush=True)
+
+
+if sys.argv[1:2] == ["s3"]:
+    s3_main(sys.argv[2:])
+    sys.exit(0)
 
 for mode, reproducible in ((2, True), (3, False)):
     ways = {"profile": (lambda: solver(profile, reproducible), run_calls),
