@@ -598,7 +598,7 @@ __device__ __forceinline__ void run_level(const Lds& L, const Level& lv, int C, 
       if (i < n)
         for (int c = sub; c < C; c += 16) {
           float hv = L.h[i * (C + 1) + c];
-          hv = hv > 0.f ? hv : 0.f;
+          hv = hv < 0.f ? 0.f : hv;   // (relu that lets a NaN through, as torch's does: `hv > 0 ? hv : 0` turned a NaN row into zeros)
           L.h[i * (C + 1) + c] = hv;
           sp = fmaf(hv, L.deg[c], sp);
         }
@@ -738,7 +738,7 @@ __global__ __launch_bounds__(WGT) void gcn_embed_kernel(mdq_gcn_net net, int NMA
   if (status && tid == 0) status[b] = (nn > NMAX || nn < 0) ? -1 : (ne > EMAX || ne < 0) ? -2 : 0;
   if (nn > NMAX || ne > EMAX || nn < 0 || ne < 0) {
     // the LDS carve-up is sized from NMAX / EMAX: a larger graph must not be staged.  Its outputs are NaN (never a
-    // plausible Q-value) and, where the caller passed one, its status says why
+    // plausible Q-value: the relus of the head let NaNs through) and, where the caller passed one, its status says why
     if (tid < 2 * C) emb[(size_t)b * 2 * C + tid] = __builtin_nanf("");
     return;
   }
@@ -830,7 +830,7 @@ __device__ inline void head_layer(const float* in, int in_stride, int K, const f
       for (int r = 0; r < 16; ++r) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         float v = acc[r] + bc;
-        if (relu) v = v > 0.f ? v : 0.f;
+        if (relu) v = v < 0.f ? 0.f : v;   // (NaN stays NaN)
         out[row * out_stride + col] = v;
       }
     }
@@ -898,7 +898,7 @@ __device__ __forceinline__ void head_mma(const float* in, int in_stride, const f
     for (int r = 0; r < 16; ++r) {
       const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
       float v = acc[r] + bc;
-      if (relu) v = v > 0.f ? v : 0.f;
+      if (relu) v = v < 0.f ? 0.f : v;   // (NaN stays NaN)
       out[row * out_stride + col] = v;
     }
   }
@@ -1002,7 +1002,7 @@ __device__ __forceinline__ void head16_mma(const float* in, int in_stride, const
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float v = acc[r] + bc;
-      if (relu) v = v > 0.f ? v : 0.f;
+      if (relu) v = v < 0.f ? 0.f : v;   // (NaN stays NaN)
       out[(4 * kq + r) * out_stride + col] = v;
     }
   }

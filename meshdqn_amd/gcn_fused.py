@@ -243,7 +243,7 @@ class FusedGcn:
 
     @torch.no_grad()
     def forward_arrays(self, x, node_ptr, esrc, edst, edge_ptr, nmax, emax, stream=None, edge_counts=None,
-                       return_perm=False, return_status=False, pack=True, edge_cnt=None):
+                       return_perm=False, return_status=False, pack=True, edge_cnt=None, return_embedding=False):
         """Same launch on pre-built arrays (what `VecEnv2DAirfoil.get_state` returns): x (sumN,F) f32,
         node_ptr / edge_ptr (B+1,) i32, esrc / edst (sumE,) i32 local node ids.  `nmax` / `emax` size the kernel's LDS
         carve-up: `edge_counts` (host array of the per-graph edge counts, where the caller has them) is checked against
@@ -251,7 +251,8 @@ class FusedGcn:
         `return_perm`: also the (B, levels, nmax) TopKPooling `perm` arrays.  `pack=False`: use the packed parameter copy
         as it is (the caller has called `_pack()` at a point ordered against the writers of the parameters).  `edge_cnt`
         ((B,) i32 device tensor): the edge lists are PADDED - esrc / edst are (B, emax) arrays, graph b owns the first
-        edge_cnt[b] slots of its row (what `mdq_env_topology` writes) - and `edge_ptr` is ignored."""
+        edge_cnt[b] slots of its row (what `mdq_env_topology` writes) - and `edge_ptr` is ignored.  `return_embedding`: also
+        the (B, 2C) graph embeddings the head read, last in the returned tuple."""
         if pack:
             self._pack(stream)
         elif self.desc is None:
@@ -281,8 +282,8 @@ class FusedGcn:
                                              out.data_ptr(), None if perm is None else perm.data_ptr(),
                                              None if status is None else status.data_ptr(), _lib.stream_ptr(stream))
             _lib.check(rc, "mdq_gcn_forward_ex")
-        if return_perm or return_status:
-            return (out,) + ((perm,) if return_perm else ()) + ((status,) if return_status else ())
+        if return_perm or return_status or return_embedding:
+            return (out,) + ((perm,) if return_perm else ()) + ((status,) if return_status else ()) + ((emb,) if return_embedding else ())
         return out
 
 
