@@ -504,6 +504,19 @@ MDQ_API int64_t mdq_gcn_train_workspace(const mdq_gcn_net* net, int32_t NMAX, in
  */
 MDQ_API int mdq_gcn_train_step(const mdq_gcn_net* net, const mdq_gcn_train_desc* d, void* stream);
 
+/*
+ * The same learning step with two optional per-graph device arrays (appended within ABI 8; both NULL: exactly
+ * mdq_gcn_train_step, which calls this one):
+ *   weight float [B] (in)   importance weight w_b of graph b (prioritized replay): its loss term is w_b huber(diff_b), the
+ *                           derivative handed to the backward pass is a clamp(diff_b, -1, 1) / B * w_b, `loss` is the mean of
+ *                           the weighted terms.  Both are one multiplication behind the unweighted arithmetic: a table of
+ *                           ones gives the bits of NULL; a graph of weight 0 leaves an all-zero slice of `partial`.
+ *   td     float [B] (out)  diff_b, the TD error the Huber loss is taken of: out[b][action_b] - target_b (mode 0),
+ *                           q_other[b][action_b] - target_b (mode 1); NaN for a graph beyond NMAX / EMAX.
+ */
+MDQ_API int mdq_gcn_train_step_weighted(const mdq_gcn_net* net, const mdq_gcn_train_desc* d, const float* weight, float* td,
+                                void* stream);
+
 /* Parameters of the module (torch layout) into the layout the kernels read, all segments in ONE launch:
  * segment s is a [rows][cols] matrix written transposed ([cols][rows]); cols == 1: a plain copy of `rows` floats. */
 #define MDQ_GCN_PACK_MAX 32
@@ -553,6 +566,53 @@ typedef struct mdq_replay_sample_desc {
   float* nonfinal;            /* [n] */
 } mdq_replay_sample_desc;
 MDQ_API int mdq_replay_sample(const mdq_replay_sample_desc* d, void* stream);
+
+/*
+ * Proportional prioritized replay on the record ring (Schaul et al. 2016; no reference counterpart: ReplayMemory.sample is
+ * uniform).  Appended within ABI 8.  float prio[capacity] holds p_j = (|td_j| + eps)^alpha of record j, and
+ *     prio[j] == 0  <=>  record j must not be drawn (never written, or of the group that is being written),
+ * so no entry point takes a window.  float pmax[1] is the largest priority seen so far (the caller starts it at 1).  All
+ * pointers device; every launch on `stream`; no atomics, no device random numbers: results are run-to-run identical.
+ *
+ * mdq_replay_prio_fill: prio[(base_new + i) % capacity] = *pmax for i < n_new (a group whose records have just received
+ * their next states: every new transition is drawn at least once soon) and prio[(base_zero + i) % capacity] = 0 for
+ * i < n_zero (the group about to be written).  Either length may be 0 (both: no launch).  A range longer than the
+ * capacity, a base outside [0, capacity) and ranges that overlap are refused before any launch.
+ */
+MDQ_API int mdq_replay_prio_fill(float* prio, int32_t capacity, int32_t base_new, int32_t n_new, int32_t base_zero,
+                         int32_t n_zero, const float* pmax, void* stream);
+
+/*
+ * mdq_replay_prio_draw: one stratified minibatch of n records, one workgroup.  With S_j = prio[0] + ... + prio[j] (fp64,
+ * summed in an order that depends on `capacity` only) and total = S_{capacity - 1}:
+ *     t_i       = total * ((i + u[i]) / n)                     evaluated as written, in fp64
+ *     idx[i]    = the smallest j with S_j > t_i (such a record has prio[j] > 0); if there is none - (i + u[i]) / n rounded
+ *                 to 1 - the last j with prio[j] > 0
+ *     weight[i] = (float) pow(min_k prio[idx[k]] / prio[idx[i]], beta)      (fp64, rounded once): the importance weights
+ *                 (N p_i)^-beta divided by their largest one
+ *     total[0]  = total                                        (if `total` is not NULL)
+ * total == 0 (nothing to draw from): every idx[i] = 0 and every weight[i] = 0 - nothing downstream reads out of bounds and
+ * the minibatch carries no gradient.
+ */
+typedef struct mdq_replay_prio_draw_desc {
+  int32_t capacity, n;        /* records of the ring; draws, 1 .. 1024 */
+  double beta;                /* >= 0 */
+  const float* prio;          /* [capacity] */
+  const double* u;            /* [n] uniforms in [0, 1), drawn by the host */
+  int32_t* idx;               /* [n] (out) */
+  float* weight;              /* [n] (out) */
+  double* total;              /* [1] (out, may be NULL) */
+} mdq_replay_prio_draw_desc;
+MDQ_API int mdq_replay_prio_draw(const mdq_replay_prio_draw_desc* d, void* stream);
+
+/*
+ * mdq_replay_prio_update: for i = 0 .. n - 1 in this order (n <= 1024; one workgroup), unless td[i] is not finite (a graph
+ * the learning step refused) or idx[i] lies outside [0, capacity):
+ *     v = (float) pow(|td[i]| + eps, alpha)  (fp64, rounded once);   prio[idx[i]] = v;   *pmax = max(*pmax, v)
+ * - so among several draws of one record the last one stays.  No write ever leaves the array.
+ */
+MDQ_API int mdq_replay_prio_update(float* prio, int32_t capacity, int32_t n, const int32_t* idx, const float* td, double alpha,
+                           double eps, float* pmax, void* stream);
 
 /*
  * torch.optim.Adam.step (amsgrad False; weight decay added to the gradient) for up to 32 parameter tensors in one

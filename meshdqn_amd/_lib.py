@@ -148,6 +148,12 @@ class ReplaySampleDesc(C.Structure):
                                   "action", "reward", "nonfinal")]
 
 
+class ReplayPrioDrawDesc(C.Structure):
+    """Mirror of `mdq_replay_prio_draw_desc` (appended within ABI 8)."""
+    _fields_ = [("capacity", C.c_int32), ("n", C.c_int32), ("beta", C.c_double)] + [
+        (n, C.c_void_p) for n in ("prio", "u", "idx", "weight", "total")]
+
+
 # every symbol include/meshdqn_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mdq_abi_version": (C.c_int, []),
@@ -219,10 +225,15 @@ SYMBOLS = {
     "mdq_ipcs_reset_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mdq_gcn_train_workspace": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32]),
     "mdq_gcn_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mdq_gcn_train_step_weighted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mdq_gcn_pack": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mdq_replay_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mdq_replay_sample": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mdq_replay_prio_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mdq_replay_prio_draw": (C.c_int, [C.POINTER(ReplayPrioDrawDesc), C.c_void_p]),
+    "mdq_replay_prio_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                         C.c_void_p, C.c_void_p]),
     "mdq_adam_step": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mdq_spin": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
     "mdq_stream_create_cu_mask": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

@@ -127,7 +127,9 @@ __device__ inline void head_bwd_w(const float* dz, int N, const float* a, int K,
   if ((int)threadIdx.x < N) gb[threadIdx.x] = dz[threadIdx.x];
 }
 
-__global__ __launch_bounds__(WGT) void gcn_train_kernel(mdq_gcn_net net, mdq_gcn_train_desc D, int wstride) {
+// weight / td (either may be null): per-graph importance weight of the loss term, per-graph TD error (out)
+__global__ __launch_bounds__(WGT) void gcn_train_kernel(mdq_gcn_net net, mdq_gcn_train_desc D, int wstride,
+                                                        const float* __restrict__ weight, float* __restrict__ td) {
   extern __shared__ __align__(16) float sm[];
   const int b = blockIdx.x, tid = threadIdx.x, C = net.C, OUT = net.out_dim, NMAX = D.NMAX, EMAX = D.EMAX;
   const int n0 = D.node_ptr[b], nn = D.node_ptr[b + 1] - n0;
@@ -137,7 +139,10 @@ __global__ __launch_bounds__(WGT) void gcn_train_kernel(mdq_gcn_net net, mdq_gcn
   if (nn > NMAX || ne > EMAX || nn <= 0 || ne < 0) {
     // a graph the LDS carve-up was not sized for: its loss term is NaN (so is the loss), it adds no gradient (its slice
     // still holds the previous minibatch's values: cleared)
-    if (tid == 0) ws[0] = __builtin_nanf("");
+    if (tid == 0) {
+      ws[0] = __builtin_nanf("");
+      if (td) td[b] = __builtin_nanf("");
+    }
     for (int i = tid; i < D.layout.total; i += WGT) gp[i] = 0.f;
     return;
   }
@@ -275,8 +280,16 @@ __global__ __launch_bounds__(WGT) void gcn_train_kernel(mdq_gcn_net net, mdq_gcn
       }
       const float diff = fmaf(a, qv, -t);
       const float ad = fabsf(diff);
-      ws[0] = ad < 1.f ? 0.5f * diff * diff : ad - 0.5f;                 // HuberLoss(delta = 1)
-      scal[0] = a * fminf(fmaxf(diff, -1.f), 1.f) / (float)D.B;          // d (mean loss) / d q
+      float term = ad < 1.f ? 0.5f * diff * diff : ad - 0.5f;            // HuberLoss(delta = 1)
+      float dq = a * fminf(fmaxf(diff, -1.f), 1.f) / (float)D.B;         // d (mean loss) / d q
+      if (weight) {   // importance weight: a multiplication behind the unweighted arithmetic (1.0f: the same bits)
+        const float w = weight[b];
+        term *= w;
+        dq *= w;
+      }
+      if (td) td[b] = diff;
+      ws[0] = term;
+      scal[0] = dq;
       scal[1] = __int_as_float(jq);
     }
   }
@@ -493,6 +506,11 @@ extern "C" int mdq_gcn_pack(const mdq_gcn_pack_table* table, void* stream) {
 }
 
 extern "C" int mdq_gcn_train_step(const mdq_gcn_net* net, const mdq_gcn_train_desc* d, void* stream) {
+  return mdq_gcn_train_step_weighted(net, d, nullptr, nullptr, stream);
+}
+
+extern "C" int mdq_gcn_train_step_weighted(const mdq_gcn_net* net, const mdq_gcn_train_desc* d, const float* weight, float* td,
+                                           void* stream) {
   using namespace mdq_gcn;
   if (!net || !d || d->B <= 0 || !d->x || !d->node_ptr || !d->edge_ptr || !d->q_other || !d->action || !d->reward ||
       !d->nonfinal || !d->workspace || !d->partial || !d->grad || !d->loss)
@@ -522,7 +540,7 @@ extern "C" int mdq_gcn_train_step(const mdq_gcn_net* net, const mdq_gcn_train_de
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return mdq_set_error(hipGetErrorString(e));
   const int wstride = tape_layout(*net, NMAX, EMAX, nullptr);
-  hipLaunchKernelGGL(gcn_train_kernel, dim3(d->B), dim3(WGT), lds, st, *net, *d, wstride);
+  hipLaunchKernelGGL(gcn_train_kernel, dim3(d->B), dim3(WGT), lds, st, *net, *d, wstride, weight, td);
   e = hipGetLastError();
   if (e != hipSuccess) return mdq_set_error(hipGetErrorString(e));
   hipLaunchKernelGGL(gcn_grad_reduce_kernel, dim3((d->layout.total + 255) / 256), dim3(256), 0, st, d->B, d->layout.total,

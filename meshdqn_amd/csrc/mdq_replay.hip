@@ -1,4 +1,4 @@
-// Device-resident replay memory and optimiser update of the DQN learning loop: with these three kernels a training
+// Device-resident replay memory and optimiser update of the DQN learning loop: with these kernels a training
 // step needs no host round trip and no per-transition Python object -
 //   replay_step_kernel   : the B transitions of one batched env step into the record ring
 //                          (ReplayMemory.push, airfoil_dqn.py:56-61, for B environments at once)
@@ -6,6 +6,7 @@
 //                          (ReplayMemory.sample + the Batch.from_data_list of DataWorker._get_data, airfoil_dqn.py:63-64,240-262)
 //   adam_kernel          : torch.optim.Adam.step (weight decay as L2 term, bias corrections) on every trained
 //                          parameter in one launch (ParameterServer.apply_gradients, airfoil_dqn.py:184-200)
+//   prio_*_kernel        : proportional prioritized replay on the ring (no reference counterpart: its replay is uniform)
 // Record layout (float32, the layout of trainer.pack_transitions: what the ranks all-gather when the replay is shared):
 //   [ x(s) N*F | x(s') N*F | src(s) EM | dst(s) EM | src(s') EM | dst(s') EM | edges(s) | edges(s') | action | reward | done ]
 // (a terminal transition has zeros for s').
@@ -154,6 +155,199 @@ extern "C" int mdq_adam_step(const mdq_adam_desc* d, void* stream) {
     return mdq_set_error("mdq_adam_step: bad arguments");
   hipLaunchKernelGGL(mdq_replay::adam_kernel, dim3(32, d->n), dim3(256), 0, (hipStream_t)stream, *d);
   if (hipGetLastError() != hipSuccess) return mdq_set_error("adam_kernel launch failed");
+  return 0;
+}
+
+// ---------------------------------------------------------------- proportional prioritized replay
+// prio[capacity] holds (|td| + eps)^alpha of every record, 0 for a record that must not be sampled (never written, or of
+// the group being written).  Three kernels on the optimiser stream (semantics: include/meshdqn_hip.h):
+//   prio_fill_kernel   : a finished group gets the largest priority seen so far, the group about to be written gets 0
+//   prio_draw_kernel   : one workgroup: fp64 prefix sums of prio, stratified draw of n records, importance weights
+//   prio_update_kernel : one workgroup: new priorities of the drawn records from their TD errors
+namespace mdq_replay {
+
+constexpr int PT = 1024;   // threads of the draw's workgroup = segments of the priority array
+
+__global__ __launch_bounds__(256) void prio_fill_kernel(float* prio, int capacity, int base_new, int n_new, int base_zero,
+                                                        int n_zero, const float* pmax) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_new)
+    prio[(int)(((long long)base_new + i) % capacity)] = *pmax;
+  else if (i - n_new < n_zero)
+    prio[(int)(((long long)base_zero + (i - n_new)) % capacity)] = 0.f;
+}
+
+// segment k of the 1024 in a table padded by one slot per 32: the 32 threads that walk 32 consecutive segments each
+// hit 32 different LDS banks
+__device__ __forceinline__ int pslot(int k) { return k + (k >> 5); }
+
+__global__ __launch_bounds__(PT) void prio_draw_kernel(mdq_replay_prio_draw_desc D) {
+  __shared__ double seg[PT + PT / 32];   // sum of every segment; then E[k]: sum of everything in front of segment k
+  __shared__ double grp[32];
+  __shared__ double total_s;
+  __shared__ int lastpos[PT];
+  __shared__ float pmin[PT];
+  const int tid = threadIdx.x, cap = D.capacity, n = D.n;
+  const float* __restrict__ prio = D.prio;
+  // segment k = records [k L, (k + 1) L): the order of every sum below is a function of the capacity alone
+  const long long L = ((long long)cap + PT - 1) / PT;
+  {
+    const int j0 = (int)min(tid * L, (long long)cap), j1 = (int)min((tid + 1) * L, (long long)cap);
+    double s = 0.0;
+    int lp = -1;
+    for (int j = j0; j < j1; ++j) {
+      const float p = prio[j];
+      s += (double)p;
+      if (p > 0.f) lp = j;
+    }
+    seg[pslot(tid)] = s;
+    lastpos[tid] = lp;
+  }
+  __syncthreads();
+  if (tid < 32) {   // 32 groups of 32 segments, every sum serial in index order
+    double g = 0.0;
+    for (int m = 0; m < 32; ++m) g += seg[pslot(tid * 32 + m)];
+    grp[tid] = g;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double a = 0.0;
+    for (int g = 0; g < 32; ++g) {
+      const double v = grp[g];
+      grp[g] = a;
+      a += v;
+    }
+    total_s = a;
+  }
+  __syncthreads();
+  if (tid < 32) {
+    const double G = grp[tid];
+    double part = 0.0;
+    for (int m = 0; m < 32; ++m) {
+      const int sl = pslot(tid * 32 + m);
+      const double v = seg[sl];
+      seg[sl] = G + part;   // non-decreasing in k: sums of non-negative terms, each rounded monotonically
+      part += v;
+    }
+  }
+  for (int off = PT / 2; off > 0; off >>= 1) {   // the last record with a priority
+    __syncthreads();
+    if (tid < off) lastpos[tid] = max(lastpos[tid], lastpos[tid + off]);
+  }
+  __syncthreads();
+  const double total = total_s;
+  const bool live = tid < n && total > 0.0;
+  int my = 0;
+  float pv = 0.f;
+  if (live) {
+    const double t = total * (((double)tid + D.u[tid]) / (double)n);
+    int lo = 0, hi = PT - 1;   // the last segment that starts at or below t (E[0] = 0)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (seg[pslot(mid)] <= t)
+        lo = mid;
+      else
+        hi = mid - 1;
+    }
+    // inclusive prefix of record j of segment k = E[k] + (sum of the segment up to j); the walk goes on into the next
+    // segments where rounding left every prefix of this one at or below t
+    int found = -1;
+    for (int k = lo; k < PT && found < 0; ++k) {
+      const long long a0 = k * L;
+      if (a0 >= cap) break;
+      const int j1 = (int)min(a0 + L, (long long)cap);
+      const double E = seg[pslot(k)];
+      double loc = 0.0;
+      for (int j = (int)a0; j < j1; ++j) {
+        const float p = prio[j];
+        loc += (double)p;
+        if (p > 0.f && E + loc > t) {
+          found = j;
+          break;
+        }
+      }
+    }
+    my = found >= 0 ? found : lastpos[0];   // (i + u) / n rounded to 1: the last record with a priority
+    pv = prio[my];
+  }
+  pmin[tid] = live ? pv : INFINITY;
+  for (int off = PT / 2; off > 0; off >>= 1) {
+    __syncthreads();
+    if (tid < off) pmin[tid] = fminf(pmin[tid], pmin[tid + off]);
+  }
+  __syncthreads();
+  if (tid < n) {
+    D.idx[tid] = my;
+    D.weight[tid] = live ? (float)pow((double)pmin[0] / (double)pv, D.beta) : 0.f;
+  }
+  if (tid == 0 && D.total) D.total[0] = total;
+}
+
+__global__ __launch_bounds__(PT) void prio_update_kernel(float* prio, int capacity, int n, const int32_t* idx, const float* td,
+                                                          double alpha, double eps, float* pmax) {
+  __shared__ int sidx[PT];
+  __shared__ float sval[PT];
+  const int tid = threadIdx.x;
+  int id = -1;      // < 0: nothing to write (no draw i, record number out of range, TD error not finite)
+  float v = 0.f;
+  if (tid < n) {
+    const int j = idx[tid];
+    const float d = td[tid];
+    if (j >= 0 && j < capacity && isfinite(d)) {
+      id = j;
+      v = (float)pow(fabs((double)d) + eps, alpha);
+    }
+  }
+  sidx[tid] = id;
+  sval[tid] = v;
+  __syncthreads();
+  bool win = id >= 0;   // among the draws of one record the last one writes
+  for (int k = tid + 1; k < n && win; ++k) win = sidx[k] != id;
+  if (win) prio[id] = v;
+  for (int off = blockDim.x / 2; off > 0; off >>= 1) {
+    __syncthreads();
+    if (tid < off) sval[tid] = fmaxf(sval[tid], sval[tid + off]);
+  }
+  if (tid == 0) *pmax = fmaxf(*pmax, sval[0]);
+}
+
+}  // namespace mdq_replay
+
+extern "C" int mdq_replay_prio_fill(float* prio, int32_t capacity, int32_t base_new, int32_t n_new, int32_t base_zero,
+                                    int32_t n_zero, const float* pmax, void* stream) {
+  if (!prio || !pmax || capacity <= 0 || n_new < 0 || n_zero < 0) return mdq_set_error("mdq_replay_prio_fill: bad arguments");
+  if (n_new > capacity || n_zero > capacity || (n_new > 0 && (base_new < 0 || base_new >= capacity)) ||
+      (n_zero > 0 && (base_zero < 0 || base_zero >= capacity)))
+    return mdq_set_error("mdq_replay_prio_fill: a range exceeds the capacity");
+  if (n_new > 0 && n_zero > 0) {   // circular ranges overlap iff one's first record lies inside the other
+    const long long dz = ((long long)base_zero - base_new + capacity) % capacity, dn = ((long long)base_new - base_zero + capacity) % capacity;
+    if (dz < n_new || dn < n_zero) return mdq_set_error("mdq_replay_prio_fill: the two ranges overlap");
+  }
+  const long long m = (long long)n_new + n_zero;
+  if (m == 0) return 0;
+  hipLaunchKernelGGL(mdq_replay::prio_fill_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, prio,
+                     capacity, base_new, n_new, base_zero, n_zero, pmax);
+  if (hipGetLastError() != hipSuccess) return mdq_set_error("prio_fill_kernel launch failed");
+  return 0;
+}
+
+extern "C" int mdq_replay_prio_draw(const mdq_replay_prio_draw_desc* d, void* stream) {
+  if (!d || d->capacity <= 0 || d->n < 1 || d->n > mdq_replay::PT || !(d->beta >= 0.0) || !d->prio || !d->u || !d->idx || !d->weight)
+    return mdq_set_error("mdq_replay_prio_draw: bad arguments");
+  hipLaunchKernelGGL(mdq_replay::prio_draw_kernel, dim3(1), dim3(mdq_replay::PT), 0, (hipStream_t)stream, *d);
+  if (hipGetLastError() != hipSuccess) return mdq_set_error("prio_draw_kernel launch failed");
+  return 0;
+}
+
+extern "C" int mdq_replay_prio_update(float* prio, int32_t capacity, int32_t n, const int32_t* idx, const float* td, double alpha,
+                                      double eps, float* pmax, void* stream) {
+  if (!prio || !pmax || !idx || !td || capacity <= 0 || n < 1 || n > mdq_replay::PT || !(alpha >= 0.0) || !(eps >= 0.0))
+    return mdq_set_error("mdq_replay_prio_update: bad arguments");
+  int threads = 64;
+  while (threads < n) threads <<= 1;
+  hipLaunchKernelGGL(mdq_replay::prio_update_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream, prio, capacity, n, idx, td,
+                     alpha, eps, pmax);
+  if (hipGetLastError() != hipSuccess) return mdq_set_error("prio_update_kernel launch failed");
   return 0;
 }
 

@@ -158,13 +158,15 @@ class FusedGcn:
         self._version = version
 
     def train_step(self, x, node_ptr, esrc, edst, edge_ptr, nmax, emax, mode, q_other, action, reward, nonfinal, gamma,
-                   loss_out=None, want_out=False, stream=None):
+                   loss_out=None, want_out=False, stream=None, weight=None, td_out=None):
         """Forward + double-DQN Huber loss + backward of the module over a minibatch on the hand-written kernels
         (`mdq_gcn_train_step`, no autograd): returns (loss (1,) tensor, flat gradient over ALL parameters in
         `parameters()` order [, head outputs (B, out)]).  The returned tensors are persistent buffers that the next call
         overwrites.  mode 0: this network evaluates the states, `q_other` the next states; mode 1 the other way
         round (the reference's `select` toggle, airfoil_dqn.py:240-310).  `loss_out`: a (1,) float32 device tensor to
-        receive the loss instead of the internal one (e.g. a slot of a log ring: no copy, no synchronisation)."""
+        receive the loss instead of the internal one (e.g. a slot of a log ring: no copy, no synchronisation).
+        `weight` / `td_out` ((B,) float32 device tensors, either may be None: `mdq_gcn_train_step_weighted`): importance
+        weight of every graph's loss term (prioritized replay) / receives every graph's TD error."""
         self._pack(stream)
         d = self.desc
         dev = x.device
@@ -191,6 +193,9 @@ class FusedGcn:
             raise ValueError("train_step: minibatch arrays of different lengths")
         if x.shape[0] > B * int(nmax):
             raise ValueError(f"{x.shape[0]} nodes in {B} graphs exceed nmax {int(nmax)}")
+        for t in (weight, td_out):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != B):
+                raise ValueError(f"train_step wants weight / td_out as contiguous float32 tensors of {B} entries on {dev}")
         loss = bufs["loss"] if loss_out is None else loss_out
         t = GcnTrainDesc()
         t.B, t.NMAX, t.EMAX, t.mode, t.gamma = B, int(nmax), max(int(emax), 1), int(mode), float(gamma)
@@ -199,7 +204,12 @@ class FusedGcn:
         t.workspace, t.partial, t.grad, t.loss = bufs["ws"].data_ptr(), bufs["partial"].data_ptr(), bufs["grad"].data_ptr(), loss.data_ptr()
         t.out = bufs["out"].data_ptr() if want_out else None
         t.layout = self.layout
-        _lib.check(self.lib.mdq_gcn_train_step(C.byref(d), C.byref(t), _lib.stream_ptr(stream)), "mdq_gcn_train_step")
+        if weight is None and td_out is None:
+            _lib.check(self.lib.mdq_gcn_train_step(C.byref(d), C.byref(t), _lib.stream_ptr(stream)), "mdq_gcn_train_step")
+        else:
+            _lib.check(self.lib.mdq_gcn_train_step_weighted(
+                C.byref(d), C.byref(t), None if weight is None else weight.data_ptr(),
+                None if td_out is None else td_out.data_ptr(), _lib.stream_ptr(stream)), "mdq_gcn_train_step_weighted")
         return (loss, bufs["grad"]) + ((bufs["out"],) if want_out else ())
 
     @torch.no_grad()

@@ -2,6 +2,7 @@
 `Transition`s, batched states stored once on the GPU, and a device ring of fixed-size records (see the classes)."""
 from __future__ import annotations
 
+import ctypes as C
 import random
 from collections import namedtuple
 from typing import List
@@ -117,7 +118,12 @@ class SharedDeviceReplay:
     `DeviceBatch` interface as `DeviceReplay` (minibatch arrays gathered by a few torch ops, nothing read back).
 
     The device loop (`grouped`) writes G groups of W records, one per batched step t (`steps_pushed` so far, over all its
-    calls): group t % G is being written during step t - its records get s' one step later -, the others are finished."""
+    calls): group t % G is being written during step t - its records get s' one step later -, the others are finished.
+
+    Prioritized replay (`prio_fill` / `prio_draw` / `prio_update`: the three `mdq_replay_prio_*` kernels on the current
+    stream): the ring owns `prio` (capacity,) - (|td| + eps)^alpha of every record, 0 for a record that must not be drawn -
+    and `pmax` (1,), the largest priority seen so far, started at 1; both are allocated on first use and, like the ring
+    itself, are not part of a checkpoint."""
 
     def __init__(self, capacity: int, N: int, F: int, e_max: int, device):
         self.capacity, self.N, self.F, self.e_max, self.device = int(capacity), int(N), int(F), int(e_max), device
@@ -126,6 +132,7 @@ class SharedDeviceReplay:
         self.position, self.count = 0, 0
         self.W, self.G, self.steps_pushed = 1, self.capacity, 0
         self._cols = torch.arange(e_max, device=device)[None, :]
+        self.prio = self.pmax = self._draw_desc = None
 
     @classmethod
     def grouped(cls, old, replay_capacity: int, W: int, N: int, F: int, e_max: int, device) -> "SharedDeviceReplay":
@@ -162,6 +169,49 @@ class SharedDeviceReplay:
     def close(self, t: int):
         """After the last step of a loop call (t steps pushed in all, the last one's records finished as well)."""
         self.steps_pushed, self.count, self.position = t, min(t, self.G) * self.W, self.group_base(t)
+
+    # --- proportional prioritized replay ----------------------------------------------------------------------
+    def _prio(self):
+        if self.prio is None:
+            self.prio = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+            self.pmax = torch.ones(1, dtype=torch.float32, device=self.device)
+        return self.prio
+
+    def prio_ranges(self, t: int, new: bool = True, zero: bool = True):
+        """(base_new, n_new, base_zero, n_zero) of `prio_fill(t)`."""
+        n_new = self.W if (new and t > 0) else 0
+        return (self.group_base(t - 1) if n_new else 0, n_new, self.group_base(t) if zero else 0, self.W if zero else 0)
+
+    def prio_fill(self, t: int, new: bool = True, zero: bool = True):
+        """In front of the minibatches of step t: the group of step t - 1, whose records have just received their next
+        states, gets the largest priority so far (`new`; False where that step belongs to an earlier call, which has
+        done it), the group step t writes gets 0 (`zero`; False after the last step of a call - `close` -, which writes
+        no further group)."""
+        bn, nn, bz, nz = self.prio_ranges(t, new, zero)
+        _lib.check(_lib.load().mdq_replay_prio_fill(self._prio().data_ptr(), self.capacity, bn, nn, bz, nz, self.pmax.data_ptr(),
+                                                    _lib.stream_ptr()), "mdq_replay_prio_fill")
+
+    def prio_draw(self, u: torch.Tensor, beta: float, idx_out: torch.Tensor, w_out: torch.Tensor):
+        """One stratified minibatch: `u` (n,) float64 uniforms on the device -> record numbers `idx_out` (n,) int32 and
+        importance weights `w_out` (n,) float32 (both device, written in place)."""
+        n = u.numel()
+        for t_, dt in ((u, torch.float64), (idx_out, torch.int32), (w_out, torch.float32)):
+            if t_.dtype != dt or t_.device.type != "cuda" or not t_.is_contiguous() or t_.numel() != n:
+                raise ValueError(f"prio_draw wants contiguous device tensors of {n} entries: u float64, idx int32, weight float32")
+        d = self._draw_desc = self._draw_desc or _lib.ReplayPrioDrawDesc()
+        d.capacity, d.n, d.beta, d.prio = self.capacity, n, float(beta), self._prio().data_ptr()
+        d.u, d.idx, d.weight = u.data_ptr(), idx_out.data_ptr(), w_out.data_ptr()
+        _lib.check(_lib.load().mdq_replay_prio_draw(C.byref(d), _lib.stream_ptr()), "mdq_replay_prio_draw")
+
+    def prio_update(self, idx: torch.Tensor, td: torch.Tensor, alpha: float, eps: float):
+        """New priorities (|td| + eps)^alpha of the records `idx` (n,) int32 from their TD errors `td` (n,) float32."""
+        n = idx.numel()
+        if (idx.dtype != torch.int32 or td.dtype != torch.float32 or td.numel() != n or not idx.is_contiguous() or
+                not td.is_contiguous() or idx.device.type != "cuda" or td.device.type != "cuda"):
+            raise ValueError("prio_update wants contiguous device tensors: idx int32, td float32, of one length")
+        _lib.check(_lib.load().mdq_replay_prio_update(self._prio().data_ptr(), self.capacity, n, idx.data_ptr(), td.data_ptr(),
+                                                      float(alpha), float(eps), self.pmax.data_ptr(), _lib.stream_ptr()),
+                   "mdq_replay_prio_update")
 
     def push_records(self, rec: torch.Tensor):
         m = rec.shape[0]

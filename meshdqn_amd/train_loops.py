@@ -72,6 +72,14 @@ class TrainingLog:
             np.save(self.base + "airfoil.npy", np.array(self.airfoils, dtype=np.int64))
 
 
+def _refuse_prioritized(trainer, loop: str):
+    """Prioritized replay draws with priorities that change with every optimiser step: only the device loop, whose draw is a
+    kernel of the optimiser chain, offers it."""
+    if trainer.prioritized is not None:
+        raise ValueError(f"{loop} samples its replay uniformly on the host: a trainer with prioritized replay "
+                         "(DQNTrainer(prioritized=...)) needs train_loop_device")
+
+
 def _draw_epsilon(steps_done, n_actions: int, eps_start, eps_end, eps_decay):
     """Host random numbers of one batched step (both batched loops): epsilon per env, who explores, the random actions."""
     eps = eps_end + (eps_start - eps_end) * np.exp(-1.0 * steps_done / eps_decay)
@@ -107,6 +115,7 @@ def train_loop_per_worker(trainer: DQNTrainer, env_factory, num_episodes: int, m
     With more than one rank every step issues collectives (the gradient all-reduce of `optimize`, the transition
     all-gather), so all ranks must take the SAME number of steps: episode lengths differ between ranks (per-rank
     seeds), hence the loop must be bounded by `max_steps` (episodes are then cut at that common step count)."""
+    _refuse_prioritized(trainer, "train_loop_per_worker")
     ctx = trainer.ctx
     if ctx.world > 1 and max_steps is None:
         raise ValueError("train_loop_per_worker with more than one rank needs max_steps (a step count common to all "
@@ -165,6 +174,7 @@ def train_loop_vec(trainer: DQNTrainer, venv, num_steps: int, optim_per_step: in
     reset in place by the vector env.  `steps_done0` continues the per-environment epsilon counters of an earlier run;
     `on_every(step, steps_done)` is called after every `every`-th batched step (periodic checkpoints / log writes).
     Returns dict(rewards (num_steps,B), dones, losses, steps_done)."""
+    _refuse_prioritized(trainer, "train_loop_vec")
     ctx = trainer.ctx
     B, N = venv.B, venv.N
     fused = FusedGcn(trainer.policy_net_1)
@@ -260,7 +270,7 @@ def train_loop_vec(trainer: DQNTrainer, venv, num_steps: int, optim_per_step: in
 
 def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step: int = 1, eps_decay=10000, eps_start=1.0,
                       eps_end=0.01, share_replay=False, log: Optional["TrainingLog"] = None, steps_done0=None, every: int = 0,
-                      on_every=None, chunk: int = 64, optimiser_stream: str = "auto"):
+                      on_every=None, chunk: int = 64, optimiser_stream: str = "auto", per_trace: bool = False):
     """`train_loop_vec` WITHOUT a host round trip inside a batched step (one rank of configs[3]): the environment step is
     `VecEnv2DAirfoil.rollout_step` (Q-forward, epsilon-greedy choice, vertex removal ... reward / reset logic as kernels),
     the B transitions go into the record ring with one launch (`mdq_replay_step`; with `share_replay` the ranks
@@ -269,9 +279,22 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
     latency-bound smoothing kernel of the same env step (`optimiser_stream`: the env's flow stream, behind the flow
     leg of the previous step, or a stream of its own).  The host only draws the random numbers (same streams as
     `train_loop_vec`: numpy for epsilon-greedy, `random.sample` for the minibatch) and enqueues; rewards / dones /
-    losses are read back once per `chunk` steps.  Same returns as `train_loop_vec`."""
+    losses are read back once per `chunk` steps.  Same returns as `train_loop_vec`.
+
+    With a prioritized trainer (`DQNTrainer(prioritized=...)`) the minibatches are drawn ON THE DEVICE, because the
+    priorities change with every optimiser step: the host uploads one table of uniforms per chunk (`random.random()`, one per
+    draw) instead of record numbers, and the optimiser chain of step t becomes `prio_fill` (the group that just got its next
+    states: largest priority so far; the group being written: 0), the all-gather, and per optimiser step `prio_draw` ->
+    `optimize_device` with the drawn device indices and importance weights -> `prio_update` from the TD errors.  All of it on
+    the optimiser stream: the main chain gains no launch and no event.  Over several ranks with `share_replay` the ring
+    stays identical on all ranks; the priorities are rank-local (every rank learns from its own minibatch, the gradient is
+    all-reduced as before).  `per_trace=True` adds out["per"]: `u`, `idx`, `weight`, `td` (minibatches, batch) and `beta`
+    (minibatches,) of every minibatch of the call, in order, read back with the losses at the chunk boundaries."""
     ctx = trainer.ctx
     dev = ctx.device
+    per = trainer.prioritized
+    if per_trace and per is None:
+        raise ValueError("per_trace needs a trainer with prioritized replay")
     if dev.type != "cuda" or not venv.gpu_remesh or not venv.auto_reset:
         raise MeshDQNHipError("train_loop_device needs a GPU and a vector env with the device mesh engine and auto_reset")
     B, N = venv.B, venv.N
@@ -288,7 +311,7 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
             out = train_loop_device(trainer, venv, num_steps, optim_per_step=optim_per_step, eps_decay=eps_decay,
                                     eps_start=eps_start, eps_end=eps_end, share_replay=share_replay, log=log,
                                     steps_done0=steps_done0, every=every, on_every=on_every, chunk=chunk,
-                                    optimiser_stream=optimiser_stream)
+                                    optimiser_stream=optimiser_stream, per_trace=per_trace)
         main.wait_stream(trainer._main_stream)
         return out
     if venv.flow_overlap and not same_stream(venv._calibrated_for, main):
@@ -309,6 +332,7 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
             trainer.calibrate_opt_stream(venv, fused1)    # (an optimiser stream that really overlaps; resets the envs)
         opt_stream = trainer._opt_stream
     ev_opt = rep = None
+    trace = dict(u=[], idx=[], weight=[], td=[], beta=[])
     rewards, dones_hist, actions_hist = [], [], []
     episodes = _EpisodeLog(log, venv)
     step_no, prev = 0, None      # prev: (record base, act, rew, done) of the step whose records await their next state
@@ -328,10 +352,20 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
                                                                      st["x"].shape[2], trainer.e_max, dev)
             t0 = rep.steps_pushed                               # the ring continues where an earlier call stopped
             loss_ring = torch.zeros(int(chunk) * max(1, optim_per_step), dtype=torch.float32, device=dev)
+            if per is not None:     # what the draw and the learning step hand each other, a row per minibatch of a chunk
+                shape = (loss_ring.numel(), trainer.batch_size)
+                per_idx = torch.zeros(shape, dtype=torch.int32, device=dev)
+                per_w, per_td = torch.zeros(shape, device=dev), torch.zeros(shape, device=dev)
         # minibatches of the chunk: the number of finished records at every step is known in advance; one upload
-        mbs = [rep.draw(t, trainer.batch_size) for t in range(t0 + step_no, t0 + step_no + K)
-               for _k in range(optim_per_step if rep.finished(t) >= trainer.batch_size else 0)]
-        mb_dev = torch.from_numpy(np.stack(mbs)).to(dev) if mbs else None
+        if per is None:
+            mbs = [rep.draw(t, trainer.batch_size) for t in range(t0 + step_no, t0 + step_no + K)
+                   for _k in range(optim_per_step if rep.finished(t) >= trainer.batch_size else 0)]
+            mb_dev = torch.from_numpy(np.stack(mbs)).to(dev) if mbs else None
+        else:                       # ... of the uniforms of every draw
+            n_mb = sum(optim_per_step for t in range(t0 + step_no, t0 + step_no + K) if rep.finished(t) >= trainer.batch_size)
+            u_host = np.array([random.random() for _ in range(n_mb * trainer.batch_size)], np.float64).reshape(n_mb, trainer.batch_size)
+            u_dev = torch.from_numpy(u_host).to(dev) if n_mb else None
+            betas = []
         n_loss = 0
         for k in range(K):
             t = t0 + step_no + k
@@ -347,15 +381,24 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
             ev.record(main)
             gather = prev is not None and W != B               # shared replay: everybody's finished records of that step
             do_opt = rep.finished(t) >= trainer.batch_size
-            if gather or do_opt:
+            if gather or do_opt or per is not None:
                 with torch.cuda.stream(opt_stream):
                     opt_stream.wait_event(ev)
+                    if per is not None:
+                        rep.prio_fill(t, new=prev is not None)     # every step, also before the ring holds a minibatch
                     if gather:
                         # on the optimiser stream, in front of the chain that may sample those records, in place in the ring
                         # (rank r's B records sit at group base + r * B on every rank): off the latency chain of the env step
                         allgather_records_into(ctx, rep.R, prev[0], B, W)
                     for _k in range(optim_per_step if do_opt else 0):
-                        trainer.optimize_device(rep, mb_dev[n_loss], loss_out=loss_ring[n_loss:n_loss + 1])
+                        if per is None:
+                            trainer.optimize_device(rep, mb_dev[n_loss], loss_out=loss_ring[n_loss:n_loss + 1])
+                        else:
+                            betas.append(trainer.beta())
+                            rep.prio_draw(u_dev[n_loss], betas[-1], per_idx[n_loss], per_w[n_loss])
+                            trainer.optimize_device(rep, per_idx[n_loss], loss_out=loss_ring[n_loss:n_loss + 1],
+                                                    weight=per_w[n_loss], td_out=per_td[n_loss])
+                            rep.prio_update(per_idx[n_loss], per_td[n_loss], per["alpha"], per["eps"])
                         n_loss += 1
                     ev_opt = torch.cuda.Event()
                     ev_opt.record(opt_stream)
@@ -368,12 +411,25 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
                 if ev_opt is not None:
                     main.wait_event(ev_opt)
                 allgather_records_into(ctx, rep.R, prev[0], B, W)
+            if per is not None:     # the last step's records are finished too: their priorities, on the optimiser stream
+                ev = torch.cuda.Event()
+                ev.record(main)
+                with torch.cuda.stream(opt_stream):
+                    opt_stream.wait_event(ev)
+                    rep.prio_fill(t0 + num_steps, zero=False)
+                    ev_opt = torch.cuda.Event()
+                    ev_opt.record(opt_stream)
             rep.close(t0 + num_steps)
         out = venv.rollout_end(ro)                              # the one synchronisation of the chunk
         if ev_opt is not None:
             ev_opt.synchronize()                                # (the last optimiser chain writes its loss on the side stream)
         new_losses = loss_ring[:n_loss].cpu().numpy().tolist()
         trainer.losses.extend(new_losses)
+        if per_trace:
+            trace["u"].append(u_host[:n_loss])
+            for key, ring in (("idx", per_idx), ("weight", per_w), ("td", per_td)):
+                trace[key].append(ring[:n_loss].cpu().numpy())
+            trace["beta"].append(np.asarray(betas[:n_loss], np.float64))
         for k in range(K):
             rew, done = out["rewards"][k], out["dones"][k]
             rewards.append(rew.copy())
@@ -386,5 +442,8 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
         step_no += K
         if every and on_every is not None and (step_no // every) > ((step_no - K) // every):
             on_every(step_no, steps_done)
-    return dict(rewards=np.array(rewards), dones=np.array(dones_hist), losses=list(trainer.losses), steps_done=steps_done,
-                actions=np.array(actions_hist))
+    out = dict(rewards=np.array(rewards), dones=np.array(dones_hist), losses=list(trainer.losses), steps_done=steps_done,
+               actions=np.array(actions_hist))
+    if per_trace:
+        out["per"] = {key: np.concatenate(v) if v else np.zeros(0) for key, v in trace.items()}
+    return out

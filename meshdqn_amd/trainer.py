@@ -40,7 +40,8 @@ from .train_loops import TrainingLog, epsilon_threshold, train_loop_device, trai
 class DQNTrainer:
     def __init__(self, n_actions: int, num_inputs: int, ctx: Optional[DistContext] = None, lr=1e-5, weight_decay=1e-6,
                  batch_size=32, gamma=1.0, target_update=50, replay_capacity=10000, conv_width=128, topk=0.1,
-                 seed=1370, dense: bool = True, e_max: int = 1536):
+                 seed=1370, dense: bool = True, e_max: int = 1536, prioritized: Optional[dict] = None):
+        self.prioritized = self._check_prioritized(prioritized, batch_size)
         self.ctx = ctx or DistContext()
         self.dense, self.e_max = bool(dense), int(e_max)   # static-shape autograd path for equal-sized graphs
         dev = self.ctx.device
@@ -72,6 +73,44 @@ class DQNTrainer:
         self.opt_calibration_ms: List[float] = []
         random.seed(seed + self.ctx.rank)
         np.random.seed(seed + self.ctx.rank)
+
+    # --- prioritized replay (Schaul et al. 2016, proportional variant; `train_loop_device` only) ----------------
+    PRIORITIZED_DEFAULTS = dict(alpha=0.6, beta0=0.4, beta_steps=100000, eps=1e-6)
+
+    @classmethod
+    def _check_prioritized(cls, prioritized, batch_size) -> Optional[dict]:
+        """None, or the complete option dict: record i is drawn with probability p_i / sum p, p_i = (|td_i| + eps)^alpha;
+        its loss term carries the importance weight (N p_i / sum p)^-beta over the largest one of the minibatch."""
+        if prioritized is None:
+            return None
+        opt = dict(cls.PRIORITIZED_DEFAULTS)
+        if not isinstance(prioritized, dict):
+            raise ValueError("prioritized: None or a dict with any of " + ", ".join(opt))
+        unknown = sorted(set(prioritized) - set(opt))
+        if unknown:
+            raise ValueError(f"prioritized: unknown option(s) {unknown}; known: " + ", ".join(opt))
+        opt.update(prioritized)
+        opt = dict(alpha=float(opt["alpha"]), beta0=float(opt["beta0"]), beta_steps=float(opt["beta_steps"]), eps=float(opt["eps"]))
+        if not 0.0 <= opt["alpha"] <= 1.0:
+            raise ValueError(f"prioritized: alpha {opt['alpha']} outside [0, 1]")
+        if not 0.0 < opt["beta0"] <= 1.0:
+            raise ValueError(f"prioritized: beta0 {opt['beta0']} outside (0, 1]")
+        if not opt["beta_steps"] > 0:
+            raise ValueError(f"prioritized: beta_steps {opt['beta_steps']} must be positive")
+        if not (opt["eps"] > 0 and np.isfinite(opt["eps"])):
+            raise ValueError(f"prioritized: eps {opt['eps']} must be positive")
+        if int(batch_size) > 1024:
+            raise ValueError(f"prioritized: batch_size {batch_size} exceeds the 1024 draws of mdq_replay_prio_draw")
+        return opt
+
+    def beta(self, g: Optional[int] = None) -> float:
+        """Importance-weight exponent after g gradient applications (`num_grads`, which is checkpointed: a restart
+        continues the schedule): linear from beta0 to 1 over beta_steps."""
+        o = self.prioritized
+        if o is None:
+            raise ValueError("beta: the trainer was built without prioritized replay")
+        g = self.num_grads if g is None else g
+        return min(1.0, o["beta0"] + (1.0 - o["beta0"]) * g / o["beta_steps"])
 
     # --- acting -------------------------------------------------------------
     @torch.no_grad()
@@ -407,13 +446,15 @@ class DQNTrainer:
         venv.reset_all()
         return self.opt_calibration_ms
 
-    def optimize_device(self, rep: "SharedDeviceReplay", idx, loss_out: Optional[torch.Tensor] = None):
+    def optimize_device(self, rep: "SharedDeviceReplay", idx, loss_out: Optional[torch.Tensor] = None,
+                        weight: Optional[torch.Tensor] = None, td_out: Optional[torch.Tensor] = None):
         """One optimiser step on a minibatch of the record ring WITHOUT host synchronisation and without autograd:
         `mdq_replay_sample` (records `idx` -> graph arrays), fused forward of the network without gradient,
         `mdq_gcn_train_step` of the other one (forward + double-DQN Huber loss + backward), ONE flat all-reduce over the
         ranks, `mdq_adam_step`.  Everything is enqueued on the current stream; the loss goes to `loss_out` (a (1,)
         device tensor, e.g. a slot of a log ring) and is also returned as a device tensor.  Same `select` toggling as
-        `optimize` (airfoil_dqn.py:315-340 + :184-200 + :240-310)."""
+        `optimize` (airfoil_dqn.py:315-340 + :184-200 + :240-310).  `weight` / `td_out`: (batch,) float32 device tensors
+        handed through to the learning step (importance weights in, TD errors out: prioritized replay)."""
         dev = self.ctx.device
         if (self.num_grads % self.target_update) == 0:
             self.select = not self.select
@@ -449,7 +490,7 @@ class DQNTrainer:
         qo = self._fused_of(other, "train").forward_arrays(go["x"], b["node_ptr"], go["esrc"], go["edst"], go["edge_ptr"], N, EM)
         loss, flat = self._fused_of(net, "train").train_step(gd["x"], b["node_ptr"], gd["esrc"], gd["edst"], gd["edge_ptr"], N, EM,
                                                     0 if sel else 1, qo, b["action"], b["reward"], b["nonfinal"], self.gamma,
-                                                    loss_out=loss_out)
+                                                    loss_out=loss_out, weight=weight, td_out=td_out)
         if self.ctx.multi:
             self.ctx.allreduce_mean_(flat)
         self._adam_step_device(k, flat)

@@ -22,7 +22,19 @@ import numpy as np
 import yaml
 
 
-def main():
+def prioritized_options(flag: bool, cfg: dict):
+    """The `prioritized` argument of `DQNTrainer` from --prioritized-replay and the optional yaml block
+    `replay: {prioritized: true, alpha: 0.6, beta0: 0.4, beta_steps: 100000, eps: 1.0e-6}` (not a reference section: its
+    replay is uniform).  None: uniform replay; the flag alone: the defaults; the block's numbers hold with either switch."""
+    block = dict(cfg.get("replay") or {})
+    on = bool(block.pop("prioritized", False)) or bool(flag)
+    unknown = sorted(set(block) - {"alpha", "beta0", "beta_steps", "eps"})
+    if unknown:
+        raise SystemExit(f"replay: unknown key(s) {unknown} (known: prioritized, alpha, beta0, beta_steps, eps)")
+    return {k: float(v) for k, v in block.items()} if on else None
+
+
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True, action="append",
                     help="yaml config; repeat it to train ONE policy on several airfoils (their configs may differ only in the "
@@ -54,7 +66,15 @@ def main():
     ap.add_argument("--host-loop", action="store_true",
                     help="host-driven loop (train_loop_vec: autograd replayed as a HIP graph, one read-back per step) instead "
                          "of the device-resident one (train_loop_device: replay, sampling, forward + backward and Adam as kernels)")
-    args = ap.parse_args()
+    ap.add_argument("--prioritized-replay", action="store_true",
+                    help="proportional prioritized experience replay in the device-resident loop (draw, importance weights and "
+                         "priority update as kernels of the optimiser chain); its numbers come from the optional yaml block "
+                         "replay: {prioritized: true, alpha: 0.6, beta0: 0.4, beta_steps: 100000, eps: 1.0e-6}")
+    return ap
+
+
+def main():
+    args = parser().parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import importlib.util
         import sys
@@ -86,7 +106,8 @@ def main():
     trainer = DQNTrainer(n_actions=int(ap_["N_closest"]), num_inputs=2 + 3 * (int(ap_["solver_steps"]) // int(ap_["save_steps"])),
                          ctx=ctx, lr=float(opt.get("lr", 1e-5)), weight_decay=float(opt.get("weight_decay", 1e-6)),
                          batch_size=int(opt.get("batch_size", 32)), gamma=float(eps.get("gamma", 1.0)),
-                         target_update=int(ap_.get("target_update", 50)))
+                         target_update=int(ap_.get("target_update", 50)),
+                         prioritized=prioritized_options(args.prioritized_replay, cfg))
     # restart chain: restart n reads the checkpoint with n - 1 "restart_" prefixes and writes with n (every rank loads the
     # same files, so the replicas stay identical)
     restart_num, steps_done0 = 0, None
@@ -119,6 +140,8 @@ def main():
             log.write()                                          # reward / rewards / losses / actions / eps .npy
 
     device_loop = ctx.device.type == "cuda" and venv.gpu_remesh and not args.host_loop
+    if trainer.prioritized is not None and not device_loop:
+        raise SystemExit("prioritized replay needs the device-resident loop (a GPU, the device mesh engine, no --host-loop)")
     loop = train_loop_device if device_loop else train_loop_vec
     kw, every, on_every = {}, args.save_every, checkpoint
     if args.digest:
