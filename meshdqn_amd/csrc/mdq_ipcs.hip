@@ -1720,24 +1720,29 @@ __device__ inline int cg_pressure_reg(int n, const int32_t* sl_off, const int32_
 // the two fma chains in the same column order as before (adding 0 * p[row] for the padded slots).  (The Chebyshev
 // variant below keeps its rows in registers too but guards every gather with a branch on the slice width, which
 // serialises the round trips: that is why it never beat the LDS version.)  Needs n <= 2 * NTH and slices of at most RW
-// entries per row: returns -1 otherwise (the caller takes cg_pressure_reg).
-template <int NTH, int RW = 16>
-__device__ inline int cg_pressure_regm(int n, const int32_t* sl_off, const int32_t* sl_col, const double* A, double rtol,
-                                       int maxit, double* x, double* r, double* p, double* red, int& rsel) {
+// entries per row.
+//
+// RW is the number of register slots per row.  The solve is instantiated at 10, 12 and 16 and the caller
+// (cg_pressure_regm below) takes the smallest that holds the environment's widest slice: the P1 Laplacian of the lab
+// meshes has rows of at most 9 entries (SELL-64 slice widths 6-9), so at RW = 16 twelve to fourteen of the 32 gathers of an
+// application read the thread's own row and multiply it by zero.  The dropped slots have value 0 and sit behind every real
+// entry of the row: the fma chain ends with acc + 0 * p[row] = acc there, so every iterate, every reduction and the
+// iteration count are those of RW = 16, bit for bit.  The caller guarantees that every slice is at most RW wide.
+template <int NTH, int RW>
+__device__ inline int cg_pressure_regm_w(int n, const int32_t* sl_off, const int32_t* sl_col, const double* A, double rtol,
+                                         int maxit, double* x, double* r, double* p, double* red, int& rsel) {
   constexpr int NW = NTH / 64;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nsl = (n + 63) >> 6;
   int row[2];
   double av[2][RW];
   int co[2][RW];                      // byte offsets into the gathered vector
-  bool fits = true;
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int s_ = wave + NW * k;
     row[k] = (s_ << 6) + lane;
     const int base = s_ < nsl ? sl_off[s_] : 0;
     const int wid = s_ < nsl ? (sl_off[s_ + 1] - base) >> 6 : 0;
-    fits = fits && wid <= RW;
     const int self = min(row[k], n - 1);
 #pragma unroll
     for (int j = 0; j < RW; ++j) {
@@ -1746,14 +1751,6 @@ __device__ inline int cg_pressure_regm(int n, const int32_t* sl_off, const int32
       co[k][j] = 8 * (in ? sl_col[base + lane + j * 64] : self);
     }
   }
-  // workgroup-wide OR of `!fits` through the (still unused) search-direction vector (no static LDS in this kernel)
-  if (threadIdx.x == 0) p[NW] = 0.0;
-  __syncthreads();
-  if (!fits) p[NW] = 1.0;
-  __syncthreads();
-  const bool toowide = p[NW] != 0.0;
-  __syncthreads();
-  if (toowide) return -1;
   auto spmv = [&](const double* vec, double(&y)[2]) {
     const char* vb = reinterpret_cast<const char*>(vec);
     double g[2][RW];
@@ -1825,6 +1822,26 @@ __device__ inline int cg_pressure_regm(int n, const int32_t* sl_off, const int32
     if (row[k] < n) x[row[k]] = xv[k];
   __syncthreads();
   return it;
+}
+
+// cg_pressure_regm_w at the environment's width.  Every thread reads ALL slice offsets (at most 2 * NTH / 64 + 1 words,
+// the same addresses in every lane), so the widest slice - and with it the variant - is the same value in every thread of
+// the workgroup without a reduction: the barriers inside the variants are reached by all waves or by none.
+template <int NTH>
+__device__ inline int cg_pressure_regm(int n, const int32_t* sl_off, const int32_t* sl_col, const double* A, double rtol,
+                                       int maxit, double* x, double* r, double* p, double* red, int& rsel) {
+  const int nsl = (n + 63) >> 6;
+  int wmax = 0, o0 = sl_off[0];
+  for (int s_ = 0; s_ < nsl; ++s_) {
+    const int o1 = sl_off[s_ + 1];
+    wmax = max(wmax, (o1 - o0) >> 6);
+    o0 = o1;
+  }
+  wmax = __builtin_amdgcn_readfirstlane(wmax);
+  if (wmax <= 10) return cg_pressure_regm_w<NTH, 10>(n, sl_off, sl_col, A, rtol, maxit, x, r, p, red, rsel);
+  if (wmax <= 12) return cg_pressure_regm_w<NTH, 12>(n, sl_off, sl_col, A, rtol, maxit, x, r, p, red, rsel);
+  if (wmax <= 16) return cg_pressure_regm_w<NTH, 16>(n, sl_off, sl_col, A, rtol, maxit, x, r, p, red, rsel);
+  return -1;
 }
 
 // The same CG with the matrix rows of a thread in REGISTERS (values + column offsets of its two rows: they do not change

@@ -116,26 +116,32 @@ __device__ __forceinline__ double rcp_nr(double x) {
   return y;
 }
 
-// inclusive scan of data[0..SNV) in place (SWG threads, PER consecutive entries each; part = SWG ints of scratch)
+// inclusive scan of data[0..SNV) in place (the first SWG threads, PER consecutive entries each; part = SWG ints of
+// scratch).  A larger workgroup reaches the barriers with all its threads (smooth_env)
 __device__ __forceinline__ void scan_inclusive(int* data, int* part) {
   const int tid = threadIdx.x;
+  const bool act = tid < SWG;
   int loc[PER], run = 0;
+  if (act) {
 #pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    run += data[tid * PER + i];
-    loc[i] = run;
+    for (int i = 0; i < PER; ++i) {
+      run += data[tid * PER + i];
+      loc[i] = run;
+    }
+    part[tid] = run;
   }
-  part[tid] = run;
   __syncthreads();
   for (int off = 1; off < SWG; off <<= 1) {
-    const int add = tid >= off ? part[tid - off] : 0;
+    const int add = (act && tid >= off) ? part[tid - off] : 0;
     __syncthreads();
-    part[tid] += add;
+    if (act) part[tid] += add;
     __syncthreads();
   }
-  const int base = part[tid] - run;
+  if (act) {
+    const int base = part[tid] - run;
 #pragma unroll
-  for (int i = 0; i < PER; ++i) data[tid * PER + i] = base + loc[i];
+    for (int i = 0; i < PER; ++i) data[tid * PER + i] = base + loc[i];
+  }
   __syncthreads();
 }
 
@@ -178,10 +184,12 @@ __device__ __forceinline__ bool exact_update(const lds_u8* recb, const lds_i32* 
   return true;
 }
 
-// one environment (b) by the whole workgroup
+// one environment (b), `iters` sweeps, by the first SWG threads of the workgroup.  The workgroup may be larger (the
+// hand-back inside smooth_linear_kernel: 768 threads): all its threads must call, they reach every barrier - the control
+// flow around the barriers is uniform - and the threads behind the first SWG do nothing in between (their `tid` is beyond
+// every loop bound and every `tid <` test).  `lds`: LDS_BYTES, 16-byte aligned.
 __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int NV, int NT, double* coords, const int32_t* cells,
-                                           const int32_t* nv_, const int32_t* nt_, const int32_t* iters_, int cap,
-                                           long long* trace) {
+                                           const int32_t* nv_, const int32_t* nt_, const int iters, long long* trace) {
   unsigned char* recb = lds + OFF_REC;
   unsigned char* rows = lds + OFF_ROW;
   uint16_t* passtab = reinterpret_cast<uint16_t*>(lds + OFF_PT);
@@ -196,8 +204,7 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
   unsigned char* hwt = recb;   // scheduler scratch in the record area (the records are loaded behind the scheduler):
                                // per interior rank and cell the interior ranks of its higher-numbered vertices
   int* part = reinterpret_cast<int*>(lds + OFF_PART);
-  const int tid = threadIdx.x;
-  const int iters = cap > 0 ? min(iters_[b], cap) : iters_[b];   // (cap: only the first sweeps)
+  const int tid = threadIdx.x < SWG ? (int)threadIdx.x : 1 << 24;
   if (iters <= 0) return;
 #ifdef MDQ_SMOOTH_TRACE
   int phase_ = 0;   // setup phase stamps of environment 0 in the slots of sweep 63
@@ -738,7 +745,7 @@ __global__ __launch_bounds__(SWG) void smooth_kernel(int B, int NV, int NT, doub
     if (__builtin_amdgcn_ballot_w64(any) == 0ull) return;
   }
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    smooth_env(lds, b, NV, NT, coords, cells, nv_, nt_, iters_, cap, trace);
+    smooth_env(lds, b, NV, NT, coords, cells, nv_, nt_, cap > 0 ? min(iters_[b], cap) : iters_[b], trace);   // (cap: only the first sweeps)
     __syncthreads();
   }
 }

@@ -31,9 +31,9 @@
 // new.  The kernel starts in this CHECKED mode (solve, validate with all waves, repair) and switches to the PIPELINED mode
 // above after the first sweep that passes at the first try.
 //
-// mdq_smooth_fast (below) = this kernel -> mdq_smooth's kernel for the environments that were handed back (a mesh beyond
-// this kernel's limits - more than 16 cells at a vertex, 14 gather slots - or a sweep that did not settle within MAXROUNDS
-// repair rounds; normally none: it returns at once).
+// mdq_smooth_fast (below) = this kernel alone.  A mesh beyond its limits - more than 16 cells at a vertex, 14 gather slots,
+// 8 lower neighbours inside a block - is handed back to the careful walk of mdq_smooth.hip (smooth_env), which the
+// environment's workgroup runs in place of the blocked solve (normally none).
 #include <hip/hip_runtime.h>
 
 #include "../../include/meshdqn_hip.h"
@@ -73,14 +73,15 @@ constexpr int OFF_R2K = OFF_G + 2 * BS * 8;                  // 1 / (2 k)
 constexpr int OFF_MISC = OFF_R2K + 32 * 8;                   // [0] n_int  [1] bad / newly flagged  [2] eligible
 constexpr int OFF_FIXV = OFF_MISC + 64;                      // per vertex: takes the exact update in the sweep at hand
 constexpr int OFF_PART = OFF_FIXV + LNV + 16;
-constexpr int LDS_BYTES = OFF_PART + LWG * 4;
+constexpr int OFF_M01 = OFF_PART + LWG * 4;                  // the inverses of blocks 0 and 1 (every sweep starts from here)
+constexpr int LDS_BYTES = OFF_M01 + 2 * MBLK * 8;
 // setup scratch inside the position buffers (the positions are loaded last): per-vertex neighbour lists, then the rows of
 // the block inverses under construction
 constexpr int OFF_NB = OFF_CUR;                              // [LNV][MAXNB] u16: id | count << 10
 constexpr int OFF_TRI = OFF_CUR;                             // 8 waves x 528 doubles (packed lower triangles)
 constexpr int OFF_TMP = OFF_SROW;                            // cell lists in arrival order (before the rows are built)
 static_assert(LNV * MAXNB * 2 <= 3 * PBUF && TRW * 528 * 8 <= 3 * PBUF && 3 * LNT * 4 <= LNV * SROW, "setup scratch");
-static_assert(OFF_SROW % 16 == 0 && OFF_PTR % 16 == 0 && OFF_INC % 16 == 0 && OFF_G % 16 == 0 && OFF_R2K % 8 == 0, "LDS alignment");
+static_assert(OFF_SROW % 16 == 0 && OFF_PTR % 16 == 0 && OFF_INC % 16 == 0 && OFF_G % 16 == 0 && OFF_R2K % 8 == 0 && OFF_M01 % 16 == 0, "LDS alignment");
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -253,13 +254,27 @@ __device__ __forceinline__ void load_m(d2 (&M)[8], const d2* mg, int b, int i, i
 #endif
 }
 
+// the same rows from the copy of blocks 0 and 1 in LDS (OFF_M01: same layout as the workspace)
+__device__ __forceinline__ void load_m_lds(d2 (&M)[8], const unsigned char* lds, int b, int i, int h) {
+  const d2* p = reinterpret_cast<const d2*>(lds + OFF_M01) + ((b * 2 + h) * 8) * 32 + i;
+#pragma unroll
+  for (int t = 0; t < 8; ++t) M[t] = p[t * 32];
+}
+
+// One sweep of a solver wave.  The rows of M stream from the workspace through three register buffers, two blocks ahead
+// of the block step - except those of blocks 0 and 1, which nothing could prefetch: a sweep used to begin with a
+// workspace round trip (L2, with 128 CUs streaming) in front of its first block step, 50 times per launch.  The block
+// inverses do not change during a launch, so the set-up leaves a copy of blocks 0 and 1 in LDS and every sweep starts from
+// there.  (Carrying the rows across the sweep boundary in REGISTERS does not fit: the sweep sits at the 168 VGPRs of three
+// waves per SIMD, and 96 / 32 more registers live through it - blocks 0 and 1 in the rotation nb mod 3 leaves them in, or
+// block 0 alone - cost 280 / 136 B of scratch per lane.)  Same values, same order of arithmetic: bitwise the old sweep.
 template <int COMP>
 __device__ __forceinline__ void solve_sweep(unsigned char* lds, const d2* mg, int nb, int lane) {
   const int i = lane & 31, h = lane >> 5;
   const unsigned char* srow = lds + OFF_SROW + i * SROW + h * 16;
   d2 MA[8], MB[8], MC[8];
-  load_m(MA, mg, 0, i, h);
-  load_m(MB, mg, 1, i, h);
+  load_m_lds(MA, lds, 0, i, h);
+  load_m_lds(MB, lds, 1, i, h);
   u4 meta = *reinterpret_cast<const u4*>(srow);
   for (int b = 0; b < nb; b += 3) {
     u4 mnext = *reinterpret_cast<const u4*>(srow + (b + 1) * (BS * SROW));
@@ -577,9 +592,16 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
   __syncthreads();
   LT_STAMP(3)
   const bool eligible = misc[2] != 0 && n_int > 0;
-  if (!eligible) {                               // the careful walk takes all the sweeps
+  if (!eligible) {
+    // a mesh beyond the limits of the blocked solve: the careful per-vertex walk of mdq_smooth.hip takes all the sweeps,
+    // here and now - this workgroup owns a compute unit and its LDS, nothing of the set-up above is needed any more and
+    // `coords` has not been touched.  (It used to be a launch of its own behind this kernel: 4 us and a launch gap per
+    // call for - normally - nothing.)  The walk is written for 256 threads: the others only reach its barriers.
+    static_assert(mdq_smoothing::LDS_BYTES <= LDS_BYTES && mdq_smoothing::SNV == LNV && mdq_smoothing::SNT == LNT, "hand-back in place");
+    __syncthreads();
+    mdq_smoothing::smooth_env(lds, b, NV, NT, coords, cells, nv_, nt_, S, nullptr);
     if (tid == 0) {
-      redo[b] = S;
+      redo[b] = S;                               // (diagnostics: handed back, with all its sweeps)
       stats[3 * b] = stats[3 * b + 1] = stats[3 * b + 2] = 0;
     }
     return;
@@ -619,11 +641,13 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
       // write-out: lane = row i (both halves of the wave: columns 0..15 / 16..31), 16 bytes per store
       const int i = lane & 31, h = lane >> 5;
       d2* out = reinterpret_cast<d2*>(mg) + ((size_t)(blk * 2 + h) * 8) * 32 + i;
+      d2* out01 = reinterpret_cast<d2*>(lds + OFF_M01) + ((blk * 2 + h) * 8) * 32 + i;   // (blocks 0 and 1: the copy in LDS too)
       for (int t = 0; t < 8; ++t) {
         const int j0 = 16 * h + 2 * t;
         const double m0 = j0 <= i ? T[i * (i + 1) / 2 + j0] * (2.0 * r2ktab[kdeg[r0 + j0] & 0xFF]) : 0.0;
         const double m1 = j0 + 1 <= i ? T[i * (i + 1) / 2 + j0 + 1] * (2.0 * r2ktab[kdeg[r0 + j0 + 1] & 0xFF]) : 0.0;
         out[t * 32] = d2{m0, m1};
+        if (blk < 2) out01[t * 32] = d2{m0, m1};
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
@@ -793,20 +817,11 @@ static int smooth_fast_impl(const char* who, int32_t B, int32_t NV, int32_t NT, 
   double* mws = reinterpret_cast<double*>(workspace);
   int32_t* redo = reinterpret_cast<int32_t*>(mws + (int64_t)B * mstride);
   hipStream_t st = (hipStream_t)stream;
-  long long* trace = nullptr;
-#ifdef MDQ_SMOOTH_TRACE
-  trace = mdq_smooth_trace_host();
-#endif
-  // 1. every sweep as a blocked triangular solve: checked + repaired while limited steps occur, then validated in parallel
+  // every sweep as a blocked triangular solve: checked + repaired while limited steps occur, then validated in parallel.
+  // Environments beyond the kernel's limits (more than 16 cells at a vertex, 14 gather slots per row, 8 lower neighbours
+  // inside a block) are walked vertex by vertex by their own workgroup inside the same launch (redo[b] = their sweeps)
   hipLaunchKernelGGL(mdq_smooth_lin::smooth_linear_kernel, dim3(B), dim3(mdq_smooth_lin::LWG), 0, st, NV, NT, coords, cells, nv,
                      nt, iterations, rem, rstat, iters_env, mws, mstride, redo, redo + B);
-  // 2. environments handed back (meshes beyond the kernel's limits: more than 16 cells at a vertex, 14 gather slots per
-  //    row, 8 lower neighbours inside a block): the per-vertex walk, ONE workgroup over the - normally zero - environments
-  //    with sweeps left (128 workgroups of 141 KB LDS each would wait for the other streams' kernels to leave the CUs)
-  //    (four workgroups since round 4: a mesh family that hits the limits often would otherwise be walked one mesh after
-  //    the other by a single workgroup; they return at once when nothing was handed back)
-  hipLaunchKernelGGL(mdq_smoothing::smooth_kernel, dim3(B < 4 ? B : 4), dim3(mdq_smoothing::SWG), 0, st, B, NV, NT, coords, cells,
-                     nv, nt, redo, 0, trace);
   if (hipGetLastError() != hipSuccess) return mdq_set_error("mdq_smooth_fast: launch failed");
   return 0;
 }

@@ -886,7 +886,7 @@ class VecEnv2DAirfoil:
         is the new batched state and `ro["act"][k] / ro["rew"][k] / ro["done"][k]` (device) describe the step (k = ro["k"] - 1).
         `pack=False`: the Q-forward uses the packed parameter copy as it is (a learning loop whose optimiser runs on another
         stream brings it up to date itself, at a point that is ordered against the parameter writes).
-        Launches of a step (round 4: 8 + the hand-back launch of the smoothing, 14 in round 3): Q-forward (embedding, MLP head),
+        Launches of a step (8 - the smoothing hands back inside its own launch; 14 in round 3): Q-forward (embedding, MLP head),
         `mdq_remesh_act` (action decoding + vertex removal), `mdq_smooth_fast_env`, `mdq_env_topology`,
         `mdq_interpolate_snapshots`, `mdq_probe_forces`, `mdq_env_finish` (reward / terminal logic, hand-over of the meshes
         to the flow stream, in-place resets, node features of the next state)."""
