@@ -10,7 +10,7 @@
 //      x_B = M_B g_B,     M_B = (I - D_B^-1 L_BB)^-1 D_B^-1  (32 x 32, lower triangular, built ONCE per launch),
 //                         g_B = sum of the neighbour positions that are not lower-numbered members of the same block
 //                               (read from the in-place position array: new values for lower blocks, old ones otherwise),
-// so that a sweep is 22 dependent block steps (gather 7 positions per lane -> 32 x 32 mat-vec, 16 FMAs per lane) instead
+// so that a sweep is 22 dependent block steps (gather 4 or 7 positions per lane -> 32 x 32 mat-vec, 16 FMAs per lane) instead
 // of 119 passes (tools/chain_depth.py, tools/smooth_block_proto.py: contiguous index blocks form a pure chain, so there
 // is nothing to gain from more waves on the solve itself).  One wave per component solves; the rows of M_B a lane needs
 // stream from L2 (176 KB per mesh: they do not fit the LDS next to the positions) two blocks ahead.
@@ -36,6 +36,8 @@
 // environment's workgroup runs in place of the blocked solve (normally none).
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #include "../../include/meshdqn_hip.h"
 #include "mdq_internal.h"
 
@@ -51,6 +53,7 @@ constexpr int TRW = LWG / 64 < 11 ? LWG / 64 : 11;   // waves that build block i
 static_assert(LWG == 512 || LWG == 768, "workgroup shape");
 constexpr int BS = 32;             // rows per block
 constexpr int NSLOT = 14;          // gather slots per row (7 per lane half)
+constexpr int NNARROW = 4;         // slots per lane half a NARROW block step reads: no row of the block has more than 8
 constexpr int MAXNB = 16;          // neighbours / cells per vertex the setup handles (more: the mesh goes to the careful walk)
 constexpr int MAXLOW = 8;          // lower-numbered neighbours inside the own block
 constexpr int SROW = 32;           // bytes per solver row: [7 x u16 gather offsets, u16 store offset] x 2 halves
@@ -71,6 +74,7 @@ constexpr int OFF_KDEG = OFF_LMETA + LNV * MAXLOW;           // per rank: number
 constexpr int OFF_G = OFF_KDEG + LNV * 2;                    // g of the block in flight, per component
 constexpr int OFF_R2K = OFF_G + 2 * BS * 8;                  // 1 / (2 k)
 constexpr int OFF_MISC = OFF_R2K + 32 * 8;                   // [0] n_int  [1] bad / newly flagged  [2] eligible
+                                                             // [3] bit b: a row of block b has more than 2 x NNARROW gather slots
 constexpr int OFF_FIXV = OFF_MISC + 64;                      // per vertex: takes the exact update in the sweep at hand
 constexpr int OFF_PART = OFF_FIXV + LNV + 16;
 constexpr int OFF_M01 = OFF_PART + LWG * 4;                  // the inverses of blocks 0 and 1 (every sweep starts from here)
@@ -81,6 +85,7 @@ constexpr int OFF_NB = OFF_CUR;                              // [LNV][MAXNB] u16
 constexpr int OFF_TRI = OFF_CUR;                             // 8 waves x 528 doubles (packed lower triangles)
 constexpr int OFF_TMP = OFF_SROW;                            // cell lists in arrival order (before the rows are built)
 static_assert(LNV * MAXNB * 2 <= 3 * PBUF && TRW * 528 * 8 <= 3 * PBUF && 3 * LNT * 4 <= LNV * SROW, "setup scratch");
+static_assert(LNV / BS <= 32, "one bit per block");
 static_assert(OFF_SROW % 16 == 0 && OFF_PTR % 16 == 0 && OFF_INC % 16 == 0 && OFF_G % 16 == 0 && OFF_R2K % 8 == 0 && OFF_M01 % 16 == 0, "LDS alignment");
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
@@ -192,25 +197,33 @@ extern "C" int mdq_lin_bt_host(long long* out, int reset) {
 #define BT(k)
 #endif
 
+// `wide` (wave-uniform): some row of the block has more than 8 gather slots, and the step reads all 7 per lane half.
+// Otherwise NNARROW = 4 - the set-up fills the slots alternately over the two halves, so positions 4-6 of both halves hold
+// the zero record there, and the wide tree would add + 0.0 behind the same four: three LDS reads and one level of
+// dependent adds less.  (The narrow sum is - 0.0 where the wide one is + 0.0 only if all eight positions are - 0.0; the
+// sign of a zero g does not reach x: the accumulators below start at + 0.0, and (+ 0.0) + (- 0.0) = + 0.0.)  One body with
+// a scalar branch around the three extra gathers: as two instances of the whole step per rotation position the sweep
+// went over its 168 VGPRs (8 B of scratch per lane).
 template <int COMP>
-__device__ __forceinline__ void solve_block(unsigned char* lds, const u4 meta, const d2 (&M)[8], int i, int h) {
+__device__ __forceinline__ void solve_block(unsigned char* lds, const u4 meta, const d2 (&M)[8], int i, int h, bool wide) {
   BT_DECL
   const unsigned char* cur = lds + OFF_CUR + COMP * 8;
   const double v0 = *reinterpret_cast<const double*>(cur + (meta.x & 0xFFFF));
   const double v1 = *reinterpret_cast<const double*>(cur + (meta.x >> 16));
   const double v2 = *reinterpret_cast<const double*>(cur + (meta.y & 0xFFFF));
   const double v3 = *reinterpret_cast<const double*>(cur + (meta.y >> 16));
-  const double v4 = *reinterpret_cast<const double*>(cur + (meta.z & 0xFFFF));
-  const double v5 = *reinterpret_cast<const double*>(cur + (meta.z >> 16));
-  const double v6 = *reinterpret_cast<const double*>(cur + (meta.w & 0xFFFF));
+  double sv_ = (v0 + v1) + (v2 + v3);
+  if (wide) {
+    const double v4 = *reinterpret_cast<const double*>(cur + (meta.z & 0xFFFF));
+    const double v5 = *reinterpret_cast<const double*>(cur + (meta.z >> 16));
+    const double v6 = *reinterpret_cast<const double*>(cur + (meta.w & 0xFFFF));
+    sv_ += (v4 + v5) + v6;
+  }
 #ifdef MDQ_LIN_TRACE2
-  double sv_ = ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + v6);
   asm volatile("" : "+v"(sv_));
-  BT(0)                                 // gather: 7 LDS reads + 6 adds
-  const double g = halves_sum(sv_);
-#else
-  const double g = halves_sum(((v0 + v1) + (v2 + v3)) + ((v4 + v5) + v6));
+  BT(0)                                 // gather: 4 or 7 LDS reads + 3 or 6 adds
 #endif
+  const double g = halves_sum(sv_);
   double* G = reinterpret_cast<double*>(lds + OFF_G) + COMP * BS;
   if (h == 0) G[i] = g;
   asm volatile("" ::: "memory");      // (the LDS serves a wave's operations in order: the reads below see the store)
@@ -275,19 +288,21 @@ __device__ __forceinline__ void solve_sweep(unsigned char* lds, const d2* mg, in
   d2 MA[8], MB[8], MC[8];
   load_m_lds(MA, lds, 0, i, h);
   load_m_lds(MB, lds, 1, i, h);
+  // (the blocks' widths - bit b: some row of block b has more than 8 gather slots - in a scalar register for the sweep)
+  const uint32_t wide = (uint32_t)__builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(lds + OFF_MISC)[3]);
   u4 meta = *reinterpret_cast<const u4*>(srow);
   for (int b = 0; b < nb; b += 3) {
     u4 mnext = *reinterpret_cast<const u4*>(srow + (b + 1) * (BS * SROW));
     load_m(MC, mg, b + 2, i, h);           // (the workspace holds two blocks of padding behind the last one)
-    solve_block<COMP>(lds, meta, MA, i, h);
+    solve_block<COMP>(lds, meta, MA, i, h, (wide >> b) & 1);
     if (b + 1 >= nb) break;
     meta = *reinterpret_cast<const u4*>(srow + (b + 2) * (BS * SROW));
     load_m(MA, mg, b + 3, i, h);
-    solve_block<COMP>(lds, mnext, MB, i, h);
+    solve_block<COMP>(lds, mnext, MB, i, h, (wide >> (b + 1)) & 1);
     if (b + 2 >= nb) break;
     mnext = *reinterpret_cast<const u4*>(srow + (b + 3) * (BS * SROW));
     load_m(MB, mg, b + 4, i, h);
-    solve_block<COMP>(lds, meta, MC, i, h);
+    solve_block<COMP>(lds, meta, MC, i, h, (wide >> (b + 2)) & 1);
     meta = mnext;
   }
 }
@@ -442,7 +457,8 @@ extern "C" int mdq_lin_trace_host(long long* out, int reset) {
 __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, double* coords, const int32_t* cells,
                                                             const int32_t* nv_, const int32_t* nt_, const int32_t* iters_,
                                                             const int32_t* rem, const int32_t* rstat, int iters_env,
-                                                            double* mws, int64_t mstride, int32_t* redo, int32_t* stats) {
+                                                            double* mws, int64_t mstride, int32_t* redo, int32_t* stats,
+                                                            int gather_all) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // sweeps: given per environment, or - inside an env step - `iters_env` where a vertex was removed successfully
@@ -472,7 +488,8 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
 #endif
   // ---- vertex -> cells
   for (int v = tid; v < LNV; v += LWG) cnt[v] = 0;
-  if (tid < 3) misc[tid] = tid == 2 ? 1 : 0;
+  // (the block widths start at "narrow" - or at "wide" everywhere under MDQ_SMOOTH_GATHER=7: the A / B switch)
+  if (tid < 4) misc[tid] = tid == 2 ? 1 : tid == 3 && gather_all ? -1 : 0;
   if (tid < 32) reinterpret_cast<double*>(lds + OFF_R2K)[tid] = tid ? 1.0 / (2.0 * tid) : 0.0;
   __syncthreads();
   for (int t = tid; t < nt; t += LWG)
@@ -502,11 +519,26 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
     if (v < nv && k > MAXNB) misc[2] = 0;                    // (a vertex of more than 16 cells: careful walk)
     int nn = 0;
     if (interior) {
-      for (int e = 0; e < k; ++e) {                          // rank sort by cell id
-        const uint32_t my = tmp[q0 + e];
-        int rank = 0;
-        for (int j = 0; j < k; ++j) rank += (tmp[q0 + j] >> 20) < (my >> 20);
-        inc[q0 + rank] = my;
+      if (k <= 8) {
+        // rank sort by cell id with the entries in registers: one batch of reads instead of k (k + 1) dependent ones.
+        // (The cell id is the top field and distinct per entry, so whole words compare as cell ids; the padding is larger.)
+        uint32_t ent[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ent[j] = j < k ? tmp[q0 + j] : 0xFFFFFFFFu;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          int rank = 0;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) rank += ent[j] < ent[e];
+          if (e < k) inc[q0 + rank] = ent[e];
+        }
+      } else {
+        for (int e = 0; e < k; ++e) {                        // rank sort by cell id
+          const uint32_t my = tmp[q0 + e];
+          int rank = 0;
+          for (int j = 0; j < k; ++j) rank += (tmp[q0 + j] >> 20) < (my >> 20);
+          inc[q0 + rank] = my;
+        }
       }
       for (int e = 0; e < k; ++e) {
         const uint32_t w = inc[q0 + e];
@@ -574,6 +606,7 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
         }
       }
       if (ns > NSLOT || nl > MAXLOW) misc[2] = 0;
+      if (ns > 2 * NNARROW) atomicOr(&misc[3], 1 << (r >> 5));
       slots[7] = (uint16_t)(v * 16);                          // where the row's result goes
       for (int q = q0; q < q0 + k; ++q) {                      // validation entries: a | c << 10 | v << 20 | new(a) << 30 | new(c) << 31
         const uint32_t w = inc[q];
@@ -817,11 +850,17 @@ static int smooth_fast_impl(const char* who, int32_t B, int32_t NV, int32_t NT, 
   double* mws = reinterpret_cast<double*>(workspace);
   int32_t* redo = reinterpret_cast<int32_t*>(mws + (int64_t)B * mstride);
   hipStream_t st = (hipStream_t)stream;
+  // (MDQ_SMOOTH_GATHER=7: every block step gathers all 14 slots of its rows - A / B switch and the reference of the narrow
+  //  block step's test, read once per process)
+  static const int gather_all = [] {
+    const char* e = std::getenv("MDQ_SMOOTH_GATHER");
+    return e && std::atoi(e) == 7 ? 1 : 0;
+  }();
   // every sweep as a blocked triangular solve: checked + repaired while limited steps occur, then validated in parallel.
   // Environments beyond the kernel's limits (more than 16 cells at a vertex, 14 gather slots per row, 8 lower neighbours
   // inside a block) are walked vertex by vertex by their own workgroup inside the same launch (redo[b] = their sweeps)
   hipLaunchKernelGGL(mdq_smooth_lin::smooth_linear_kernel, dim3(B), dim3(mdq_smooth_lin::LWG), 0, st, NV, NT, coords, cells, nv,
-                     nt, iterations, rem, rstat, iters_env, mws, mstride, redo, redo + B);
+                     nt, iterations, rem, rstat, iters_env, mws, mstride, redo, redo + B, gather_all);
   if (hipGetLastError() != hipSuccess) return mdq_set_error("mdq_smooth_fast: launch failed");
   return 0;
 }
