@@ -568,6 +568,37 @@ typedef struct mdq_replay_sample_desc {
 MDQ_API int mdq_replay_sample(const mdq_replay_sample_desc* d, void* stream);
 
 /*
+ * The same sampling launch with the n-step transition of every draw composed on the way (appended within ABI 8; ns NULL:
+ * exactly mdq_replay_sample, which calls this one; no reference counterpart: its targets are 1-step).  The ring is written
+ * in groups of W records, one per batched step, so record (j + W) % capacity is the next transition of the environment of
+ * record j.  The walk of draw i takes j_0 = idx[i] and, after taking j_k, stops if k + 1 == n_step, if record j_k is
+ * terminal (done > 0.5) or if (j_k + W) % capacity lies in [head, head + W) - the group being written; otherwise
+ * j_(k+1) = (j_k + W) % capacity.  With m records taken, L = j_(m-1), g_0 = 1, g_(k+1) = g_k gamma:
+ *     x_s, edges of s, action   of record j_0 (as mdq_replay_sample)
+ *     reward[i]   = (float) sum_{k<m} g_k (double) reward_(j_k): fp64, in the order k = 0 .. m - 1, every product and every
+ *                   sum rounded on its own, rounded to float once
+ *     nonfinal[i] = 0 if record L is terminal, else (float) g_(m-1): gamma^m is formed as float(gamma^(m-1)) * float(gamma)
+ *                   inside the learning step, which multiplies `nonfinal` by its own gamma; no division: gamma = 0 is served
+ *     x_n, edges of s'          s' of record L; L terminal: the own state of j_0 as the masked placeholder
+ *     steps[i]    = m
+ * Every successor is formed modulo `capacity`: given idx[i] in [0, capacity) (the caller's job, as in mdq_replay_sample) no
+ * read leaves the ring whatever it holds.  A drawn record of the head group is taken as it is.  n_step = 1: the bits of
+ * mdq_replay_sample for any W, head and gamma.  One launch, no atomics, no device random numbers: run-to-run identical.
+ * n_step outside 1 .. 64, W < 1, a capacity that is no multiple of W or below 2 W, a head that is no multiple of W or
+ * outside [0, capacity) and a gamma that is negative or not finite are refused before any launch.
+ */
+typedef struct mdq_replay_nstep {
+  int32_t n_step;             /* 1 .. 64 */
+  int32_t W;                  /* records per group: the successor of record j is (j + W) % capacity */
+  int32_t capacity;           /* records of the ring, a multiple of W, at least 2 W */
+  int32_t head;               /* first record of the group the walk must never step INTO: the group being written
+                                 (SharedDeviceReplay.group_base(t)); a multiple of W in [0, capacity) */
+  double gamma;               /* finite, >= 0 */
+  int32_t* steps;             /* device [n] (out, may be NULL): m_i, the transitions composed for draw i */
+} mdq_replay_nstep;
+MDQ_API int mdq_replay_sample_nstep(const mdq_replay_sample_desc* d, const mdq_replay_nstep* ns, void* stream);
+
+/*
  * Proportional prioritized replay on the record ring (Schaul et al. 2016; no reference counterpart: ReplayMemory.sample is
  * uniform).  Appended within ABI 8.  float prio[capacity] holds p_j = (|td_j| + eps)^alpha of record j, and
  *     prio[j] == 0  <=>  record j must not be drawn (never written, or of the group that is being written),

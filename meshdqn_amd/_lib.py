@@ -154,6 +154,12 @@ class ReplayPrioDrawDesc(C.Structure):
         (n, C.c_void_p) for n in ("prio", "u", "idx", "weight", "total")]
 
 
+class ReplayNstepDesc(C.Structure):
+    """Mirror of `mdq_replay_nstep` (appended within ABI 8)."""
+    _fields_ = [("n_step", C.c_int32), ("W", C.c_int32), ("capacity", C.c_int32), ("head", C.c_int32), ("gamma", C.c_double),
+                ("steps", C.c_void_p)]
+
+
 # every symbol include/meshdqn_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mdq_abi_version": (C.c_int, []),
@@ -230,6 +236,7 @@ SYMBOLS = {
     "mdq_replay_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mdq_replay_sample": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mdq_replay_sample_nstep": (C.c_int, [C.c_void_p, C.POINTER(ReplayNstepDesc), C.c_void_p]),
     "mdq_replay_prio_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mdq_replay_prio_draw": (C.c_int, [C.POINTER(ReplayPrioDrawDesc), C.c_void_p]),
     "mdq_replay_prio_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double,

@@ -4,6 +4,8 @@
 //                          (ReplayMemory.push, airfoil_dqn.py:56-61, for B environments at once)
 //   replay_sample_kernel : a minibatch of records -> the arrays of mdq_gcn_forward / mdq_gcn_train_step
 //                          (ReplayMemory.sample + the Batch.from_data_list of DataWorker._get_data, airfoil_dqn.py:63-64,240-262)
+//   replay_sample_nstep_kernel : the same launch with the n-step transition of every draw composed from the ring's
+//                          groups (no reference counterpart: its targets are 1-step)
 //   adam_kernel          : torch.optim.Adam.step (weight decay as L2 term, bias corrections) on every trained
 //                          parameter in one launch (ParameterServer.apply_gradients, airfoil_dqn.py:184-200)
 //   prio_*_kernel        : proportional prioritized replay on the ring (no reference counterpart: its replay is uniform)
@@ -11,6 +13,8 @@
 //   [ x(s) N*F | x(s') N*F | src(s) EM | dst(s) EM | src(s') EM | dst(s') EM | edges(s) | edges(s') | action | reward | done ]
 // (a terminal transition has zeros for s').
 #include <hip/hip_runtime.h>
+
+#include <cmath>
 
 #include "../../include/meshdqn_hip.h"
 #include "mdq_internal.h"
@@ -106,6 +110,99 @@ __global__ __launch_bounds__(256) void replay_sample_kernel(mdq_replay_sample_de
   }
 }
 
+// The last record of the n-step walk from record j0 (semantics: include/meshdqn_hip.h): successor (j + W) % capacity, at most
+// n_step records, never past a terminal one and never INTO the group at `head`.  A chain of dependent reads of `done`.
+__device__ __forceinline__ int nstep_last(const float* R, int rec_len, int tail, const mdq_replay_nstep& S, int j0) {
+  int j = j0;
+  for (int k = 1; k < S.n_step; ++k) {
+    if (R[(size_t)j * rec_len + tail + 4] > 0.5f) break;
+    const int nx = (int)(((unsigned)j + (unsigned)S.W) % (unsigned)S.capacity);
+    if (nx >= S.head && nx < S.head + S.W) break;
+    j = nx;
+  }
+  return j;
+}
+
+// replay_sample_kernel with the n-step transition of every draw composed on the way: s, its edges and the action of
+// record idx[i]; s' and its edges of the walk's last record; the discounted reward sum and gamma^(m-1) in `nonfinal`.
+__global__ __launch_bounds__(256) void replay_sample_nstep_kernel(mdq_replay_sample_desc D, mdq_replay_nstep S) {
+  const int i = blockIdx.x, tid = threadIdx.x, nf = D.nf, EM = D.EM, tail = 2 * nf + 4 * EM;
+  __shared__ int red[2][256];
+  __shared__ int own[2];      // last record of this draw's walk, records taken
+  __shared__ float ownf[2];   // reward, nonfinal
+  // packed edge offsets of this transition's two graphs: counts of the transitions before it, each behind its own walk
+  int c0 = 0, c1 = 0;
+  for (int j = tid; j < i; j += 256) {
+    const int j0 = D.idx[j];
+    const float* t0 = D.R + (size_t)j0 * D.rec_len + tail;
+    const float* tl = D.R + (size_t)nstep_last(D.R, D.rec_len, tail, S, j0) * D.rec_len + tail;
+    c0 += (int)t0[0];
+    c1 += tl[4] > 0.5f ? (int)t0[0] : (int)tl[1];   // terminal: the own state of idx[j] as a masked placeholder
+  }
+  red[0][tid] = c0;
+  red[1][tid] = c1;
+  if (tid == 0) {   // this draw's own walk, once: fp64, every product and every sum rounded on its own, in the order of k
+#pragma clang fp contract(off)   // (plain operators under this pragma: HIP's __dmul_rn / __dadd_rn do not stop an fma)
+    int j = D.idx[i], m = 1;
+    const float* t = D.R + (size_t)j * D.rec_len + tail;
+    double g = 1.0, acc = (double)t[3];
+    while (m < S.n_step && !(t[4] > 0.5f)) {
+      const int nx = (int)(((unsigned)j + (unsigned)S.W) % (unsigned)S.capacity);
+      if (nx >= S.head && nx < S.head + S.W) break;
+      j = nx;
+      t = D.R + (size_t)j * D.rec_len + tail;
+      g = g * S.gamma;
+      const double term = g * (double)t[3];
+      acc = acc + term;
+      ++m;
+    }
+    own[0] = j;
+    own[1] = m;
+    ownf[0] = (float)acc;
+    ownf[1] = t[4] > 0.5f ? 0.f : (float)g;   // gamma^(m-1): the learning step multiplies by (float)gamma once more
+  }
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) {
+      red[0][tid] += red[0][tid + off];
+      red[1][tid] += red[1][tid + off];
+    }
+    __syncthreads();
+  }
+  const int o0 = red[0][0], o1 = red[1][0];
+  const float* r = D.R + (size_t)D.idx[i] * D.rec_len;
+  const float* rl = D.R + (size_t)own[0] * D.rec_len;
+  const float* t = r + tail;
+  const bool dn = rl[tail + 4] > 0.5f;
+  const int n0 = (int)t[0], n1 = dn ? n0 : (int)rl[tail + 1];
+  const float* xn = dn ? r : rl + nf;
+  const float* sn = dn ? r + 2 * nf : rl + 2 * nf + 2 * EM;
+  for (int k = tid; k < nf; k += 256) {
+    D.x_s[(size_t)i * nf + k] = r[k];
+    D.x_n[(size_t)i * nf + k] = xn[k];
+  }
+  for (int e = tid; e < n0; e += 256) {
+    D.esrc_s[o0 + e] = (int32_t)r[2 * nf + e];
+    D.edst_s[o0 + e] = (int32_t)r[2 * nf + EM + e];
+  }
+  for (int e = tid; e < n1; e += 256) {
+    D.esrc_n[o1 + e] = (int32_t)sn[e];
+    D.edst_n[o1 + e] = (int32_t)sn[EM + e];
+  }
+  if (tid == 0) {
+    D.edge_ptr_s[i] = o0;
+    D.edge_ptr_n[i] = o1;
+    if (i == (int)gridDim.x - 1) {
+      D.edge_ptr_s[i + 1] = o0 + n0;
+      D.edge_ptr_n[i + 1] = o1 + n1;
+    }
+    D.action[i] = (int64_t)t[2];
+    D.reward[i] = ownf[0];
+    D.nonfinal[i] = ownf[1];
+    if (S.steps) S.steps[i] = own[1];
+  }
+}
+
 // torch.optim.Adam (amsgrad False, maximize False), one thread per parameter element of every segment
 __global__ __launch_bounds__(256) void adam_kernel(mdq_adam_desc D) {
   const int s = blockIdx.y;
@@ -141,14 +238,29 @@ extern "C" int mdq_replay_step(float* ring, int32_t rec_len, int32_t capacity, i
   return 0;
 }
 
-extern "C" int mdq_replay_sample(const mdq_replay_sample_desc* d, void* stream) {
+extern "C" int mdq_replay_sample_nstep(const mdq_replay_sample_desc* d, const mdq_replay_nstep* ns, void* stream) {
   if (!d || d->n <= 0 || !d->R || !d->idx || d->rec_len != 2 * d->nf + 4 * d->EM + 5 || !d->x_s || !d->x_n || !d->esrc_s ||
       !d->edst_s || !d->esrc_n || !d->edst_n || !d->edge_ptr_s || !d->edge_ptr_n || !d->action || !d->reward || !d->nonfinal)
-    return mdq_set_error("mdq_replay_sample: bad arguments");
-  hipLaunchKernelGGL(mdq_replay::replay_sample_kernel, dim3(d->n), dim3(256), 0, (hipStream_t)stream, *d);
-  if (hipGetLastError() != hipSuccess) return mdq_set_error("replay_sample_kernel launch failed");
+    return mdq_set_error(ns ? "mdq_replay_sample_nstep: bad arguments" : "mdq_replay_sample: bad arguments");
+  if (!ns) {
+    hipLaunchKernelGGL(mdq_replay::replay_sample_kernel, dim3(d->n), dim3(256), 0, (hipStream_t)stream, *d);
+    if (hipGetLastError() != hipSuccess) return mdq_set_error("replay_sample_kernel launch failed");
+    return 0;
+  }
+  if (ns->n_step < 1 || ns->n_step > 64) return mdq_set_error("mdq_replay_sample_nstep: n_step outside 1 .. 64");
+  if (ns->W < 1) return mdq_set_error("mdq_replay_sample_nstep: W must be positive");
+  if (ns->capacity < 2 * (long long)ns->W || ns->capacity % ns->W != 0)
+    return mdq_set_error("mdq_replay_sample_nstep: capacity must be a multiple of W and at least 2 W");
+  if (ns->head < 0 || ns->head >= ns->capacity || ns->head % ns->W != 0)
+    return mdq_set_error("mdq_replay_sample_nstep: head must be a multiple of W in [0, capacity)");
+  if (!(ns->gamma >= 0.0) || !std::isfinite(ns->gamma))
+    return mdq_set_error("mdq_replay_sample_nstep: gamma must be finite and not negative");
+  hipLaunchKernelGGL(mdq_replay::replay_sample_nstep_kernel, dim3(d->n), dim3(256), 0, (hipStream_t)stream, *d, *ns);
+  if (hipGetLastError() != hipSuccess) return mdq_set_error("replay_sample_nstep_kernel launch failed");
   return 0;
 }
+
+extern "C" int mdq_replay_sample(const mdq_replay_sample_desc* d, void* stream) { return mdq_replay_sample_nstep(d, nullptr, stream); }
 
 extern "C" int mdq_adam_step(const mdq_adam_desc* d, void* stream) {
   if (!d || d->n <= 0 || d->n > MDQ_GCN_PACK_MAX || !d->grad || !d->exp_avg || !d->exp_avg_sq)

@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import random
 from collections import namedtuple
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -123,7 +123,11 @@ class SharedDeviceReplay:
     Prioritized replay (`prio_fill` / `prio_draw` / `prio_update`: the three `mdq_replay_prio_*` kernels on the current
     stream): the ring owns `prio` (capacity,) - (|td| + eps)^alpha of every record, 0 for a record that must not be drawn -
     and `pmax` (1,), the largest priority seen so far, started at 1; both are allocated on first use and, like the ring
-    itself, are not part of a checkpoint."""
+    itself, are not part of a checkpoint.
+
+    N-step returns (`nstep_desc`): record j + W (mod capacity) is the next transition of the environment of record j - the
+    environments reset in place and every record stores `done` -, so `mdq_replay_sample_nstep` composes the n-step
+    transition of a drawn record from the finished groups, stopping in front of the one being written."""
 
     def __init__(self, capacity: int, N: int, F: int, e_max: int, device):
         self.capacity, self.N, self.F, self.e_max, self.device = int(capacity), int(N), int(F), int(e_max), device
@@ -156,6 +160,16 @@ class SharedDeviceReplay:
         if t >= self.G:                                        # wrapped: skip over the group being written
             idx = np.where(idx < self.group_base(t), idx, idx + self.W)
         return idx.astype(np.int32)
+
+    def nstep_desc(self, t: int, n_step: int, gamma: float, steps: Optional[torch.Tensor] = None, desc=None):
+        """The `mdq_replay_nstep` of a minibatch of step t (a new one, or `desc` refilled): walks over the ring's groups that
+        never step into the group step t writes.  `steps`: (n,) int32 device tensor for the composed lengths, or None."""
+        if steps is not None and (steps.dtype != torch.int32 or steps.device.type != "cuda" or not steps.is_contiguous()):
+            raise ValueError("nstep_desc wants a contiguous int32 device tensor for steps")
+        d = desc if desc is not None else _lib.ReplayNstepDesc()
+        d.n_step, d.W, d.capacity, d.head, d.gamma = int(n_step), self.W, self.capacity, self.group_base(t), float(gamma)
+        d.steps = None if steps is None else steps.data_ptr()
+        return d
 
     def step(self, st: dict, base_cur: int = -1, prev=None):
         """One `mdq_replay_step` launch on the current stream: the batched env state `st` becomes s of the records at `base_cur`

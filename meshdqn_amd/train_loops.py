@@ -80,6 +80,14 @@ def _refuse_prioritized(trainer, loop: str):
                          "(DQNTrainer(prioritized=...)) needs train_loop_device")
 
 
+def _refuse_n_step(trainer, loop: str):
+    """N-step targets are composed from the device ring, whose groups keep the environments' lane order (record j + W is the
+    successor of record j); the host replay stores keep no such order."""
+    if trainer.n_step > 1:
+        raise ValueError(f"{loop} samples a host replay store that keeps no lane order: a trainer with n-step returns "
+                         "(DQNTrainer(n_step=...)) needs train_loop_device")
+
+
 def _draw_epsilon(steps_done, n_actions: int, eps_start, eps_end, eps_decay):
     """Host random numbers of one batched step (both batched loops): epsilon per env, who explores, the random actions."""
     eps = eps_end + (eps_start - eps_end) * np.exp(-1.0 * steps_done / eps_decay)
@@ -116,6 +124,7 @@ def train_loop_per_worker(trainer: DQNTrainer, env_factory, num_episodes: int, m
     all-gather), so all ranks must take the SAME number of steps: episode lengths differ between ranks (per-rank
     seeds), hence the loop must be bounded by `max_steps` (episodes are then cut at that common step count)."""
     _refuse_prioritized(trainer, "train_loop_per_worker")
+    _refuse_n_step(trainer, "train_loop_per_worker")
     ctx = trainer.ctx
     if ctx.world > 1 and max_steps is None:
         raise ValueError("train_loop_per_worker with more than one rank needs max_steps (a step count common to all "
@@ -175,6 +184,7 @@ def train_loop_vec(trainer: DQNTrainer, venv, num_steps: int, optim_per_step: in
     `on_every(step, steps_done)` is called after every `every`-th batched step (periodic checkpoints / log writes).
     Returns dict(rewards (num_steps,B), dones, losses, steps_done)."""
     _refuse_prioritized(trainer, "train_loop_vec")
+    _refuse_n_step(trainer, "train_loop_vec")
     ctx = trainer.ctx
     B, N = venv.B, venv.N
     fused = FusedGcn(trainer.policy_net_1)
@@ -270,7 +280,8 @@ def train_loop_vec(trainer: DQNTrainer, venv, num_steps: int, optim_per_step: in
 
 def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step: int = 1, eps_decay=10000, eps_start=1.0,
                       eps_end=0.01, share_replay=False, log: Optional["TrainingLog"] = None, steps_done0=None, every: int = 0,
-                      on_every=None, chunk: int = 64, optimiser_stream: str = "auto", per_trace: bool = False):
+                      on_every=None, chunk: int = 64, optimiser_stream: str = "auto", per_trace: bool = False,
+                      nstep_trace: bool = False):
     """`train_loop_vec` WITHOUT a host round trip inside a batched step (one rank of configs[3]): the environment step is
     `VecEnv2DAirfoil.rollout_step` (Q-forward, epsilon-greedy choice, vertex removal ... reward / reset logic as kernels),
     the B transitions go into the record ring with one launch (`mdq_replay_step`; with `share_replay` the ranks
@@ -289,12 +300,25 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
     the optimiser stream: the main chain gains no launch and no event.  Over several ranks with `share_replay` the ring
     stays identical on all ranks; the priorities are rank-local (every rank learns from its own minibatch, the gradient is
     all-reduced as before).  `per_trace=True` adds out["per"]: `u`, `idx`, `weight`, `td` (minibatches, batch) and `beta`
-    (minibatches,) of every minibatch of the call, in order, read back with the losses at the chunk boundaries."""
+    (minibatches,) of every minibatch of the call, in order, read back with the losses at the chunk boundaries.
+
+    With `DQNTrainer(n_step=n)`, n > 1, the sampling launch of every minibatch of step t composes n-step transitions from the
+    ring (`mdq_replay_sample_nstep`, head = the group step t writes); the host draw and the prioritized chain do not change -
+    a drawn record is never in the head group, and its priority comes from the n-step TD error.  The walk needs no new event
+    or stream dependency: the optimiser chain of step t already runs behind the event recorded after `rep.step` of step t,
+    which finished group t - 1; the main stream already waits for that chain (`ev_opt`) before the next `rep.step`, the only
+    writer of the ring on it; with `share_replay` the all-gather of group t - 1 precedes the minibatches on the optimiser
+    stream itself.  So every record a walk can reach (the groups of steps t - G + 1 .. t - 1) is finished and stable while
+    the walk reads it.  `nstep_trace=True` (refused for n_step = 1) adds out["nstep"]: `idx`, `reward`, `nonfinal`, `steps`
+    (minibatches, batch) and `head` (minibatches,), the first record of the head group, read back like the `per` trace."""
     ctx = trainer.ctx
     dev = ctx.device
     per = trainer.prioritized
     if per_trace and per is None:
         raise ValueError("per_trace needs a trainer with prioritized replay")
+    n_step = trainer.n_step
+    if nstep_trace and n_step == 1:
+        raise ValueError("nstep_trace needs a trainer with n_step > 1")
     if dev.type != "cuda" or not venv.gpu_remesh or not venv.auto_reset:
         raise MeshDQNHipError("train_loop_device needs a GPU and a vector env with the device mesh engine and auto_reset")
     B, N = venv.B, venv.N
@@ -311,7 +335,7 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
             out = train_loop_device(trainer, venv, num_steps, optim_per_step=optim_per_step, eps_decay=eps_decay,
                                     eps_start=eps_start, eps_end=eps_end, share_replay=share_replay, log=log,
                                     steps_done0=steps_done0, every=every, on_every=on_every, chunk=chunk,
-                                    optimiser_stream=optimiser_stream, per_trace=per_trace)
+                                    optimiser_stream=optimiser_stream, per_trace=per_trace, nstep_trace=nstep_trace)
         main.wait_stream(trainer._main_stream)
         return out
     if venv.flow_overlap and not same_stream(venv._calibrated_for, main):
@@ -333,6 +357,7 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
         opt_stream = trainer._opt_stream
     ev_opt = rep = None
     trace = dict(u=[], idx=[], weight=[], td=[], beta=[])
+    ntrace = dict(idx=[], reward=[], nonfinal=[], steps=[], head=[])
     rewards, dones_hist, actions_hist = [], [], []
     episodes = _EpisodeLog(log, venv)
     step_no, prev = 0, None      # prev: (record base, act, rew, done) of the step whose records await their next state
@@ -356,6 +381,10 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
                 shape = (loss_ring.numel(), trainer.batch_size)
                 per_idx = torch.zeros(shape, dtype=torch.int32, device=dev)
                 per_w, per_td = torch.zeros(shape, device=dev), torch.zeros(shape, device=dev)
+            if nstep_trace:         # what the sampling launch composed, a row per minibatch of a chunk
+                shape = (loss_ring.numel(), trainer.batch_size)
+                ns_steps = torch.zeros(shape, dtype=torch.int32, device=dev)
+                ns_rew, ns_nf = torch.zeros(shape, device=dev), torch.zeros(shape, device=dev)
         # minibatches of the chunk: the number of finished records at every step is known in advance; one upload
         if per is None:
             mbs = [rep.draw(t, trainer.batch_size) for t in range(t0 + step_no, t0 + step_no + K)
@@ -366,6 +395,7 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
             u_host = np.array([random.random() for _ in range(n_mb * trainer.batch_size)], np.float64).reshape(n_mb, trainer.batch_size)
             u_dev = torch.from_numpy(u_host).to(dev) if n_mb else None
             betas = []
+        heads = []
         n_loss = 0
         for k in range(K):
             t = t0 + step_no + k
@@ -391,14 +421,19 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
                         # (rank r's B records sit at group base + r * B on every rank): off the latency chain of the env step
                         allgather_records_into(ctx, rep.R, prev[0], B, W)
                     for _k in range(optim_per_step if do_opt else 0):
+                        nkw = dict(head_step=t, steps_out=ns_steps[n_loss] if nstep_trace else None) if n_step > 1 else {}
                         if per is None:
-                            trainer.optimize_device(rep, mb_dev[n_loss], loss_out=loss_ring[n_loss:n_loss + 1])
+                            trainer.optimize_device(rep, mb_dev[n_loss], loss_out=loss_ring[n_loss:n_loss + 1], **nkw)
                         else:
                             betas.append(trainer.beta())
                             rep.prio_draw(u_dev[n_loss], betas[-1], per_idx[n_loss], per_w[n_loss])
                             trainer.optimize_device(rep, per_idx[n_loss], loss_out=loss_ring[n_loss:n_loss + 1],
-                                                    weight=per_w[n_loss], td_out=per_td[n_loss])
+                                                    weight=per_w[n_loss], td_out=per_td[n_loss], **nkw)
                             rep.prio_update(per_idx[n_loss], per_td[n_loss], per["alpha"], per["eps"])
+                        if nstep_trace:     # (the minibatch buffers are rewritten by the next sampling launch)
+                            ns_rew[n_loss].copy_(trainer._mb_bufs["reward"])
+                            ns_nf[n_loss].copy_(trainer._mb_bufs["nonfinal"])
+                            heads.append(rep.group_base(t))
                         n_loss += 1
                     ev_opt = torch.cuda.Event()
                     ev_opt.record(opt_stream)
@@ -430,6 +465,12 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
             for key, ring in (("idx", per_idx), ("weight", per_w), ("td", per_td)):
                 trace[key].append(ring[:n_loss].cpu().numpy())
             trace["beta"].append(np.asarray(betas[:n_loss], np.float64))
+        if nstep_trace:
+            ntrace["idx"].append(per_idx[:n_loss].cpu().numpy() if per is not None else
+                                 (np.stack(mbs) if mbs else np.zeros((0, trainer.batch_size), np.int32)))
+            for key, ring in (("reward", ns_rew), ("nonfinal", ns_nf), ("steps", ns_steps)):
+                ntrace[key].append(ring[:n_loss].cpu().numpy())
+            ntrace["head"].append(np.asarray(heads, np.int64))
         for k in range(K):
             rew, done = out["rewards"][k], out["dones"][k]
             rewards.append(rew.copy())
@@ -446,4 +487,6 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
                actions=np.array(actions_hist))
     if per_trace:
         out["per"] = {key: np.concatenate(v) if v else np.zeros(0) for key, v in trace.items()}
+    if nstep_trace:
+        out["nstep"] = {key: np.concatenate(v) if v else np.zeros(0) for key, v in ntrace.items()}
     return out

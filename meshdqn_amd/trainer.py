@@ -40,8 +40,9 @@ from .train_loops import TrainingLog, epsilon_threshold, train_loop_device, trai
 class DQNTrainer:
     def __init__(self, n_actions: int, num_inputs: int, ctx: Optional[DistContext] = None, lr=1e-5, weight_decay=1e-6,
                  batch_size=32, gamma=1.0, target_update=50, replay_capacity=10000, conv_width=128, topk=0.1,
-                 seed=1370, dense: bool = True, e_max: int = 1536, prioritized: Optional[dict] = None):
+                 seed=1370, dense: bool = True, e_max: int = 1536, prioritized: Optional[dict] = None, n_step: int = 1):
         self.prioritized = self._check_prioritized(prioritized, batch_size)
+        self.n_step = self._check_n_step(n_step)           # a constructor option like `prioritized`: not checkpointed
         self.ctx = ctx or DistContext()
         self.dense, self.e_max = bool(dense), int(e_max)   # static-shape autograd path for equal-sized graphs
         dev = self.ctx.device
@@ -102,6 +103,19 @@ class DQNTrainer:
         if int(batch_size) > 1024:
             raise ValueError(f"prioritized: batch_size {batch_size} exceeds the 1024 draws of mdq_replay_prio_draw")
         return opt
+
+    # --- n-step returns (`train_loop_device` only: composed from the record ring inside the sampling launch) ------
+    N_STEP_MAX = 64
+
+    @classmethod
+    def _check_n_step(cls, n_step) -> int:
+        """The number of transitions a target spans: r_0 + g r_1 + ... + g^(m-1) r_(m-1) + g^m max_a Q(s_m, a), m <= n_step
+        (fewer where the episode ends or the ring's newest finished group is reached).  1: the 1-step target."""
+        if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)):
+            raise ValueError(f"n_step: an integer in 1 .. {cls.N_STEP_MAX}, not {n_step!r}")
+        if not 1 <= int(n_step) <= cls.N_STEP_MAX:
+            raise ValueError(f"n_step: {n_step} outside 1 .. {cls.N_STEP_MAX} (the walk of mdq_replay_sample_nstep)")
+        return int(n_step)
 
     def beta(self, g: Optional[int] = None) -> float:
         """Importance-weight exponent after g gradient applications (`num_grads`, which is checkpointed: a restart
@@ -447,15 +461,23 @@ class DQNTrainer:
         return self.opt_calibration_ms
 
     def optimize_device(self, rep: "SharedDeviceReplay", idx, loss_out: Optional[torch.Tensor] = None,
-                        weight: Optional[torch.Tensor] = None, td_out: Optional[torch.Tensor] = None):
+                        weight: Optional[torch.Tensor] = None, td_out: Optional[torch.Tensor] = None,
+                        head_step: Optional[int] = None, steps_out: Optional[torch.Tensor] = None):
         """One optimiser step on a minibatch of the record ring WITHOUT host synchronisation and without autograd:
         `mdq_replay_sample` (records `idx` -> graph arrays), fused forward of the network without gradient,
         `mdq_gcn_train_step` of the other one (forward + double-DQN Huber loss + backward), ONE flat all-reduce over the
         ranks, `mdq_adam_step`.  Everything is enqueued on the current stream; the loss goes to `loss_out` (a (1,)
         device tensor, e.g. a slot of a log ring) and is also returned as a device tensor.  Same `select` toggling as
         `optimize` (airfoil_dqn.py:315-340 + :184-200 + :240-310).  `weight` / `td_out`: (batch,) float32 device tensors
-        handed through to the learning step (importance weights in, TD errors out: prioritized replay)."""
+        handed through to the learning step (importance weights in, TD errors out: prioritized replay).
+
+        A trainer with `n_step` > 1 samples with `mdq_replay_sample_nstep` instead: the reward becomes the discounted sum over
+        the walk from every drawn record, s' the state the walk ends in, and `nonfinal` carries gamma^(m-1), which the
+        unchanged learning step multiplies by gamma.  `head_step` (required then): the batched step t whose group is being
+        written, which no walk enters (`rep.group_base(t)`); `steps_out`: (batch,) int32 device tensor for the lengths m."""
         dev = self.ctx.device
+        if self.n_step > 1 and head_step is None:
+            raise ValueError("optimize_device: a trainer with n_step > 1 needs head_step (the batched step being written)")
         if (self.num_grads % self.target_update) == 0:
             self.select = not self.select
         sel = self.select
@@ -483,7 +505,12 @@ class DQNTrainer:
             b["idx"].copy_(torch.as_tensor(np.asarray(idx, dtype=np.int32)))     # (pageable source: a blocking copy)
             b["desc"].idx = b["idx"].data_ptr()
         b["desc"].R = rep.R.data_ptr()
-        _lib.check(_lib.load().mdq_replay_sample(C.byref(b["desc"]), _lib.stream_ptr()), "mdq_replay_sample")
+        if self.n_step == 1:
+            _lib.check(_lib.load().mdq_replay_sample(C.byref(b["desc"]), _lib.stream_ptr()), "mdq_replay_sample")
+        else:
+            ns = b["nstep"] = rep.nstep_desc(head_step, self.n_step, self.gamma, steps_out, b.get("nstep"))
+            _lib.check(_lib.load().mdq_replay_sample_nstep(C.byref(b["desc"]), C.byref(ns), _lib.stream_ptr()),
+                       "mdq_replay_sample_nstep")
         gs = dict(x=b["x_s"], esrc=b["esrc_s"], edst=b["edst_s"], edge_ptr=b["edge_ptr_s"])
         gn = dict(x=b["x_n"], esrc=b["esrc_n"], edst=b["edst_n"], edge_ptr=b["edge_ptr_n"])
         go, gd = (gn, gs) if sel else (gs, gn)

@@ -1,7 +1,7 @@
 """Time train_loop_device (S3 env step + replay + optimiser chain) with the optimiser chain on the flow stream / on a stream
-of its own (dev tool).   python tools/time_train_device.py [B] [steps] [--prioritized]
+of its own (dev tool).   python tools/time_train_device.py [B] [steps] [--prioritized] [--n-step N]
 --prioritized: every placement is timed with uniform replay and, beside it, with prioritized replay (three more launches per
-optimiser step on the optimiser stream)."""
+optimiser step on the optimiser stream).  --n-step N: the trainer composes N-step returns inside its sampling launch."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
@@ -14,18 +14,24 @@ cfg = dict(flow_config=dict(flow_params=dict(mu=1e-3, rho=1.0, inflow="constant"
                             solver_params=dict(dt=0.001, solver_type="lu", smooth=True)),
            agent_params=dict(solver_steps=500, episodes=10, timesteps=10000, threshold=0.001, N_closest=180, gt_drag=-1, gt_time=-1, u=-1, p=-1,
                              time_reward=0.005, save_steps=100, goal_vertices=0.95, plot_dir=""))
-pos = [a for a in sys.argv[1:] if not a.startswith("--")]
+argv = sys.argv[1:]
+n_step = 1
+if "--n-step" in argv:
+    k = argv.index("--n-step")
+    n_step = int(argv[k + 1])
+    del argv[k:k + 2]
+pos = [a for a in argv if not a.startswith("--")]
 B = int(pos[0]) if len(pos) > 0 else 128
 n = int(pos[1]) if len(pos) > 1 else 40
 base = Env2DAirfoil(cfg)
 for mode, prio in [(m, p) for m in ("flow", "own", "flow", "own") for p in ((None, {}) if "--prioritized" in sys.argv else (None,))]:
-    trainer = DQNTrainer(n_actions=180, num_inputs=17, ctx=DistContext(), prioritized=prio)
+    trainer = DQNTrainer(n_actions=180, num_inputs=17, ctx=DistContext(), prioritized=prio, n_step=n_step)
     venv = VecEnv2DAirfoil(cfg, B, base_env=base, flow_steps=1, flow_overlap=True)
     train_loop_device(trainer, venv, 6, optimiser_stream=mode)
     torch.cuda.synchronize(); t0 = time.time()
     train_loop_device(trainer, venv, n, optimiser_stream=mode)
     torch.cuda.synchronize(); dt = time.time() - t0
-    print(f"optimiser_stream={mode} prioritized={'off' if prio is None else 'on'}: {dt / n * 1e3:.3f} ms per batched step -> {B * n / dt:.0f} env-steps/s; calibration flow "
+    print(f"optimiser_stream={mode} prioritized={'off' if prio is None else 'on'} n_step={n_step}: {dt / n * 1e3:.3f} ms per batched step -> {B * n / dt:.0f} env-steps/s; calibration flow "
           f"{[round(v, 2) for v in getattr(venv, 'calibration_ms', [])]} opt {[round(v, 2) for v in trainer.opt_calibration_ms]}", flush=True)
     venv.flow_wait()
     del venv, trainer

@@ -27,11 +27,23 @@ def prioritized_options(flag: bool, cfg: dict):
     `replay: {prioritized: true, alpha: 0.6, beta0: 0.4, beta_steps: 100000, eps: 1.0e-6}` (not a reference section: its
     replay is uniform).  None: uniform replay; the flag alone: the defaults; the block's numbers hold with either switch."""
     block = dict(cfg.get("replay") or {})
+    block.pop("n_step", None)               # (the block's other option: `n_step_option`)
     on = bool(block.pop("prioritized", False)) or bool(flag)
     unknown = sorted(set(block) - {"alpha", "beta0", "beta_steps", "eps"})
     if unknown:
-        raise SystemExit(f"replay: unknown key(s) {unknown} (known: prioritized, alpha, beta0, beta_steps, eps)")
+        raise SystemExit(f"replay: unknown key(s) {unknown} (known: prioritized, alpha, beta0, beta_steps, eps, n_step)")
     return {k: float(v) for k, v in block.items()} if on else None
+
+
+def n_step_option(flag, cfg: dict) -> int:
+    """The `n_step` argument of `DQNTrainer` from --n-step and the optional yaml key `replay: {n_step: N}` (not a reference
+    key: its targets are 1-step).  The flag wins when both are given; neither: 1."""
+    if flag is not None:
+        return int(flag)
+    n = (cfg.get("replay") or {}).get("n_step", 1)
+    if isinstance(n, bool) or not isinstance(n, int):
+        raise SystemExit(f"replay: n_step must be an integer, not {n!r}")
+    return n
 
 
 def parser():
@@ -70,6 +82,10 @@ def parser():
                     help="proportional prioritized experience replay in the device-resident loop (draw, importance weights and "
                          "priority update as kernels of the optimiser chain); its numbers come from the optional yaml block "
                          "replay: {prioritized: true, alpha: 0.6, beta0: 0.4, beta_steps: 100000, eps: 1.0e-6}")
+    ap.add_argument("--n-step", type=int, default=None, metavar="N",
+                    help="n-step returns in the device-resident loop, 1 .. 64 (the n-step transition of every drawn record is "
+                         "composed from the record ring inside the sampling launch); also the yaml key replay: {n_step: N}; "
+                         "default 1")
     return ap
 
 
@@ -107,7 +123,7 @@ def main():
                          ctx=ctx, lr=float(opt.get("lr", 1e-5)), weight_decay=float(opt.get("weight_decay", 1e-6)),
                          batch_size=int(opt.get("batch_size", 32)), gamma=float(eps.get("gamma", 1.0)),
                          target_update=int(ap_.get("target_update", 50)),
-                         prioritized=prioritized_options(args.prioritized_replay, cfg))
+                         prioritized=prioritized_options(args.prioritized_replay, cfg), n_step=n_step_option(args.n_step, cfg))
     # restart chain: restart n reads the checkpoint with n - 1 "restart_" prefixes and writes with n (every rank loads the
     # same files, so the replicas stay identical)
     restart_num, steps_done0 = 0, None
@@ -142,6 +158,8 @@ def main():
     device_loop = ctx.device.type == "cuda" and venv.gpu_remesh and not args.host_loop
     if trainer.prioritized is not None and not device_loop:
         raise SystemExit("prioritized replay needs the device-resident loop (a GPU, the device mesh engine, no --host-loop)")
+    if trainer.n_step > 1 and not device_loop:
+        raise SystemExit("n-step returns need the device-resident loop (a GPU, the device mesh engine, no --host-loop)")
     loop = train_loop_device if device_loop else train_loop_vec
     kw, every, on_every = {}, args.save_every, checkpoint
     if args.digest:
