@@ -393,10 +393,17 @@ MDQ_API int mdq_probe_forces(const mdq_ipcs_desc* d, int32_t nfields, const doub
  * boundary-eliminated pressure matrix (K1s, as written by mdq_ipcs_assemble / mdq_ipcs_setup_matfree) - recursive
  * coordinate bisection into 8 parts, vertex separator, dense inverses of the interior blocks and of the Schur
  * complement by Gauss-Jordan in LDS.  The pd_* arrays of `d` must be allocated with capacities NPART >= 8,
- * NPW >= 8 * 112^2, NPF >= 8 * 112 * 48, NPGI >= 8 * 48, NPS >= 112^2 + 8 * 48^2 (the inverse Schur complement in front, scratch behind it), NPGK >= 112 * 16 (written here although the
+ * NPW >= 8 * 112^2, NPF >= 8 * 112 * 48, NPGI >= 8 * 48, NPS >= 112^2 + 8 * 48^2 (the inverse Schur complement in front, one 48^2 scratch slice per subdomain behind it: an
+ * environment with fewer subdomains is accepted with less, see -2 below), NPGK >= 112 * 16 (written here although the
  * descriptor declares them const: they are this call's outputs).  status (device int32 [B], may be NULL): 0 ok;
  * < 0: the mesh exceeds those limits - its header says nparts = 0 and mdq_ipcs_evolve (pd_enabled = 1) runs the
- * Krylov pressure solve for that environment.
+ * Krylov pressure solve for that environment.  The codes, in the order they are checked, each for ONE environment:
+ *   -1  nv outside [1, 1024] (nothing but the header and the status is written);
+ *   -2  a subdomain with more than 112 interior nodes, more than 112 separator nodes, more subdomains than NPART, or
+ *       NPS < 112^2 + 48^2 * (its number of subdomains);
+ *   -3  more entries of K[G, I] than NPGK;
+ *   -4  a subdomain touching more than 48 separator nodes, or its blocks beyond NPW / NPF / NPGI.
+ * A refused environment may have written part of its own [b] slices of the pd_* arrays, never another one's.
  */
 MDQ_API int mdq_ipcs_factorize_pressure(const mdq_ipcs_desc* d, int32_t* status, void* stream);
 

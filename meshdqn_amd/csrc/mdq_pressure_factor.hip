@@ -317,7 +317,9 @@ __global__ __launch_bounds__(TH) void pressure_factor_kernel(mdq_ipcs_desc d, in
   {
     int mmax = 0;
     for (int s = 0; s < nparts; ++s) mmax = max(mmax, ms[s]);
-    if (mmax > MMAX || nG > NGMAX || nparts > d.NPART || (int64_t)NGMAX * NGMAX + (int64_t)PARTS * GMAX * GMAX > d.NPS) {
+    // (the room behind the inverse Schur complement: one slice per subdomain THIS environment has - a small mesh next to
+    // a refused one stays direct)
+    if (mmax > MMAX || nG > NGMAX || nparts > d.NPART || (int64_t)NGMAX * NGMAX + (int64_t)nparts * GMAX * GMAX > d.NPS) {
       fail(-2);
       return;
     }
