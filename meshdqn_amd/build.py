@@ -25,14 +25,17 @@ RESOURCES = os.path.join(HERE, "libmeshdqn_hip.resources.json")   # per-kernel V
 OBJ = os.path.join(ROOT, "build", "obj")
 ARCH = "gfx950"
 
-# translation unit -> (source, extra flags, the .hip files it includes besides itself).  mdq_ipcs.hip is compiled in
+# translation unit -> (source, extra flags, the .hip files it includes besides itself, transitively: they are part of the
+# object cache's key - tests/test_build_units_cpu.py holds the lists to the #include lines).  mdq_ipcs.hip is compiled in
 # parts (-DMDQ_IPCS_PART=k: each part instantiates the kernels of some operator modes and their launchers; part 0 also
-# holds the entry points) because it alone took a minute as one unit.
+# holds the entry points) because it alone took a minute as one unit.  Its fragments are compiled by part 0 only, but
+# every part's source names them, so every part lists them.
+IPCS_FRAGMENTS = ["mdq_ipcs_setup.hip", "mdq_ipcs_inflow.hip"]
 UNITS = {
-    "ipcs0": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=0"], []),
-    "ipcs1": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=1"], []),
-    "ipcs2": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=2"], []),
-    "ipcs3": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=3"], []),
+    "ipcs0": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=0"], IPCS_FRAGMENTS),
+    "ipcs1": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=1"], IPCS_FRAGMENTS),
+    "ipcs2": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=2"], IPCS_FRAGMENTS),
+    "ipcs3": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=3"], IPCS_FRAGMENTS),
     "pressure_factor": ("mdq_pressure_factor.hip", [], []),
     "tilemaps": ("mdq_tilemaps.hip", [], []),
     "gcn": ("mdq_tu_gcn.hip", [], ["mdq_gcn.hip", "mdq_gcn_train.hip"]),

@@ -786,3 +786,47 @@ extern "C" int mdq_env_topology_host(const mdq_env_topo_desc* d, int32_t nthread
   mdq_host::Pool::get().parallel_for(D.B, T, [&](int b) { status[b] = mdq_host::topology_one(D, b); });
   return 0;
 }
+
+// DOLFIN MeshSmoothing::smooth restated for the host (flow_solver.py:65-67, 236-237).
+extern "C" int mdq_smooth_host(double* x, int32_t nv, const int32_t* cells, int32_t nt, const int64_t* nbr_ptr,
+                               const int64_t* nbr, const int64_t* vc_ptr, const int64_t* vc, const uint8_t* on_boundary,
+                               int32_t iterations) {
+  if (!x || !cells || !nbr_ptr || !nbr || !vc_ptr || !vc || !on_boundary) return mdq_set_error("null argument");
+  (void)nt;
+  const double DOLFIN_EPS = 3.0e-16;
+  for (int it = 0; it < iterations; ++it) {
+    for (int v = 0; v < nv; ++v) {
+      if (on_boundary[v]) continue;
+      const double px = x[2 * v], py = x[2 * v + 1];
+      double cx = 0.0, cy = 0.0;
+      const int64_t n0 = nbr_ptr[v], n1 = nbr_ptr[v + 1];
+      for (int64_t k = n0; k < n1; ++k) {
+        cx += x[2 * nbr[k]];
+        cy += x[2 * nbr[k] + 1];
+      }
+      const double cnt = (double)(n1 - n0);
+      cx /= cnt;
+      cy /= cnt;
+      double rmin = 0.0;
+      for (int64_t k = vc_ptr[v]; k < vc_ptr[v + 1]; ++k) {
+        const int64_t c = vc[k] / 3, loc = vc[k] % 3;
+        const int32_t o0 = cells[3 * c + (loc == 0 ? 1 : 0)], o1 = cells[3 * c + (loc == 2 ? 1 : 2)];
+        const double ax = x[2 * o0], ay = x[2 * o0 + 1];
+        const double tx = x[2 * o1] - ax, ty = x[2 * o1 + 1] - ay;
+        double nx = ty, ny = -tx;
+        const double nn = std::sqrt(nx * nx + ny * ny);
+        nx /= nn;
+        ny /= nn;
+        const double r = std::fabs(nx * (px - ax) + ny * (py - ay));
+        rmin = (rmin == 0.0) ? r : (r < rmin ? r : rmin);
+      }
+      const double dx = cx - px, dy = cy - py;
+      const double r = std::sqrt(dx * dx + dy * dy);
+      if (r < DOLFIN_EPS) continue;
+      const double step = (0.5 * rmin < r) ? 0.5 * rmin : r;
+      x[2 * v] = px + step * dx / r;
+      x[2 * v + 1] = py + step * dy / r;
+    }
+  }
+  return 0;
+}

@@ -26,7 +26,8 @@
 
 // This file is compiled as several translation units (meshdqn_amd/build.py: -DMDQ_IPCS_PART=k), each instantiating the
 // kernels of some operator modes together with their launchers - as ONE unit it took a minute of every rebuild:
-//   part 0  entry points, assembly, matrix-free set-up, probes, the three kernels of mode 3
+//   part 0  entry points, probes, the three kernels of mode 3; assembly and the matrix-free set-up (mdq_ipcs_setup.hip), the
+//           inflow profile and the inlet map (mdq_ipcs_inflow.hip) - fragments that only this part includes
 //   part 1  evolve_kernel<0 / 1> (assembled SELL operators)
 //   part 2  evolve_kernel<5> (element tiles, global vectors), evolve_team_kernel (mode 4)
 //   part 3  the kernels of mode 2 (element tiles, LDS / register vectors: the reproducible mode of the long runs)
@@ -298,567 +299,11 @@ __device__ __forceinline__ void p2_dphi_one(int j, double l0, double l1, double 
   dy = 4.0 * (la * dby + lb * day);
 }
 
-// ================================================================== assembly
-
-// B^{cd}_e[i][j] = int_{outflow facet k of cell e} phi_i (d_c phi_j) n_d ds
-// (`- dot(mu*nabla_grad(U)*n, v)*ds`, flow_solver.py:109), 2-point Gauss (degree 3 integrand).
-__device__ inline void outflow_entry(const EnvView& v, int e, int k, int i, int j, const Geo& g, double (&Bcd)[2][2]) {
-  double X[3][2];
-  load_cell_coords(v, e, X);
-  const Facet f = facet_geometry(X, k);
-  Bcd[0][0] = Bcd[0][1] = Bcd[1][0] = Bcd[1][1] = 0.0;
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const double s = c_tab.gx[q], w = c_tab.gw[q] * f.len;
-    const double xi = f.ra[0] + s * (f.rb[0] - f.ra[0]);
-    const double eta = f.ra[1] + s * (f.rb[1] - f.ra[1]);
-    const double l0 = 1.0 - xi - eta;
-    const double phi = p2_phi_one(i, l0, xi, eta);
-    double dx, dy;
-    p2_dphi_one(j, l0, xi, eta, dx, dy);
-    const double gxp = g.j00 * dx + g.j10 * dy;  // physical d/dx phi_j
-    const double gyp = g.j01 * dx + g.j11 * dy;
-    Bcd[0][0] += w * phi * gxp * f.nx;
-    Bcd[0][1] += w * phi * gxp * f.ny;
-    Bcd[1][0] += w * phi * gyp * f.nx;
-    Bcd[1][1] += w * phi * gyp * f.ny;
-  }
-}
-
 #if MDQ_IN_PART(0)
-static __global__ __launch_bounds__(WG) void assemble_kernel(mdq_ipcs_desc d) {
-  const int b = blockIdx.x;
-  EnvView v = env_view(d, b);
-  v.nnz2 = v.rowptr2[v.n2];
-  v.nnz1 = v.rowptr1[v.nv];
-  const int tid = threadIdx.x;
-  const double a = v.rho / v.dt, mu = v.mu;
-
-  // ---- phase 0: affine geometry per triangle
-  for (int e = tid; e < v.nt; e += WG) {
-    double X[3][2];
-    load_cell_coords(v, e, X);
-    const double J00 = X[1][0] - X[0][0], J01 = X[2][0] - X[0][0];
-    const double J10 = X[1][1] - X[0][1], J11 = X[2][1] - X[0][1];
-    const double det = J00 * J11 - J01 * J10;
-    v.geom[0 * v.NT + e] = J11 / det;
-    v.geom[1 * v.NT + e] = -J01 / det;
-    v.geom[2 * v.NT + e] = -J10 / det;
-    v.geom[3 * v.NT + e] = J00 / det;
-    v.geom[4 * v.NT + e] = fabs(det);
-  }
-  __syncthreads();
-
-  // position of entry j of row r inside the SELL-64 arrays
-  auto pos2 = [&](int r, int j) { return v.sl2_off[r >> 6] + j * 64 + (r & 63); };
-  auto pos1 = [&](int r, int j) { return v.sl1_off[r >> 6] + j * 64 + (r & 63); };
-
-  // ---- phase 1: full (pre-BC) operator values, one thread per non-zero
-  for (int k = tid; k < v.nnz2; k += WG) {
-    double m = 0.0, kxx = 0.0, kxy = 0.0, kyx = 0.0, kyy = 0.0;
-    double bxx = 0.0, bxy = 0.0, byx = 0.0, byy = 0.0;
-    const int s0 = v.asm2_ptr[k], s1 = v.asm2_ptr[k + 1];
-    int row = 0;
-    for (int s = s0; s < s1; ++s) {
-      const int slot = v.asm2_src[s];
-      const int e = slot / 36, ij = slot - e * 36, i = ij / 6, j = ij - i * 6;
-      if (s == s0) row = v.cell_dofs[i * v.NT + e];
-      const Geo g = load_geo(v, e);
-      m += g.det * c_tab.Mhat[i][j];
-      // K^{ab}_ij = det * sum_{cd} Jinv[c][a] Jinv[d][b] Ghat[c][d][i][j]
-      const double g00 = c_tab.Ghat[0][0][i][j], g01 = c_tab.Ghat[0][1][i][j];
-      const double g10 = c_tab.Ghat[1][0][i][j], g11 = c_tab.Ghat[1][1][i][j];
-      // Jinv[c][a]: c = reference index (row), a = physical index (col)
-      const double Ja[2][2] = {{g.j00, g.j01}, {g.j10, g.j11}};
-      kxx += g.det * (Ja[0][0] * (Ja[0][0] * g00 + Ja[1][0] * g01) + Ja[1][0] * (Ja[0][0] * g10 + Ja[1][0] * g11));
-      kxy += g.det * (Ja[0][0] * (Ja[0][1] * g00 + Ja[1][1] * g01) + Ja[1][0] * (Ja[0][1] * g10 + Ja[1][1] * g11));
-      kyx += g.det * (Ja[0][1] * (Ja[0][0] * g00 + Ja[1][0] * g01) + Ja[1][1] * (Ja[0][0] * g10 + Ja[1][0] * g11));
-      kyy += g.det * (Ja[0][1] * (Ja[0][1] * g00 + Ja[1][1] * g01) + Ja[1][1] * (Ja[0][1] * g10 + Ja[1][1] * g11));
-      const int ko = v.cell_outflow[e];
-      if (ko >= 0) {
-        double Bcd[2][2];
-        outflow_entry(v, e, ko, i, j, g, Bcd);
-        bxx += Bcd[0][0];
-        bxy += Bcd[0][1];
-        byx += Bcd[1][0];
-        byy += Bcd[1][1];
-      }
-    }
-    const double L = kxx + kyy;
-    // block(c,d) = a M delta_cd + mu/2 (delta_cd L + K^{dc}) - mu/2 B^{cd}
-    double4 blk;
-    blk.x = a * m + 0.5 * mu * (L + kxx) - 0.5 * mu * bxx;
-    blk.y = 0.5 * mu * kyx - 0.5 * mu * bxy;
-    blk.z = 0.5 * mu * kxy - 0.5 * mu * byx;
-    blk.w = a * m + 0.5 * mu * (L + kyy) - 0.5 * mu * byy;
-    const int ps = pos2(row, k - v.rowptr2[row]);
-    reinterpret_cast<double4*>(v.A1)[ps] = blk;
-    v.Ms[ps] = m;
-  }
-  for (int k = tid; k < v.nnz1; k += WG) {
-    double kk = 0.0;
-    const int s0 = v.asm1_ptr[k], s1 = v.asm1_ptr[k + 1];
-    int row = 0;
-    for (int s = s0; s < s1; ++s) {
-      const int slot = v.asm1_src[s];
-      const int e = slot / 9, ij = slot - e * 9, i = ij / 3, j = ij - i * 3;
-      if (s == s0) row = v.cell_dofs[i * v.NT + e];
-      const Geo g = load_geo(v, e);
-      // grad lambda_i = Jinv^T dl_i, dl = (-1,-1),(1,0),(0,1)
-      const double dix = sel3(i, -g.j00 - g.j10, g.j00, g.j10), diy = sel3(i, -g.j01 - g.j11, g.j01, g.j11);
-      const double djx = sel3(j, -g.j00 - g.j10, g.j00, g.j10), djy = sel3(j, -g.j01 - g.j11, g.j01, g.j11);
-      kk += 0.5 * g.det * (dix * djx + diy * djy);
-    }
-    v.K1s[pos1(row, k - v.rowptr1[row])] = kk;
-  }
-  // outflow row list of the matrix-free mode 3 (same facet integrals as above, kept separate)
-  if (v.nbo > 0) {
-    const int nbe = v.bo_ptr[v.nbo];
-    for (int t = tid; t < nbe; t += WG) {
-      const int slot = v.bo_src[t];
-      const int e = slot / 36, ij = slot - e * 36, i = ij / 6, j = ij - i * 6;
-      const Geo g = load_geo(v, e);
-      double Bcd[2][2];
-      outflow_entry(v, e, v.cell_outflow[e], i, j, g, Bcd);
-      reinterpret_cast<double4*>(v.bo_val)[t] = make_double4(Bcd[0][0], Bcd[0][1], Bcd[1][0], Bcd[1][1]);
-    }
-  }
-  __syncthreads();
-
-  // ---- phase 2: Dirichlet lifting vectors and diagonals, one thread per row
-  for (int r = tid; r < v.n2; r += WG) {
-    double l1x = 0.0, l1y = 0.0, l3x = 0.0, dx = 1.0, dy = 1.0, dm = 1.0;
-    const bool fr = v.bcu_flag[r] != 0;
-    const int k0 = v.rowptr2[r], len = v.rowptr2[r + 1] - k0;
-    for (int j = 0; j < len; ++j) {
-      const int c = v.colidx2[k0 + j], ps = pos2(r, j);
-      const double4 blk = reinterpret_cast<const double4*>(v.A1)[ps];
-      if (v.bcu_flag[c]) {
-        const double gx = v.bcu_gx[c];  // gy = 0 for every BC of the reference
-        l1x += blk.x * gx;
-        l1y += blk.z * gx;
-        l3x += v.Ms[ps] * gx;
-      }
-      if (c == r && !fr) {
-        dx = blk.x;
-        dy = blk.w;
-        dm = v.Ms[ps];
-      }
-    }
-    v.lift1[r] = make_double2(l1x, l1y);
-    v.lift3[r] = make_double2(l3x, 0.0);
-    v.idiag1[r] = make_double2(1.0 / dx, 1.0 / dy);
-    v.sdiagM[r] = sqrt(dm);
-  }
-  for (int r = tid; r < v.nv; r += WG) {
-    double dk = 1.0;
-    if (!v.bcp_flag[r]) {
-      const int k0 = v.rowptr1[r], len = v.rowptr1[r + 1] - k0;
-      for (int j = 0; j < len; ++j)
-        if (v.colidx1[k0 + j] == r) dk = v.K1s[pos1(r, j)];
-    }
-    v.sdiagK[r] = sqrt(dk);
-  }
-  __syncthreads();
-
-  // ---- phase 3: symmetric elimination + Jacobi scaling (+ zero the SELL padding)
-  const int rows2 = ((v.n2 + 63) >> 6) << 6;
-  for (int r = tid; r < rows2; r += WG) {
-    const int width = (v.sl2_off[(r >> 6) + 1] - v.sl2_off[r >> 6]) >> 6;
-    int len = 0;
-    if (r < v.n2) {
-      const bool fr = v.bcu_flag[r] != 0;
-      const double2 id = v.idiag1[r];
-      const double sr = v.sdiagM[r];
-      const int k0 = v.rowptr2[r];
-      len = v.rowptr2[r + 1] - k0;
-      for (int j = 0; j < len; ++j) {
-        const int c = v.colidx2[k0 + j], ps = pos2(r, j);
-        const bool fc = v.bcu_flag[c] != 0;
-        double4 blk = reinterpret_cast<const double4*>(v.A1)[ps];
-        double m = v.Ms[ps];
-        if (fr || fc) {
-          const double one = (c == r) ? 1.0 : 0.0;
-          blk = make_double4(one, 0.0, 0.0, one);
-          m = one;
-        } else {
-          blk.x *= id.x;
-          blk.y *= id.x;
-          blk.z *= id.y;
-          blk.w *= id.y;
-          m = m / (sr * v.sdiagM[c]);
-        }
-        reinterpret_cast<double4*>(v.A1)[ps] = blk;
-        v.Ms[ps] = m;
-      }
-    }
-    for (int j = len; j < width; ++j) {
-      const int ps = pos2(r, j);
-      reinterpret_cast<double4*>(v.A1)[ps] = make_double4(0.0, 0.0, 0.0, 0.0);
-      v.Ms[ps] = 0.0;
-    }
-  }
-  const int rows1 = ((v.nv + 63) >> 6) << 6;
-  for (int r = tid; r < rows1; r += WG) {
-    const int width = (v.sl1_off[(r >> 6) + 1] - v.sl1_off[r >> 6]) >> 6;
-    int len = 0;
-    if (r < v.nv) {
-      const bool fr = v.bcp_flag[r] != 0;
-      const double sr = v.sdiagK[r];
-      const int k0 = v.rowptr1[r];
-      len = v.rowptr1[r + 1] - k0;
-      for (int j = 0; j < len; ++j) {
-        const int c = v.colidx1[k0 + j], ps = pos1(r, j);
-        const bool fc = v.bcp_flag[c] != 0;
-        double kk = v.K1s[ps];
-        if (fr || fc)
-          kk = (c == r) ? 1.0 : 0.0;
-        else
-          kk = kk / (sr * v.sdiagK[c]);
-        v.K1s[ps] = kk;
-      }
-    }
-    for (int j = len; j < width; ++j) v.K1s[pos1(r, j)] = 0.0;
-  }
-}
+}  // namespace mdq
+#include "mdq_ipcs_setup.hip"
+namespace mdq {
 #endif
-
-// ================================================================== matrix-free operator setup
-//
-// Everything mode 3 (with the CG pressure solver) needs from a NEW mesh, without any global sparsity pattern:
-// geometry, outflow-row blocks, Jacobi diagonals and Dirichlet lifting vectors of A1 / M accumulated row-wise from
-// the element matrices (dof <- element-slot gathers g2/g1), the scaled + BC-eliminated P1 Laplacian in SELL-64.
-// Same numbers as assemble_kernel up to the summation order.  One workgroup per environment.
-#ifdef MDQ_SETUP_TRACE
-static __device__ long long mdq_st_trace_buf[16];
-#define ST_STAMP(k) { __syncthreads(); const long long tn_ = __builtin_amdgcn_s_memtime(); if (threadIdx.x == 0 && blockIdx.x == 0) mdq_st_trace_buf[k] += tn_ - tq_; tq_ = tn_; }
-#if MDQ_IN_PART(0)
-extern "C" MDQ_API int mdq_st_trace_host(long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mdq_st_trace_buf), sizeof(long long) * 16) != hipSuccess) return -1;
-  if (reset) { long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(mdq_st_trace_buf), z, sizeof z) != hipSuccess) return -1; }
-  return 0;
-}
-#endif
-#else
-#define ST_STAMP(k)
-#endif
-
-// ST: the per-cell / per-dof data the row loops chase (geometry, cell dofs, Dirichlet flags and values, the P1 scaling) is
-// staged in LDS first.  The row loops are chains of dependent loads (slot -> geometry / dofs -> flags -> values, per
-// incident cell of every row): from global memory each level is an L2 round trip and the kernel was 270 k cycles of
-// latency (P2 rows 134 k, P1 values 71 k, P1 diagonal 33 k); from LDS a level costs a tenth of that.
-// 52 NT + 9 N2 + 9 NV bytes: 119 KB for ys930; a mesh that does not fit runs the unstaged instance.
-constexpr int SWG = MDQ_SETUP_WG;   // threads of the set-up kernel (its row loops are latency chains: more rows in flight)
-// LS (with ST): the dof <- element-slot lists (g1 / g2 pointers and slots, 16-bit in LDS) are staged as well when they fit:
-// the row loops then have no dependent global load left.
-// GEO = false with ST (round 6, the meshes whose 40 B of geometry per cell do not fit: the red-refined lab meshes): only the
-// INDEX data is staged - cell dofs (16-bit), Dirichlet flags, the P1 scaling - 12 NT + N2 + 9 NV bytes (118 KB for the refined
-// ys930); geometry and Dirichlet values come from global memory.  Of a slot's chain slot -> cell dofs -> flags (-> values at
-// boundary cells only) the two inner levels are LDS round trips then; the unstaged instance paid an L2 round trip for each.
-template <bool ST, bool LS = false, bool GEO = ST>
-__global__ __launch_bounds__(SWG) void setup_matfree_kernel(mdq_ipcs_desc d) {
-  static_assert(ST || !GEO, "geometry is staged together with the index data only");
-  static_assert(GEO || !LS, "the slot lists are staged in the full instance only");
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const EnvView v = env_view(d, b);
-  const double a = v.rho / v.dt, mu = v.mu;
-  extern __shared__ __align__(16) unsigned char setup_lds[];
-  double* sGeo = reinterpret_cast<double*>(setup_lds);             // [5][NT]   (GEO)
-  double* sGx = sGeo + (GEO ? 5 * (size_t)d.NT : 0);                // [N2]      (GEO)
-  double* sSd = sGx + (GEO ? d.N2 : 0);                             // [NV]
-  uint16_t* sCd = reinterpret_cast<uint16_t*>(sSd + d.NV);          // [6][NT]
-  uint8_t* sFl = reinterpret_cast<uint8_t*>(sCd + 6 * (size_t)d.NT);  // [N2]
-  uint8_t* sPf = sFl + d.N2;                                        // [NV]
-  uint16_t* sG2p = reinterpret_cast<uint16_t*>(sPf + d.NV + ((d.N2 + d.NV) & 1));   // [N2 + 1]  (LS)
-  uint16_t* sG2s = sG2p + d.N2 + 1;                                 // [6 NT]
-  uint16_t* sG1p = sG2s + 6 * (size_t)d.NT;                         // [NV + 1]
-  uint16_t* sG1s = sG1p + d.NV + 1;                                 // [3 NT]
-  auto g2p = [&](int i) -> int { return LS ? (int)sG2p[i] : v.g2_ptr[i]; };
-  auto g2s = [&](int i) -> int { return LS ? (int)sG2s[i] : v.g2_src[i]; };
-  auto g1p = [&](int i) -> int { return LS ? (int)sG1p[i] : v.g1_ptr[i]; };
-  auto g1s = [&](int i) -> int { return LS ? (int)sG1s[i] : v.g1_src[i]; };
-  auto geo = [&](int e) -> Geo {
-    if (!GEO) return load_geo(v, e);
-    Geo g;
-    g.j00 = sGeo[0 * v.NT + e];
-    g.j01 = sGeo[1 * v.NT + e];
-    g.j10 = sGeo[2 * v.NT + e];
-    g.j11 = sGeo[3 * v.NT + e];
-    g.det = sGeo[4 * v.NT + e];
-    return g;
-  };
-  auto cdof = [&](int j, int e) -> int { return ST ? (int)sCd[j * v.NT + e] : v.cell_dofs[j * v.NT + e]; };
-  auto uflag = [&](int i) -> bool { return ST ? sFl[i] != 0 : v.bcu_flag[i] != 0; };
-  auto ugx = [&](int i) -> double { return GEO ? sGx[i] : v.bcu_gx[i]; };
-  auto pflag = [&](int i) -> bool { return ST ? sPf[i] != 0 : v.bcp_flag[i] != 0; };
-  auto sdk = [&](int i) -> double { return ST ? sSd[i] : v.sdiagK[i]; };
-  if (ST) {
-    for (int j = 0; j < 6; ++j)
-      for (int e = tid; e < v.nt; e += SWG) sCd[j * v.NT + e] = (uint16_t)v.cell_dofs[j * v.NT + e];
-    for (int i = tid; i < v.n2; i += SWG) {
-      sFl[i] = v.bcu_flag[i];
-      if (GEO) sGx[i] = v.bcu_gx[i];
-    }
-    for (int i = tid; i < v.nv; i += SWG) sPf[i] = v.bcp_flag[i];
-    if (LS) {
-      for (int i = tid; i <= v.n2; i += SWG) sG2p[i] = (uint16_t)v.g2_ptr[i];
-      for (int i = tid; i < 6 * v.nt; i += SWG) sG2s[i] = (uint16_t)v.g2_src[i];
-      for (int i = tid; i <= v.nv; i += SWG) sG1p[i] = (uint16_t)v.g1_ptr[i];
-      for (int i = tid; i < 3 * v.nt; i += SWG) sG1s[i] = (uint16_t)v.g1_src[i];
-    }
-  }
-  // reference-element tables in LDS: the row loops index them with the (lane-dependent) local row of a slot; from
-  // constant memory that is one more dependent round trip per local column inside the conditional column loop
-  __shared__ double sMhat[6][6];
-  __shared__ double sGhat[2][2][6][6];
-  for (int q = tid; q < 36; q += SWG) sMhat[q / 6][q % 6] = c_tab.Mhat[q / 6][q % 6];
-  for (int q = tid; q < 144; q += SWG) sGhat[q / 72][(q / 36) % 2][(q / 6) % 6][q % 6] = c_tab.Ghat[q / 72][(q / 36) % 2][(q / 6) % 6][q % 6];
-#ifdef MDQ_SETUP_TRACE
-  long long tq_ = __builtin_amdgcn_s_memtime();
-#endif
-  for (int e = tid; e < v.nt; e += SWG) {
-    double X[3][2];
-    load_cell_coords(v, e, X);
-    const double J00 = X[1][0] - X[0][0], J01 = X[2][0] - X[0][0];
-    const double J10 = X[1][1] - X[0][1], J11 = X[2][1] - X[0][1];
-    const double det = J00 * J11 - J01 * J10;
-    const double q0 = J11 / det, q1 = -J01 / det, q2 = -J10 / det, q3 = J00 / det, q4 = fabs(det);
-    v.geom[0 * v.NT + e] = q0;
-    v.geom[1 * v.NT + e] = q1;
-    v.geom[2 * v.NT + e] = q2;
-    v.geom[3 * v.NT + e] = q3;
-    v.geom[4 * v.NT + e] = q4;
-    if (GEO) {
-      sGeo[0 * v.NT + e] = q0;
-      sGeo[1 * v.NT + e] = q1;
-      sGeo[2 * v.NT + e] = q2;
-      sGeo[3 * v.NT + e] = q3;
-      sGeo[4 * v.NT + e] = q4;
-    }
-  }
-  __syncthreads();
-  ST_STAMP(0)
-  if (v.nbo > 0) {
-    const int nbe = v.bo_ptr[v.nbo];
-    for (int t = tid; t < nbe; t += SWG) {
-      const int slot = v.bo_src[t];
-      const int e = slot / 36, ij = slot - e * 36, i = ij / 6, j = ij - i * 6;
-      const Geo g = load_geo(v, e);
-      double Bcd[2][2];
-      outflow_entry(v, e, v.cell_outflow[e], i, j, g, Bcd);
-      reinterpret_cast<double4*>(v.bo_val)[t] = make_double4(Bcd[0][0], Bcd[0][1], Bcd[1][0], Bcd[1][1]);
-    }
-  }
-  ST_STAMP(1)
-  // ---- P2 rows: raw diagonals (kept in idiag1 / sdiagM until the outflow rows have been corrected) and lifts
-  for (int r = tid; r < v.n2; r += SWG) {
-    double l1x = 0.0, l1y = 0.0, l3x = 0.0, dx = 0.0, dy = 0.0, dm = 0.0;
-    // incident cells two at a time: the four dependent load levels of a cell (slot -> geometry / dofs -> Dirichlet
-    // flags -> values) are paid once per pair; the second cell of an odd tail is the first one again, not added
-    const int s0 = g2p(r), s1 = g2p(r + 1);
-    for (int s = s0; s < s1; s += 2) {
-      const bool two = s + 1 < s1;
-      int ee[2], ii[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int slot = g2s((u == 1 && two) ? s + 1 : s);
-        ee[u] = slot / 6;
-        ii[u] = slot - ee[u] * 6;
-      }
-      Geo gg[2];
-      int cj[2][6];
-      bool fj[2][6];
-      double gj[2][6];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        gg[u] = geo(ee[u]);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) cj[u][j] = cdof(j, ee[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int j = 0; j < 6; ++j) fj[u][j] = uflag(cj[u][j]);
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int j = 0; j < 6; ++j) gj[u][j] = ugx(cj[u][j]);
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        if (u == 1 && !two) break;
-        const Geo g = gg[u];
-        const int i = ii[u];
-        const double Ja[2][2] = {{g.j00, g.j01}, {g.j10, g.j11}};
-        // The diagonal term with the tables indexed by the lane's own i: ONE block for the wave.  (As a column loop
-        // unrolled over j with `if (j != i && !fc) continue` the wave ran all six blocks - its lanes sit at different i -
-        // i.e. ~270 fp64 instructions per cell for one term per lane.)  The Dirichlet columns follow in ascending j as
-        // before; only waves that hold cells at the boundary enter those blocks.
-        {
-          const double m = g.det * sMhat[i][i];
-          const double g00 = sGhat[0][0][i][i], g01 = sGhat[0][1][i][i];
-          const double g10 = sGhat[1][0][i][i], g11 = sGhat[1][1][i][i];
-          const double kxx = g.det * (Ja[0][0] * (Ja[0][0] * g00 + Ja[1][0] * g01) + Ja[1][0] * (Ja[0][0] * g10 + Ja[1][0] * g11));
-          const double kyy = g.det * (Ja[0][1] * (Ja[0][1] * g00 + Ja[1][1] * g01) + Ja[1][1] * (Ja[0][1] * g10 + Ja[1][1] * g11));
-          const double L = kxx + kyy;
-          dx += a * m + 0.5 * mu * (L + kxx);
-          dy += a * m + 0.5 * mu * (L + kyy);
-          dm += m;
-        }
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-          if (!fj[u][j]) continue;
-          const double m = g.det * sMhat[i][j];
-          const double g00 = sGhat[0][0][i][j], g01 = sGhat[0][1][i][j];
-          const double g10 = sGhat[1][0][i][j], g11 = sGhat[1][1][i][j];
-          const double kxx = g.det * (Ja[0][0] * (Ja[0][0] * g00 + Ja[1][0] * g01) + Ja[1][0] * (Ja[0][0] * g10 + Ja[1][0] * g11));
-          const double kxy = g.det * (Ja[0][0] * (Ja[0][1] * g00 + Ja[1][1] * g01) + Ja[1][0] * (Ja[0][1] * g10 + Ja[1][1] * g11));
-          const double kyy = g.det * (Ja[0][1] * (Ja[0][1] * g00 + Ja[1][1] * g01) + Ja[1][1] * (Ja[0][1] * g10 + Ja[1][1] * g11));
-          const double L = kxx + kyy;
-          const double bx = a * m + 0.5 * mu * (L + kxx), bz = 0.5 * mu * kxy;
-          const double gx = gj[u][j];
-          l1x += bx * gx;
-          l1y += bz * gx;
-          l3x += m * gx;
-        }
-      }
-    }
-    v.lift1[r] = make_double2(l1x, l1y);
-    v.lift3[r] = make_double2(l3x, 0.0);
-    v.idiag1[r] = make_double2(dx, dy);
-    v.sdiagM[r] = dm;
-  }
-  __syncthreads();
-  ST_STAMP(2)
-  // outflow rows: - mu/2 B on the diagonal and in the lifts (one thread per row: no conflicts)
-  for (int t = tid; t < v.nbo; t += SWG) {
-    const int row = v.bo_rows[t];
-    double2 dg = v.idiag1[row], l1 = v.lift1[row];
-    for (int k = v.bo_ptr[t]; k < v.bo_ptr[t + 1]; ++k) {
-      const double4 bv = reinterpret_cast<const double4*>(v.bo_val)[k];
-      const int c = v.bo_col[k];
-      if (c == row) {
-        dg.x -= 0.5 * mu * bv.x;
-        dg.y -= 0.5 * mu * bv.w;
-      }
-      if (uflag(c)) {
-        const double gx = ugx(c);
-        l1.x -= 0.5 * mu * bv.x * gx;
-        l1.y -= 0.5 * mu * bv.z * gx;
-      }
-    }
-    v.idiag1[row] = dg;
-    v.lift1[row] = l1;
-  }
-  __syncthreads();
-  for (int r = tid; r < v.n2; r += SWG) {
-    const bool fr = uflag(r);
-    const double2 dg = v.idiag1[r];
-    v.idiag1[r] = fr ? make_double2(1.0, 1.0) : make_double2(1.0 / dg.x, 1.0 / dg.y);
-    v.sdiagM[r] = fr ? 1.0 : sqrt(v.sdiagM[r]);
-  }
-  ST_STAMP(3)
-  // ---- P1 Laplacian: entry (r, c) = sum over the cells of r that contain c of |T| grad(l_r).grad(l_c)
-  auto k1_entry = [&](int r, int c) {
-    double kk = 0.0;
-    for (int s = g1p(r); s < g1p(r + 1); ++s) {
-      const int slot = g1s(s);
-      const int e = slot / 3, i = slot - e * 3;
-      int j = -1;
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-        if (cdof(q, e) == c) j = q;
-      if (j < 0) continue;
-      const Geo g = geo(e);
-      const double dix = sel3(i, -g.j00 - g.j10, g.j00, g.j10), diy = sel3(i, -g.j01 - g.j11, g.j01, g.j11);
-      const double djx = sel3(j, -g.j00 - g.j10, g.j00, g.j10), djy = sel3(j, -g.j01 - g.j11, g.j01, g.j11);
-      kk += 0.5 * g.det * (dix * djx + diy * djy);
-    }
-    return kk;
-  };
-  for (int r = tid; r < v.nv; r += SWG) {
-    const double sd = pflag(r) ? 1.0 : sqrt(k1_entry(r, r));
-    v.sdiagK[r] = sd;
-    if (ST) sSd[r] = sd;
-  }
-  __syncthreads();
-  ST_STAMP(4)
-  const int rows1 = ((v.nv + 63) >> 6) << 6;
-  constexpr int KW = 16;   // widest row handled by the one-pass path (vertex degree + 1; wider rows: generic path)
-  for (int r = tid; r < rows1; r += SWG) {
-    const int off = v.sl1_off[r >> 6];
-    const int width = (v.sl1_off[(r >> 6) + 1] - off) >> 6;
-    if (width <= KW) {
-      // ONE pass over the cells of the row: every cell adds its three entries (r, c_q) to the row's column list held in
-      // registers (the generic path walks all cells of the row again for every entry: 7x the dependent loads; it
-      // was 47 % of this kernel).  Same contributions in the same (cell) order per entry: same bits.
-      int cols[KW];
-      double vals[KW];
-      int prev = -1;
-#pragma unroll
-      for (int j = 0; j < KW; ++j) {
-        int c = -1;
-        if (j < width && r < v.nv) {
-          c = v.sl1_col[off + j * 64 + (r & 63)];
-          if (c > prev) prev = c; else c = -1;   // (columns ascend; the padding repeats the row index)
-        }
-        cols[j] = c;
-        vals[j] = 0.0;
-      }
-      if (r < v.nv) {
-        if (pflag(r)) {
-#pragma unroll
-          for (int j = 0; j < KW; ++j) vals[j] = cols[j] == r ? 1.0 : 0.0;
-        } else {
-          for (int s_ = g1p(r); s_ < g1p(r + 1); ++s_) {
-            const int slot = g1s(s_);
-            const int e = slot / 3, i = slot - e * 3;
-            const Geo g = geo(e);
-            int cq[3];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) cq[q] = cdof(q, e);
-            const double dix = sel3(i, -g.j00 - g.j10, g.j00, g.j10), diy = sel3(i, -g.j01 - g.j11, g.j01, g.j11);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-              const double djx = sel3(q, -g.j00 - g.j10, g.j00, g.j10), djy = sel3(q, -g.j01 - g.j11, g.j01, g.j11);
-              const double val = 0.5 * g.det * (dix * djx + diy * djy);
-#pragma unroll
-              for (int j = 0; j < KW; ++j) vals[j] += cols[j] == cq[q] ? val : 0.0;
-            }
-          }
-          const double sr = sdk(r);
-#pragma unroll
-          for (int j = 0; j < KW; ++j) {
-            if (cols[j] >= 0) {
-              const int c = cols[j];
-              vals[j] = pflag(c) ? (c == r ? 1.0 : 0.0) : vals[j] / (sr * sdk(c));
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < KW; ++j)
-        if (j < width) v.K1s[off + j * 64 + (r & 63)] = cols[j] >= 0 ? vals[j] : 0.0;
-      continue;
-    }
-    int prev = -1;
-    for (int j = 0; j < width; ++j) {
-      const int ps = off + j * 64 + (r & 63);
-      double kk = 0.0;
-      if (r < v.nv) {
-        const int c = v.sl1_col[ps];
-        if (c > prev) {  // real entry (columns ascend; the padding repeats the row index)
-          prev = c;
-          if (pflag(r) || pflag(c))
-            kk = (c == r) ? 1.0 : 0.0;
-          else
-            kk = k1_entry(r, c) / (sdk(r) * sdk(c));
-        }
-      }
-      v.K1s[ps] = kk;
-    }
-  }
-  ST_STAMP(5)
-}
 
 // ================================================================== element right-hand sides
 
@@ -5497,262 +4942,9 @@ static hipError_t upload_tables() {
 }
 
 #if MDQ_IN_PART(0)
-// ================================================================== inflow profile (mdq_ipcs_evolve_profile)
-//
-// The inflow of ONE step of a launch sequence: values[b][step] scattered into bcu_gx at the inlet dofs, then lift1 / lift3
-// recomputed on the rows that share a cell with an inlet dof - the three things of the set-up that depend on the Dirichlet
-// vector (the elimination is linear in it and only the inlet is non-zero).  The per-row sums are the "P2 rows" loop of
-// setup_matfree_kernel restated (not shared: that kernel's resource row stays what it is): slots through g2_ptr / g2_src,
-// the cell's geom and cell_dofs, every flagged column j adds bx gx, bz gx, m gx.  A row list is a few dozen rows of ~6 cells, each
-// cell a chain of four dependent loads, so a row is spread over 8 lanes (one slot each) and summed by a fixed shuffle tree:
-// one pass of the workgroup for up to 64 rows, the order fixed, no atomics.  Outflow rows are not in the list (the host
-// refuses such a mesh): their - mu/2 B correction is not re-applied.  Writes bcu_gx[inlet], lift1[rows], lift3[rows] only.
-constexpr int IWG = 512;   // 64 rows x 8 lanes per pass
-static __global__ __launch_bounds__(IWG) void inflow_lift_kernel(mdq_ipcs_desc d, mdq_inflow_profile pr, int nsteps, int step) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const EnvView v = env_view(d, b);
-  const double a = v.rho / v.dt, mu = v.mu;
-  __shared__ double sMhat[6][6];
-  __shared__ double sGhat[2][2][6][6];
-  for (int q = tid; q < 36; q += IWG) sMhat[q / 6][q % 6] = c_tab.Mhat[q / 6][q % 6];
-  for (int q = tid; q < 144; q += IWG) sGhat[q / 72][(q / 36) % 2][(q / 6) % 6][q % 6] = c_tab.Ghat[q / 72][(q / 36) % 2][(q / 6) % 6][q % 6];
-  const int nin = min(pr.n_inlet[b], pr.NIN), nr = min(pr.n_rows[b], pr.NIR);
-  const int32_t* dofs = pr.inlet_dofs + (int64_t)b * pr.NIN;
-  const double* val = pr.values + ((int64_t)b * nsteps + step) * pr.NIN;
-  // (an input of every other entry point, hence const in the descriptor; this one is documented to rewrite its inlet entries)
-  double* gxw = const_cast<double*>(d.bcu_gx) + (int64_t)b * d.N2;
-  for (int k = tid; k < nin; k += IWG) {
-    const int i = dofs[k];
-    if (i >= 0 && i < v.n2) gxw[i] = val[k];
-  }
-  __syncthreads();   // (the new Dirichlet values and the tables are visible to the workgroup)
-  const int32_t* rows = pr.rows + (int64_t)b * pr.NIR;
-  const int sub = tid & 7;
-  for (int base = 0; base < nr; base += IWG / 8) {   // (uniform trip count: every lane takes part in the shuffles)
-    const int q = base + (tid >> 3);
-    const int r = q < nr ? rows[q] : -1;
-    const bool ok = r >= 0 && r < v.n2;
-    double l1x = 0.0, l1y = 0.0, l3x = 0.0;
-    if (ok) {
-      const int s1 = v.g2_ptr[r + 1];
-      for (int s = v.g2_ptr[r] + sub; s < s1; s += 8) {
-        const int slot = v.g2_src[s];
-        const int e = slot / 6, i = slot - e * 6;
-        const Geo g = load_geo(v, e);
-        int cj[6];
-        bool fj[6];
-        double gj[6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) cj[j] = v.cell_dofs[j * v.NT + e];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) fj[j] = v.bcu_flag[cj[j]] != 0;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) gj[j] = fj[j] ? gxw[cj[j]] : 0.0;
-        const double Ja[2][2] = {{g.j00, g.j01}, {g.j10, g.j11}};
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-          if (!fj[j]) continue;
-          const double m = g.det * sMhat[i][j];
-          const double g00 = sGhat[0][0][i][j], g01 = sGhat[0][1][i][j];
-          const double g10 = sGhat[1][0][i][j], g11 = sGhat[1][1][i][j];
-          const double kxx = g.det * (Ja[0][0] * (Ja[0][0] * g00 + Ja[1][0] * g01) + Ja[1][0] * (Ja[0][0] * g10 + Ja[1][0] * g11));
-          const double kxy = g.det * (Ja[0][0] * (Ja[0][1] * g00 + Ja[1][1] * g01) + Ja[1][0] * (Ja[0][1] * g10 + Ja[1][1] * g11));
-          const double kyy = g.det * (Ja[0][1] * (Ja[0][1] * g00 + Ja[1][1] * g01) + Ja[1][1] * (Ja[0][1] * g10 + Ja[1][1] * g11));
-          const double L = kxx + kyy;
-          const double bx = a * m + 0.5 * mu * (L + kxx), bz = 0.5 * mu * kxy;
-          l1x += bx * gj[j];
-          l1y += bz * gj[j];
-          l3x += m * gj[j];
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 4; o > 0; o >>= 1) {
-      l1x += __shfl_down(l1x, o, 8);
-      l1y += __shfl_down(l1y, o, 8);
-      l3x += __shfl_down(l3x, o, 8);
-    }
-    if (ok && sub == 0) {
-      v.lift1[r] = make_double2(l1x, l1y);
-      v.lift3[r] = make_double2(l3x, 0.0);
-    }
-  }
-}
-
-// ================================================================== inlet map of a device-built mesh (mdq_ipcs_build_inlet_map)
-//
-// The tables inflow_lift_kernel reads - inlet dofs and inlet-adjacent rows - for a mesh whose dofs were numbered on the
-// device (the S3 flow leg: every step a new mesh).  The inlet POINTS never change (boundary vertices are neither removed nor
-// moved, the inlet facets lie on the convex hull), only their numbers: the caller hands over the canonical inlet of the
-// ORIGINAL mesh, its y ascending (inlet_y[b][0 .. n_ref[b])), and the kernel finds which dof of this mesh is which point.
-// PRECONDITION: bcu_gx holds what the topology run wrote, the constant parabola - non-zero exactly on the inlet dofs the
-// airfoil / wall conditions do not override (the two corner vertices sit at y = bot / top: overridden, and the parabola is
-// zero there anyway); it runs before any profile step has rewritten bcu_gx.  Reads cell_dofs, coords, nv / nt / ne, bcu_flag,
-// bcu_gx, cell_outflow.  One workgroup per environment, one pass over the dofs and two over the cells:
-//   inlet set   dof i < n2 with bcu_flag[i] != 0 && bcu_gx[i] != 0: a bitmap over n2 in LDS; its position in the set (the
-//               number of set bits below it, from a per-word prefix) is its slot in the LDS lists
-//   y           from a cell that holds the dof: a vertex's coords, or 0.5 * (ya + yb) of the edge opposite vertex k for local
-//               dof 3 + k - the expression of MeshTopology.dof_coords, so the bits agree (an inlet edge has one cell; the
-//               cells of an inlet vertex all store the same bits)
-//   order       rank r = the number of inlet dofs with a smaller y (ties - there are none on an inlet - by slot, so the ranks
-//               are a permutation whatever the input); inlet_dofs[b][r] = that dof, |y - inlet_y[b][r]| <= 1e-12 (top - bot)
-//               with top - bot the extent of the mesh's vertices in y (what the topology run and the host use as H)
-//   rows        every dof with bcu_flag == 0 of every cell that holds an inlet dof: a second bitmap (LDS atomicOr: the result
-//               does not depend on the order), compacted by the same per-word prefix -> unique, ascending, no global atomics
-// map_status[b] (sticky: written only while it is 0) takes the first failure: 1 inlet count != n_ref[b] (or beyond NIN / the
-// 64 slots of the LDS lists), 2 a y differs, 3 more rows than NIR, 4 an inlet-adjacent free row is a row of an outflow facet
-// (inflow_lift_kernel does not re-apply their correction).  A failing environment gets n_inlet = n_rows = 0 and lists of -1.
-// Every index read from the mesh is range-checked and every write stays inside [b][NIN] / [b][NIR] whatever the input.
-constexpr int MWG = 256;       // latency-bound: ~6 cells per thread on the lab meshes, 4 waves = one per SIMD
-constexpr int MAP_BITS = 3584; // the bitmaps cover the meshes of the LDS-resident modes (MF_ROWS * WG rows)
-constexpr int MAP_WORDS = MAP_BITS / 32;
-constexpr int MAP_NIN = 64;    // slots of the LDS inlet lists (lab meshes: about a dozen inlet dofs)
-static __global__ __launch_bounds__(MWG) void inlet_map_kernel(mdq_ipcs_desc d, int NIN, int NIR, const int32_t* n_ref,
-                                                               const double* inlet_y, int32_t* n_inlet, int32_t* inlet_dofs,
-                                                               int32_t* n_rows, int32_t* rows, int32_t* map_status) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  __shared__ unsigned s_in[MAP_WORDS], s_row[MAP_WORDS];
-  __shared__ int s_pre[MAP_WORDS + 1];
-  __shared__ double s_y[MAP_NIN];
-  __shared__ int s_dof[MAP_NIN], s_sorted[MAP_NIN];
-  __shared__ double s_lo[MWG / 64], s_hi[MWG / 64];
-  __shared__ int s_bad_y, s_bad_out;
-  const int nv = min(max(d.nv[b], 0), d.NV), nt = min(max(d.nt[b], 0), d.NT), ne = min(max(d.ne[b], 0), d.NE);
-  const int n2 = min(nv + ne, MAP_BITS);
-  const int64_t B = b;
-  const double* coords = d.coords + B * d.NV * 2;
-  const int32_t* cd = d.cell_dofs + B * 6 * d.NT;
-  const int8_t* cof = d.cell_outflow + B * d.NT;
-  const uint8_t* fl = d.bcu_flag + B * d.N2;
-  const double* gx = d.bcu_gx + B * d.N2;
-  for (int w = tid; w < MAP_WORDS; w += MWG) s_in[w] = s_row[w] = 0u;
-  for (int k = tid; k < MAP_NIN; k += MWG) {
-    s_y[k] = 0.0;
-    s_dof[k] = s_sorted[k] = -1;
-  }
-  if (tid == 0) s_bad_y = s_bad_out = 0;
-  // extent of the mesh in y (fixed tree: lanes by shuffle, waves through LDS)
-  double lo = INFINITY, hi = -INFINITY;
-  for (int i = tid; i < nv; i += MWG) {
-    const double y = coords[2 * i + 1];
-    lo = fmin(lo, y);
-    hi = fmax(hi, y);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fmin(lo, __shfl_xor(lo, o));
-    hi = fmax(hi, __shfl_xor(hi, o));
-  }
-  if ((tid & 63) == 0) {
-    s_lo[tid >> 6] = lo;
-    s_hi[tid >> 6] = hi;
-  }
-  __syncthreads();
-  // inlet set
-  for (int i = tid; i < n2; i += MWG)
-    if (fl[i] != 0 && gx[i] != 0.0) atomicOr(&s_in[i >> 5], 1u << (i & 31));
-  __syncthreads();
-  auto word_prefix = [&](const unsigned* bits) {   // s_pre[w] = set bits in the words below w; s_pre[MAP_WORDS] = all
-    for (int w = tid; w <= MAP_WORDS; w += MWG) {
-      int s = 0;
-      for (int q = 0; q < w; ++q) s += __popc(bits[q]);
-      s_pre[w] = s;
-    }
-  };
-  auto slot_of = [&](const unsigned* bits, int i) { return s_pre[i >> 5] + __popc(bits[i >> 5] & ((1u << (i & 31)) - 1u)); };
-  auto has = [&](const unsigned* bits, int i) { return (bits[i >> 5] >> (i & 31)) & 1u; };
-  word_prefix(s_in);
-  __syncthreads();
-  double H = 0.0;
-  {
-    double l = s_lo[0], h = s_hi[0];
-#pragma unroll
-    for (int q = 1; q < MWG / 64; ++q) {
-      l = fmin(l, s_lo[q]);
-      h = fmax(h, s_hi[q]);
-    }
-    H = h - l;
-  }
-  const int nin = s_pre[MAP_WORDS], want = n_ref[b];
-  int fail = (nin != want || nin > NIN || nin > MAP_NIN) ? 1 : 0;   // (workgroup-uniform from here on)
-  if (!fail) {
-    // cells: y of the inlet dofs, the rows around them
-    for (int e = tid; e < nt; e += MWG) {
-      int c[6];
-      bool in_range = true;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        c[j] = cd[j * d.NT + e];
-        in_range = in_range && c[j] >= 0 && c[j] < n2 && (j >= 3 || c[j] < nv);
-      }
-      if (!in_range) continue;
-      unsigned m = 0;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) m |= has(s_in, c[j]) << j;
-      if (!m) continue;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        if (fl[c[j]] == 0) atomicOr(&s_row[c[j] >> 5], 1u << (c[j] & 31));
-        if (!((m >> j) & 1u)) continue;
-        double y;
-        if (j < 3) {
-          y = coords[2 * c[j] + 1];
-        } else {
-          const int k = j - 3, va = c[k == 0 ? 1 : 0], vb = c[k == 2 ? 1 : 2];
-          y = 0.5 * (coords[2 * va + 1] + coords[2 * vb + 1]);
-        }
-        const int slot = slot_of(s_in, c[j]);   // (< nin <= MAP_NIN)
-        s_y[slot] = y;
-        s_dof[slot] = c[j];
-      }
-    }
-    __syncthreads();
-    // canonical order
-    const double tol = 1e-12 * H;
-    for (int t = tid; t < nin; t += MWG) {
-      const double y = s_y[t];
-      int r = 0;
-      for (int k = 0; k < nin; ++k) r += (s_y[k] < y || (s_y[k] == y && k < t)) ? 1 : 0;
-      s_sorted[r] = s_dof[t];
-      if (s_dof[t] < 0 || !(fabs(y - inlet_y[B * NIN + r]) <= tol)) atomicOr(&s_bad_y, 1);
-    }
-    __syncthreads();
-    word_prefix(s_row);
-    // a row of an outflow facet among them?
-    for (int e = tid; e < nt; e += MWG) {
-      const int k = cof[e];
-      if (k < 0 || k > 2) continue;
-      const int loc[3] = {k == 0 ? 1 : 0, k == 2 ? 1 : 2, 3 + k};
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const int i = cd[loc[q] * d.NT + e];
-        if (i >= 0 && i < n2 && has(s_row, i)) atomicOr(&s_bad_out, 1);
-      }
-    }
-    __syncthreads();
-    fail = s_bad_y ? 2 : (s_pre[MAP_WORDS] > NIR ? 3 : (s_bad_out ? 4 : 0));
-  }
-  const int nr = fail ? 0 : s_pre[MAP_WORDS], nok = fail ? 0 : nin;
-  int32_t* od = inlet_dofs + B * NIN;
-  int32_t* orow = rows + B * NIR;
-  for (int r = tid; r < NIN; r += MWG) od[r] = r < nok ? s_sorted[r] : -1;
-  for (int q = nr + tid; q < NIR; q += MWG) orow[q] = -1;
-  if (!fail)
-    for (int i = tid; i < n2; i += MWG)
-      if (has(s_row, i)) orow[slot_of(s_row, i)] = i;   // (slot < nr <= NIR)
-  if (tid == 0) {
-    n_inlet[b] = nok;
-    n_rows[b] = nr;
-    if (fail && map_status[b] == 0) map_status[b] = fail;
-  }
-}
-#endif  // part 0
-
-#if MDQ_IN_PART(0)
-hipError_t launch_inflow_lift(const mdq_ipcs_desc* d, const mdq_inflow_profile* prof, int nsteps, int step, hipStream_t st) {
-  hipLaunchKernelGGL(inflow_lift_kernel, dim3(d->B), dim3(IWG), 0, st, *d, *prof, nsteps, step);
-  return hipGetLastError();
-}
+}  // namespace mdq
+#include "mdq_ipcs_inflow.hip"
+namespace mdq {
 #endif
 
 // launchers of the operator modes whose kernels live in the other parts of this file (each uploads its own tables)
@@ -5914,26 +5106,28 @@ static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
                             const double* inflow_scale, void* stream, double* kernel_ms, int fresh = 0,
                             const mdq_inflow_profile* prof = nullptr);
 
+// the argument checks of the two inflow-profile entry points (`entry`: the name their messages carry), then the step loop
+static int evolve_profile_checked(const char* entry, int fresh, const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift,
+                                  int32_t* iters, const mdq_inflow_profile* prof, void* stream) {
+  if (prof) {
+    const auto bad = [entry](const char* what) { return fail_msg(std::string(entry) + what); };
+    if (prof->NIN <= 0 || prof->NIR <= 0) return bad(": NIN and NIR must be positive");
+    if (!prof->n_inlet || !prof->inlet_dofs || !prof->n_rows || !prof->rows || !prof->values)
+      return bad(": incomplete inflow profile (n_inlet, inlet_dofs, n_rows, rows, values)");
+    if (d && (!d->cell_dofs || !d->g2_ptr || !d->g2_src || !d->bcu_flag || !d->bcu_gx || !d->geom || !d->lift1 || !d->lift3))
+      return bad(": incomplete descriptor (cell_dofs, g2_ptr, g2_src, bcu_flag, bcu_gx, geom, lift1, lift3)");
+  }
+  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, nullptr, fresh, prof);
+}
+
 int mdq_ipcs_evolve_profile(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
                             const mdq_inflow_profile* prof, void* stream) {
-  if (!prof) return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, nullptr);
-  if (prof->NIN <= 0 || prof->NIR <= 0) return fail_msg("mdq_ipcs_evolve_profile: NIN and NIR must be positive");
-  if (!prof->n_inlet || !prof->inlet_dofs || !prof->n_rows || !prof->rows || !prof->values)
-    return fail_msg("mdq_ipcs_evolve_profile: incomplete inflow profile (n_inlet, inlet_dofs, n_rows, rows, values)");
-  if (d && (!d->cell_dofs || !d->g2_ptr || !d->g2_src || !d->bcu_flag || !d->bcu_gx || !d->geom || !d->lift1 || !d->lift3))
-    return fail_msg("mdq_ipcs_evolve_profile: incomplete descriptor (cell_dofs, g2_ptr, g2_src, bcu_flag, bcu_gx, geom, lift1, lift3)");
-  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, nullptr, 0, prof);
+  return evolve_profile_checked("mdq_ipcs_evolve_profile", 0, d, nsteps, drag, lift, iters, prof, stream);
 }
 
 int mdq_ipcs_evolve_fresh_profile(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
                                   const mdq_inflow_profile* prof, void* stream) {
-  if (!prof) return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, nullptr, 1);
-  if (prof->NIN <= 0 || prof->NIR <= 0) return fail_msg("mdq_ipcs_evolve_fresh_profile: NIN and NIR must be positive");
-  if (!prof->n_inlet || !prof->inlet_dofs || !prof->n_rows || !prof->rows || !prof->values)
-    return fail_msg("mdq_ipcs_evolve_fresh_profile: incomplete inflow profile (n_inlet, inlet_dofs, n_rows, rows, values)");
-  if (d && (!d->cell_dofs || !d->g2_ptr || !d->g2_src || !d->bcu_flag || !d->bcu_gx || !d->geom || !d->lift1 || !d->lift3))
-    return fail_msg("mdq_ipcs_evolve_fresh_profile: incomplete descriptor (cell_dofs, g2_ptr, g2_src, bcu_flag, bcu_gx, geom, lift1, lift3)");
-  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, nullptr, 1, prof);
+  return evolve_profile_checked("mdq_ipcs_evolve_fresh_profile", 1, d, nsteps, drag, lift, iters, prof, stream);
 }
 
 int mdq_ipcs_build_inlet_map(const mdq_ipcs_desc* d, int32_t NIN, int32_t NIR, const int32_t* n_ref, const double* inlet_y,
@@ -6140,50 +5334,6 @@ int mdq_probe_forces(const mdq_ipcs_desc* d, int32_t nfields, const double* u, c
   hipLaunchKernelGGL(probe_kernel, dim3(d->B), dim3(WG), 0, (hipStream_t)stream, *d, nfields, u, p, drag, lift);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail("probe_kernel launch", e);
-  return 0;
-}
-
-// DOLFIN MeshSmoothing::smooth restated for the host (flow_solver.py:65-67, 236-237).
-int mdq_smooth_host(double* x, int32_t nv, const int32_t* cells, int32_t nt, const int64_t* nbr_ptr,
-                    const int64_t* nbr, const int64_t* vc_ptr, const int64_t* vc, const uint8_t* on_boundary,
-                    int32_t iterations) {
-  if (!x || !cells || !nbr_ptr || !nbr || !vc_ptr || !vc || !on_boundary) return fail_msg("null argument");
-  (void)nt;
-  const double DOLFIN_EPS = 3.0e-16;
-  for (int it = 0; it < iterations; ++it) {
-    for (int v = 0; v < nv; ++v) {
-      if (on_boundary[v]) continue;
-      const double px = x[2 * v], py = x[2 * v + 1];
-      double cx = 0.0, cy = 0.0;
-      const int64_t n0 = nbr_ptr[v], n1 = nbr_ptr[v + 1];
-      for (int64_t k = n0; k < n1; ++k) {
-        cx += x[2 * nbr[k]];
-        cy += x[2 * nbr[k] + 1];
-      }
-      const double cnt = (double)(n1 - n0);
-      cx /= cnt;
-      cy /= cnt;
-      double rmin = 0.0;
-      for (int64_t k = vc_ptr[v]; k < vc_ptr[v + 1]; ++k) {
-        const int64_t c = vc[k] / 3, loc = vc[k] % 3;
-        const int32_t o0 = cells[3 * c + (loc == 0 ? 1 : 0)], o1 = cells[3 * c + (loc == 2 ? 1 : 2)];
-        const double ax = x[2 * o0], ay = x[2 * o0 + 1];
-        const double tx = x[2 * o1] - ax, ty = x[2 * o1 + 1] - ay;
-        double nx = ty, ny = -tx;
-        const double nn = std::sqrt(nx * nx + ny * ny);
-        nx /= nn;
-        ny /= nn;
-        const double r = std::fabs(nx * (px - ax) + ny * (py - ay));
-        rmin = (rmin == 0.0) ? r : (r < rmin ? r : rmin);
-      }
-      const double dx = cx - px, dy = cy - py;
-      const double r = std::sqrt(dx * dx + dy * dy);
-      if (r < DOLFIN_EPS) continue;
-      const double step = (0.5 * rmin < r) ? 0.5 * rmin : r;
-      x[2 * v] = px + step * dx / r;
-      x[2 * v + 1] = py + step * dy / r;
-    }
-  }
   return 0;
 }
 
