@@ -81,7 +81,7 @@ constexpr int OFF_M01 = OFF_PART + LWG * 4;                  // the inverses of 
 constexpr int LDS_BYTES = OFF_M01 + 2 * MBLK * 8;
 // setup scratch inside the position buffers (the positions are loaded last): per-vertex neighbour lists, then the rows of
 // the block inverses under construction
-constexpr int OFF_NB = OFF_CUR;                              // [LNV][MAXNB] u16: id | count << 10
+constexpr int OFF_NB = OFF_CUR;                              // [LNV][MAXNB] u16: id | count << 10 (the count: look-up loop only)
 constexpr int OFF_TRI = OFF_CUR;                             // 8 waves x 528 doubles (packed lower triangles)
 constexpr int OFF_TMP = OFF_SROW;                            // cell lists in arrival order (before the rows are built)
 static_assert(LNV * MAXNB * 2 <= 3 * PBUF && TRW * 528 * 8 <= 3 * PBUF && 3 * LNT * 4 <= LNV * SROW, "setup scratch");
@@ -458,9 +458,12 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
                                                             const int32_t* nv_, const int32_t* nt_, const int32_t* iters_,
                                                             const int32_t* rem, const int32_t* rstat, int iters_env,
                                                             double* mws, int64_t mstride, int32_t* redo, int32_t* stats,
-                                                            int gather_all) {
+                                                            int flags) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the A / B switches of the launch (smooth_fast_impl): bit 0 every block at full gather width, bit 1 the per-vertex
+  // neighbour lists by the look-up loop, bit 2 every row of a block inverse through the serial row loop
+  const bool gather_all = flags & 1, nb_loop = flags & 2, inv_all = flags & 4;
   // sweeps: given per environment, or - inside an env step - `iters_env` where a vertex was removed successfully
   // (Env2DAirfoil._check_mesh -> flow_solver.remesh -> smooth(50), flow_solver.py:236-237; nothing otherwise)
   const int S = iters_ ? iters_[b] : ((rem[b] >= 0 && rstat[b] == 0) ? iters_env : 0);
@@ -519,6 +522,7 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
     if (v < nv && k > MAXNB) misc[2] = 0;                    // (a vertex of more than 16 cells: careful walk)
     int nn = 0;
     if (interior) {
+      bool listed = false;
       if (k <= 8) {
         // rank sort by cell id with the entries in registers: one batch of reads instead of k (k + 1) dependent ones.
         // (The cell id is the top field and distinct per entry, so whole words compare as cell ids; the padding is larger.)
@@ -532,6 +536,36 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
           for (int j = 0; j < 8; ++j) rank += ent[j] < ent[e];
           if (e < k) inc[q0 + rank] = ent[e];
         }
+        if (!nb_loop) {
+          // the neighbour list in registers too.  The sorted cells come back in one batch of reads (the words behind the
+          // k-th are whatever follows in LDS - still inside it - and are replaced by padding ids no vertex has, all
+          // distinct), which gives the 2 k ids in the order of the loop below: cell order, a before c.  An id is listed
+          // where it appears first: 120 compares and one store per list entry instead of up to 2 k x nn dependent reads.
+          // (The earlier equals are counted in a register: as lane masks the 120 results stay live and spill.)  2 k <=
+          // MAXNB, so the list cannot overflow.  The interior test needs no counts per neighbour: nn == k firsts among
+          // 2 k ids leave k repeats, so "every id is seen exactly twice" is "no id is seen a third time" - no id has two
+          // earlier equals.  (The count field of nbl[] is the look-up loop's own: 0 here.)
+          static_assert(OFF_INC + (3 * LNT + 8) * 4 <= LDS_BYTES, "batched read of the sorted cells");
+          asm volatile("" ::: "memory");
+          uint32_t ids[16];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const uint32_t w = inc[q0 + e];
+            ids[2 * e] = e < k ? w & 0x3FF : 0x400u + 2 * e;
+            ids[2 * e + 1] = e < k ? (w >> 10) & 0x3FF : 0x401u + 2 * e;
+          }
+          bool third = false;
+#pragma unroll
+          for (int p = 0; p < 16; ++p) {
+            int seen = 0;                                       // earlier equal ids
+#pragma unroll
+            for (int q = 0; q < p; ++q) seen += ids[q] == ids[p];
+            third = third | (seen > 1);
+            if (p < 2 * k && seen == 0) nbl[v * MAXNB + nn++] = (uint16_t)ids[p];
+          }
+          interior = !third && nn == k;
+          listed = true;
+        }
       } else {
         for (int e = 0; e < k; ++e) {                        // rank sort by cell id
           const uint32_t my = tmp[q0 + e];
@@ -540,24 +574,26 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
           inc[q0 + rank] = my;
         }
       }
-      for (int e = 0; e < k; ++e) {
-        const uint32_t w = inc[q0 + e];
-        for (int s = 0; s < 2; ++s) {
-          const uint32_t id = s ? (w >> 10) & 0x3FF : w & 0x3FF;
-          int f = -1;
-          for (int j = 0; j < nn; ++j)
-            if ((nbl[v * MAXNB + j] & 0x3FF) == id) f = j;
-          if (f >= 0) {
-            nbl[v * MAXNB + f] += 1 << 10;
-          } else if (nn < MAXNB) {
-            nbl[v * MAXNB + nn++] = (uint16_t)(id | (1 << 10));
-          } else {
-            interior = false;                                // more than 16 distinct neighbours: a boundary fan
+      if (!listed) {
+        for (int e = 0; e < k; ++e) {
+          const uint32_t w = inc[q0 + e];
+          for (int s = 0; s < 2; ++s) {
+            const uint32_t id = s ? (w >> 10) & 0x3FF : w & 0x3FF;
+            int f = -1;
+            for (int j = 0; j < nn; ++j)
+              if ((nbl[v * MAXNB + j] & 0x3FF) == id) f = j;
+            if (f >= 0) {
+              nbl[v * MAXNB + f] += 1 << 10;
+            } else if (nn < MAXNB) {
+              nbl[v * MAXNB + nn++] = (uint16_t)(id | (1 << 10));
+            } else {
+              interior = false;                              // more than 16 distinct neighbours: a boundary fan
+            }
           }
         }
+        for (int j = 0; j < nn; ++j) interior = interior && (nbl[v * MAXNB + j] >> 10) == 2;
+        interior = interior && nn == k;
       }
-      for (int j = 0; j < nn; ++j) interior = interior && (nbl[v * MAXNB + j] >> 10) == 2;
-      interior = interior && nn == k;
     }
     cnt[v] = interior ? 1 : 0;
   }
@@ -653,36 +689,91 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
       // trips in front of the reads of T: 64 k of the set-up's 140 k cycles went into this phase)
       const uint32_t kdv = kdeg[r0 + j];
       const uint2 lmv = *reinterpret_cast<const uint2*>(lmeta + (r0 + j) * MAXLOW);
-      if (lane < 32) {
-        for (int i = 0; i < BS; ++i) {
-          const uint32_t kd = (uint32_t)__builtin_amdgcn_readlane((int)kdv, i);
-          const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)lmv.x, i), hi = (uint32_t)__builtin_amdgcn_readlane((int)lmv.y, i);
-          const int nl = kd >> 8;
-          // (the reads of T stay in a loop of nl steps: fully unrolled to 8 unconditional reads the step was 2.5x slower -
-          // a lone wave issues ~170 instructions per row then, and issue, not the LDS round trips, bounds the chain)
-          double val = 0.0;
-          for (int t = 0; t < nl; ++t) {
-            const int w = (int)(((t < 4 ? lo : hi) >> (8 * (t & 3))) & 0xFFu);
-            if (j <= w) val += T[w * (w + 1) / 2 + j];
+      if (inv_all) {
+        if (lane < 32) {
+          for (int i = 0; i < BS; ++i) {
+            const uint32_t kd = (uint32_t)__builtin_amdgcn_readlane((int)kdv, i);
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)lmv.x, i), hi = (uint32_t)__builtin_amdgcn_readlane((int)lmv.y, i);
+            const int nl = kd >> 8;
+            // (the reads of T stay in a loop of nl steps: fully unrolled to 8 unconditional reads the step was 2.5x slower -
+            // a lone wave issues ~170 instructions per row then, and issue, not the LDS round trips, bounds the chain)
+            double val = 0.0;
+            for (int t = 0; t < nl; ++t) {
+              const int w = (int)(((t < 4 ? lo : hi) >> (8 * (t & 3))) & 0xFFu);
+              if (j <= w) val += T[w * (w + 1) / 2 + j];
+            }
+            val = val * (2.0 * r2ktab[kd & 0xFF]) + (i == j ? 1.0 : 0.0);
+            if (j <= i) T[i * (i + 1) / 2 + j] = val;
+            asm volatile("" ::: "memory");
           }
-          val = val * (2.0 * r2ktab[kd & 0xFF]) + (i == j ? 1.0 : 0.0);
-          if (j <= i) T[i * (i + 1) / 2 + j] = val;
-          asm volatile("" ::: "memory");
         }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // write-out: lane = row i (both halves of the wave: columns 0..15 / 16..31), 16 bytes per store
+        const int i = lane & 31, h = lane >> 5;
+        d2* out = reinterpret_cast<d2*>(mg) + ((size_t)(blk * 2 + h) * 8) * 32 + i;
+        d2* out01 = reinterpret_cast<d2*>(lds + OFF_M01) + ((blk * 2 + h) * 8) * 32 + i;   // (blocks 0 and 1: the copy in LDS too)
+        for (int t = 0; t < 8; ++t) {
+          const int j0 = 16 * h + 2 * t;
+          const double m0 = j0 <= i ? T[i * (i + 1) / 2 + j0] * (2.0 * r2ktab[kdeg[r0 + j0] & 0xFF]) : 0.0;
+          const double m1 = j0 + 1 <= i ? T[i * (i + 1) / 2 + j0 + 1] * (2.0 * r2ktab[kdeg[r0 + j0 + 1] & 0xFF]) : 0.0;
+          out[t * 32] = d2{m0, m1};
+          if (blk < 2) out01[t * 32] = d2{m0, m1};
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      } else {
+        // A row without in-block lower neighbours is e_i whatever else the block holds (0.0 x 1 / k + delta_ij), and on the lab
+        // meshes that is three rows of five.  So the wave first writes the whole packed triangle as the identity - stores only,
+        // no waits - and then walks, in ascending order, only the rows that have lower neighbours: the same arithmetic in the
+        // same order of adds, and the lower neighbours of a row are final when it is reached exactly as in the full loop.
+        // 1 / k_i is formed once per lane in front of the loop and broadcast like the rest of the row's metadata; the
+        // write-out takes its column factors from a per-wave copy in LDS (the scans' scratch, dead since the interior ranks) in
+        // one batch next to the rows of T, not through kdeg -> r2ktab chains.
+        static_assert(TRW * BS * 8 <= LWG * 4, "column factors in the scan scratch");
+        double* ck = reinterpret_cast<double*>(lds + OFF_PART) + wave * BS;
+        const double rkv = 2.0 * r2ktab[kdv & 0xFF];
+        for (int q = lane; q < 528; q += 64) T[q] = 0.0;
+        if (lane < 32) {
+          T[j * (j + 3) / 2] = 1.0;
+          ck[j] = rkv;
+        }
+        uint32_t todo = (uint32_t)__builtin_amdgcn_ballot_w64(lane < 32 && (kdv >> 8) != 0);
+        const int rklo = __double2loint(rkv), rkhi = __double2hiint(rkv);
+        asm volatile("" ::: "memory");
+        if (lane < 32) {
+          while (todo) {
+            const int i = __builtin_ctz(todo);
+            todo &= todo - 1;
+            const uint32_t kd = (uint32_t)__builtin_amdgcn_readlane((int)kdv, i);
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)lmv.x, i), hi = (uint32_t)__builtin_amdgcn_readlane((int)lmv.y, i);
+            const double rk = __hiloint2double(__builtin_amdgcn_readlane(rkhi, i), __builtin_amdgcn_readlane(rklo, i));
+            const int nl = kd >> 8;
+            double val = 0.0;
+            for (int t = 0; t < nl; ++t) {
+              const int w = (int)(((t < 4 ? lo : hi) >> (8 * (t & 3))) & 0xFFu);
+              if (j <= w) val += T[w * (w + 1) / 2 + j];
+            }
+            val = val * rk + (i == j ? 1.0 : 0.0);
+            if (j <= i) T[i * (i + 1) / 2 + j] = val;
+            asm volatile("" ::: "memory");
+          }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const int i = lane & 31, h = lane >> 5;
+        d2* out = reinterpret_cast<d2*>(mg) + ((size_t)(blk * 2 + h) * 8) * 32 + i;
+        d2* out01 = reinterpret_cast<d2*>(lds + OFF_M01) + ((blk * 2 + h) * 8) * 32 + i;
+        const double* row = T + i * (i + 1) / 2 + 16 * h;        // (entries behind the diagonal: still inside this wave's T)
+        const d2* cf = reinterpret_cast<const d2*>(ck + 16 * h);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          const int j0 = 16 * h + 2 * t;
+          const double a0 = row[2 * t], a1 = row[2 * t + 1];
+          const d2 c = cf[t];
+          const double m0 = j0 <= i ? a0 * c.x : 0.0, m1 = j0 + 1 <= i ? a1 * c.y : 0.0;
+          out[t * 32] = d2{m0, m1};
+          if (blk < 2) out01[t * 32] = d2{m0, m1};
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      // write-out: lane = row i (both halves of the wave: columns 0..15 / 16..31), 16 bytes per store
-      const int i = lane & 31, h = lane >> 5;
-      d2* out = reinterpret_cast<d2*>(mg) + ((size_t)(blk * 2 + h) * 8) * 32 + i;
-      d2* out01 = reinterpret_cast<d2*>(lds + OFF_M01) + ((blk * 2 + h) * 8) * 32 + i;   // (blocks 0 and 1: the copy in LDS too)
-      for (int t = 0; t < 8; ++t) {
-        const int j0 = 16 * h + 2 * t;
-        const double m0 = j0 <= i ? T[i * (i + 1) / 2 + j0] * (2.0 * r2ktab[kdeg[r0 + j0] & 0xFF]) : 0.0;
-        const double m1 = j0 + 1 <= i ? T[i * (i + 1) / 2 + j0 + 1] * (2.0 * r2ktab[kdeg[r0 + j0 + 1] & 0xFF]) : 0.0;
-        out[t * 32] = d2{m0, m1};
-        if (blk < 2) out01[t * 32] = d2{m0, m1};
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
   }
   __threadfence_block();
@@ -856,11 +947,18 @@ static int smooth_fast_impl(const char* who, int32_t B, int32_t NV, int32_t NT, 
     const char* e = std::getenv("MDQ_SMOOTH_GATHER");
     return e && std::atoi(e) == 7 ? 1 : 0;
   }();
+  // (MDQ_SMOOTH_SETUP_PARENT, a bit mask read once per process: 1 - the per-vertex neighbour lists by the look-up loop in
+  //  LDS, 2 - every row of a block inverse through the serial row loop; the A / B switches of the two set-up sections and
+  //  the references of their tests.  Every output is bitwise the same either way.)
+  static const int setup_parent = [] {
+    const char* e = std::getenv("MDQ_SMOOTH_SETUP_PARENT");
+    return e ? std::atoi(e) & 3 : 0;
+  }();
   // every sweep as a blocked triangular solve: checked + repaired while limited steps occur, then validated in parallel.
   // Environments beyond the kernel's limits (more than 16 cells at a vertex, 14 gather slots per row, 8 lower neighbours
   // inside a block) are walked vertex by vertex by their own workgroup inside the same launch (redo[b] = their sweeps)
   hipLaunchKernelGGL(mdq_smooth_lin::smooth_linear_kernel, dim3(B), dim3(mdq_smooth_lin::LWG), 0, st, NV, NT, coords, cells, nv,
-                     nt, iterations, rem, rstat, iters_env, mws, mstride, redo, redo + B, gather_all);
+                     nt, iterations, rem, rstat, iters_env, mws, mstride, redo, redo + B, gather_all | (setup_parent << 1));
   if (hipGetLastError() != hipSuccess) return mdq_set_error("mdq_smooth_fast: launch failed");
   return 0;
 }

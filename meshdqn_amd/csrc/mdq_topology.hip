@@ -10,6 +10,7 @@
 // sqrt / division), so every output array is bit-identical to mdq_env_topology_host's.
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <type_traits>
 
 #include "../../include/meshdqn_hip.h"
@@ -130,7 +131,8 @@ extern "C" int mdq_topo_trace_host(long long* out, int reset) {
 
 template <int K>
 __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_ipcs_topo_out O, int has_ipcs,
-                                                      int32_t* status, unsigned char* slab, mdq_topo_handover HO) {
+                                                      int32_t* status, unsigned char* slab, mdq_topo_handover HO,
+                                                      int idx_parent) {
 #pragma clang fp contract(off)
 #ifdef MDQ_TOPO_TRACE
   long long tq_ = __builtin_amdgcn_s_memtime();
@@ -1210,11 +1212,23 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
   using stage_t = typename CP::stage_t;
   stage_t* stage = K > 4 ? reinterpret_cast<stage_t*>(smem + CP::BASE) : reinterpret_cast<stage_t*>(R);   // [nl * nt] <= 6 TNT entries = 24 KB (blist .. cntd are dead)
   static_assert(K > 4 || 6 * TNT * 2 <= RSEG + (TNP + 8) * 4, "gather staging fits in front of `fill`");
+  // The rows of the EDGE dofs (half of the 6 nt entries) need none of this: an edge's list is its owner slot and, unless
+  // it lies on the boundary, the slot of its second cell - known from eid_slot / eown / eflag since the edge phase.  Their
+  // counts are 2 - boundary, one pass over the slots puts 6 t + 3 + k in front if the slot is the owner (the lowest slot of
+  // the edge) and behind it otherwise, and only the vertex dofs go through count, fill and sort: three passes of atomics
+  // each instead of six, nv lists instead of n2, and a list of at most 8 entries is ranked in registers (one batch of
+  // reads; the insertion sort is a chain of dependent LDS round trips).  The instance with every table in LDS only - the
+  // one the env step's flow stream runs; idx_parent & 1 (MDQ_TOPO_INDEX_PARENT) selects the general path there as well.
+  // (An edge in three cells - no triangulation - would lose its third slot here; nothing is written out of bounds.)
   auto gather = [&](int nl, int ndof, int32_t* gptr, int32_t* gsrc) {
+    const bool direct = K == 1 && nl == 6 && !(idx_parent & 1);
+    const int nlv = direct ? 3 : nl;                          // local dofs that are counted and filled by atomics
     for (int i = tid; i < TNS; i += TW) scanb[i] = 0;
     __syncthreads();
-    for (int i = 0; i < nl; ++i)
+    for (int i = 0; i < nlv; ++i)
       for (int t = tid; t < nt; t += TW) atomicAdd(&scanb[cd[i * D.NT + t]], 1);
+    if (direct)
+      for (int e = tid; e < ne; e += TW) scanb[nv + e] = 2 - (eflag[e] & 1);
     __syncthreads();
     const int tot = scan_excl(scanb, TNS, part);
     (void)tot;
@@ -1223,14 +1237,33 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
       if (i < ndof) fill[i] = 0;
     }
     __syncthreads();
-    for (int i = 0; i < nl; ++i)
+    for (int i = 0; i < nlv; ++i)
       for (int t = tid; t < nt; t += TW) {
         const int dof = cd[i * D.NT + t];
         stage[scanb[dof] + atomicAdd(&fill[dof], 1)] = (stage_t)(t * nl + i);   // slot = t * nl + i
       }
+    if (direct)
+      for (int s = tid; s < 3 * nt; s += TW) {
+        const int e = eid_slot[s], t = s / 3;
+        stage[scanb[nv + e] + (s != (int)eown[e] ? 1 : 0)] = (stage_t)(t * 6 + 3 + (s - 3 * t));
+      }
     __syncthreads();
-    for (int i = tid; i < ndof; i += TW) {
+    for (int i = tid; i < (direct ? nv : ndof); i += TW) {
       const int q0 = scanb[i], q1 = q0 + fill[i];
+      if (direct && q1 - q0 <= 8) {
+        // (slots are distinct: the rank of an entry is the number of smaller ones; the padding is larger than any slot)
+        uint32_t ent[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ent[j] = q0 + j < q1 ? (uint32_t)stage[q0 + j] : 0xFFFFFFFFu;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          int rank = 0;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) rank += ent[j] < ent[e];
+          if (q0 + e < q1) stage[q0 + rank] = (stage_t)ent[e];
+        }
+        continue;
+      }
       for (int a_ = q0 + 1; a_ < q1; ++a_) {
         const stage_t w = stage[a_];
         int j = a_ - 1;
@@ -1322,6 +1355,21 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
         const int q0 = rptr[r], q1 = rptr[r + 1];
         len = q1 - q0 + 1;
         int below = 0;                                       // neighbours below the diagonal
+        if (K == 1 && !(idx_parent & 2) && q1 - q0 <= 8) {
+          // the row's (distinct) neighbours in registers, read once: ranks by 64 compares there, not by a nested loop of
+          // LDS reads per entry (idx_parent & 2: that loop for every row)
+          uint32_t a[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) a[j] = q0 + j < q1 ? (uint32_t)adjl[q0 + j] : 0xFFFFFFFFu;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            int rank = a[e] > (uint32_t)r ? 1 : 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) rank += a[j] < a[e];
+            below += a[e] < (uint32_t)r ? 1 : 0;
+            if (q0 + e < q1) sc[base + 64 * rank + l] = (int)a[e];
+          }
+        } else
         for (int q = q0; q < q1; ++q) {
           const int v = adjl[q];
           int rank = v > r ? 1 : 0;                          // (the diagonal entry)
@@ -1359,6 +1407,13 @@ extern "C" int mdq_env_topology(const mdq_env_topo_desc* d, void* stream, int32_
     if (d->npoly > (huge_ ? 2 : 1) * mdq_topo::TNPOLY)
       return mdq_set_error("mdq_env_topology: more than 256 polygon points (512 for the 16384-vertex instance)");
   }
+  // (MDQ_TOPO_INDEX_PARENT, a bit mask read once per process: 1 - the dof <- slot gather lists of the IPCS index section all
+  //  through count / fill / sort, 2 - the SELL rows of the P1 Laplacian ranked by loops of LDS reads; the A / B switches of
+  //  the two sections and the references of their test.  Every table is the same either way.)
+  static const int idx_parent = [] {
+    const char* e = std::getenv("MDQ_TOPO_INDEX_PARENT");
+    return e ? std::atoi(e) & 3 : 0;
+  }();
   mdq_ipcs_topo_out o = {};
   if (d->ipcs) o = *d->ipcs;
   mdq_topo_handover h = {};
@@ -1369,7 +1424,7 @@ extern "C" int mdq_env_topology(const mdq_env_topo_desc* d, void* stream, int32_
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (attr != hipSuccess) return mdq_set_error("hipFuncSetAttribute(topology_kernel) failed");
     hipLaunchKernelGGL(mdq_topo::topology_kernel<1>, dim3(d->B), dim3(mdq_topo::TW), lds, (hipStream_t)stream, *d, o,
-                       d->ipcs ? 1 : 0, status, nullptr, h);
+                       d->ipcs ? 1 : 0, status, nullptr, h, idx_parent);
   } else {
     using C4 = mdq_topo::TCap<4>;
     using C16 = mdq_topo::TCap<16>;
@@ -1391,10 +1446,10 @@ extern "C" int mdq_env_topology(const mdq_env_topo_desc* d, void* stream, int32_
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
       if (attr16 != hipSuccess) return mdq_set_error("hipFuncSetAttribute(topology_kernel<16>) failed");
       hipLaunchKernelGGL(mdq_topo::topology_kernel<16>, dim3(d->B), dim3(mdq_topo::TW), lds4, (hipStream_t)stream, *d, o,
-                         d->ipcs ? 1 : 0, status, slab, h);
+                         d->ipcs ? 1 : 0, status, slab, h, idx_parent);
     } else
     hipLaunchKernelGGL(mdq_topo::topology_kernel<4>, dim3(d->B), dim3(mdq_topo::TW), lds4, (hipStream_t)stream, *d, o,
-                       d->ipcs ? 1 : 0, status, slab, h);
+                       d->ipcs ? 1 : 0, status, slab, h, idx_parent);
   }
   if (hipGetLastError() != hipSuccess) return mdq_set_error("topology_kernel launch failed");
   return 0;
