@@ -27,10 +27,12 @@ ARCH = "gfx950"
 
 # translation unit -> (source, extra flags, the .hip files it includes besides itself, transitively: they are part of the
 # object cache's key - tests/test_build_units_cpu.py holds the lists to the #include lines).  mdq_ipcs.hip is compiled in
-# parts (-DMDQ_IPCS_PART=k: each part instantiates the kernels of some operator modes and their launchers; part 0 also
-# holds the entry points) because it alone took a minute as one unit.  Its fragments are compiled by part 0 only, but
-# every part's source names them, so every part lists them.
-IPCS_FRAGMENTS = ["mdq_ipcs_setup.hip", "mdq_ipcs_inflow.hip"]
+# parts (-DMDQ_IPCS_PART=k: each part instantiates the kernels of some operator modes and their launchers; part 0 is the
+# set-up, mode 3 and the entry points) because it alone took a minute as one unit.  Its fragments hold what part 0 alone
+# compiles - the file itself keeps what the parts share and the kernels of parts 1-3 - but every part's source names
+# them, so every part lists them.
+IPCS_FRAGMENTS = ["mdq_ipcs_setup.hip", "mdq_ipcs_pcg_reg.hip", "mdq_ipcs_mode3.hip", "mdq_ipcs_inflow.hip",
+                  "mdq_ipcs_entry.hip"]
 UNITS = {
     "ipcs0": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=0"], IPCS_FRAGMENTS),
     "ipcs1": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=1"], IPCS_FRAGMENTS),

@@ -3,5 +3,5 @@
 // -fvisibility=hidden: only the MDQ_API entry points of include/meshdqn_hip.h are exported.
 #pragma once
 
-// records the text mdq_last_error() returns (thread-local, mdq_ipcs.hip) and returns -2
+// records the text mdq_last_error() returns (thread-local, mdq_ipcs_entry.hip) and returns -2
 int mdq_set_error(const char* msg);

@@ -26,8 +26,10 @@
 
 // This file is compiled as several translation units (meshdqn_amd/build.py: -DMDQ_IPCS_PART=k), each instantiating the
 // kernels of some operator modes together with their launchers - as ONE unit it took a minute of every rebuild:
-//   part 0  entry points, probes, the three kernels of mode 3; assembly and the matrix-free set-up (mdq_ipcs_setup.hip), the
-//           inflow profile and the inlet map (mdq_ipcs_inflow.hip) - fragments that only this part includes
+//   part 0  the probe kernel here, everything else in fragments that only this part includes: assembly and the matrix-free
+//           set-up (mdq_ipcs_setup.hip), the register-resident pressure solvers of mode 3 (mdq_ipcs_pcg_reg.hip), the three
+//           kernels of mode 3 (mdq_ipcs_mode3.hip), the inflow profile and the inlet map (mdq_ipcs_inflow.hip), the error
+//           state and the entry points with the launch sequence of mode 3 (mdq_ipcs_entry.hip)
 //   part 1  evolve_kernel<0 / 1> (assembled SELL operators)
 //   part 2  evolve_kernel<5> (element tiles, global vectors), evolve_team_kernel (mode 4)
 //   part 3  the kernels of mode 2 (element tiles, LDS / register vectors: the reproducible mode of the long runs)
@@ -38,12 +40,6 @@
 #endif
 #define MDQ_IN_PART(k) (MDQ_IPCS_PART == (k) || MDQ_IPCS_PART == -1)
 
-#ifndef MDQ_CORR_MX0_INTERLEAVE
-#define MDQ_CORR_MX0_INTERLEAVE false
-#endif
-#ifndef MDQ_PCG_REGM
-#define MDQ_PCG_REGM 1
-#endif
 #ifndef MDQ_SETUP_WG
 #define MDQ_SETUP_WG 768
 #endif
@@ -1071,625 +1067,13 @@ __device__ inline int cg_pressure(int n, const int32_t* sl_off, const int32_t* s
   return it;
 }
 
-// Jacobi-scaled CG on the SELL-64 P1 Laplacian for the three-kernel mode 3: every thread keeps x, r, q of its own
-// two rows (slice = wave, wave + NTH/64; lane = row in the slice: the rows its SpMV produces) in registers, only the
-// search direction lives in LDS for the gather; one-barrier reductions.  3 barriers per iteration instead of 6.
-// Needs n <= 2 * NTH (the caller falls back to cg_pressure otherwise).  x, r, p: LDS vectors as in cg_pressure.
-template <int NTH>
-__device__ inline int cg_pressure_reg(int n, const int32_t* sl_off, const int32_t* sl_col, const double* A, double rtol,
-                                      int maxit, double* x, double* r, double* p, double* red, int& rsel) {
-  constexpr int NW = NTH / 64;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nsl = (n + 63) >> 6;
-  int base[2], wid[2], row[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int s_ = wave + NW * k;
-    row[k] = (s_ << 6) + lane;
-    base[k] = s_ < nsl ? sl_off[s_] : 0;
-    wid[k] = s_ < nsl ? (sl_off[s_ + 1] - base[k]) >> 6 : 0;
-  }
-  auto spmv = [&](const double* vec, double(&y)[2]) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const double* a = A + base[k] + lane;
-      const int32_t* c = sl_col + base[k] + lane;
-      double y0 = 0.0;
-#pragma unroll 4
-      for (int j = 0; j < wid[k]; ++j) y0 += a[j * 64] * vec[c[j * 64]];
-      y[k] = y0;
-    }
-  };
-  __syncthreads();
-  double y[2], xv[2], rv[2], pv[2];
-  spmv(x, y);
-  double acc[2] = {0.0, 0.0};
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    xv[k] = rv[k] = pv[k] = 0.0;
-    if (row[k] < n) {
-      const double b = r[row[k]];
-      xv[k] = x[row[k]];
-      rv[k] = pv[k] = b - y[k];
-      p[row[k]] = pv[k];
-      acc[0] += b * b;
-      acc[1] += rv[k] * rv[k];
-    }
-  }
-  block_sum<2, NW>(acc, red);
-  const double bb = acc[0], tol2 = rtol * rtol * bb;
-  double rr = acc[1];
-  int it = 0;
-  if (rr > tol2 && bb != 0.0) {
-    while (it < maxit) {
-      ++it;
-      double q[2];
-      spmv(p, q);
-      double a1[1] = {pv[0] * q[0] + pv[1] * q[1]};
-      block_sum1<1, NW>(a1, red, rsel);
-      if (!(a1[0] > 0.0)) break;
-      const double alpha = rr / a1[0];
-      double a2[1] = {0.0};
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        xv[k] += alpha * pv[k];
-        rv[k] -= alpha * q[k];
-        a2[0] += rv[k] * rv[k];
-      }
-      block_sum1<1, NW>(a2, red, rsel);
-      const double rr_new = a2[0];
-      if (!(rr_new > tol2)) break;
-      const double beta = rr_new / rr;
-      rr = rr_new;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        pv[k] = rv[k] + beta * pv[k];
-        if (row[k] < n) p[row[k]] = pv[k];
-      }
-      __syncthreads();
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    if (row[k] < n) x[row[k]] = xv[k];
-  __syncthreads();
-  return it;
-}
-
-// cg_pressure_reg with the matrix rows of a thread in REGISTERS and a BRANCH-FREE operator application.  Counters of the
-// LDS-resident version (profiles/r03_sq_summary.json): LDS utilisation 20 %, bank conflicts 0.3 %, VALU busy 18 % - the
-// iteration is a chain of LDS LATENCIES, not bandwidth: per row three batches of (index, value) reads followed by the
-// dependent gathers, two rows one after the other, ~2 100 of the iteration's ~3 400 cycles.  Here a thread loads the
-// up to RW entries of its two rows once (slots past a slice's width: value 0, column = own row, like the SELL padding),
-// and an application issues all 2 x RW gathers back to back - no branch, so nothing waits between them - and then runs
-// the two fma chains in the same column order as before (adding 0 * p[row] for the padded slots).  (The Chebyshev
-// variant below keeps its rows in registers too but guards every gather with a branch on the slice width, which
-// serialises the round trips: that is why it never beat the LDS version.)  Needs n <= 2 * NTH and slices of at most RW
-// entries per row.
-//
-// RW is the number of register slots per row.  The solve is instantiated at 10, 12 and 16 and the caller
-// (cg_pressure_regm below) takes the smallest that holds the environment's widest slice: the P1 Laplacian of the lab
-// meshes has rows of at most 9 entries (SELL-64 slice widths 6-9), so at RW = 16 twelve to fourteen of the 32 gathers of an
-// application read the thread's own row and multiply it by zero.  The dropped slots have value 0 and sit behind every real
-// entry of the row: the fma chain ends with acc + 0 * p[row] = acc there, so every iterate, every reduction and the
-// iteration count are those of RW = 16, bit for bit.  The caller guarantees that every slice is at most RW wide.
-template <int NTH, int RW>
-__device__ inline int cg_pressure_regm_w(int n, const int32_t* sl_off, const int32_t* sl_col, const double* A, double rtol,
-                                         int maxit, double* x, double* r, double* p, double* red, int& rsel) {
-  constexpr int NW = NTH / 64;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nsl = (n + 63) >> 6;
-  int row[2];
-  double av[2][RW];
-  int co[2][RW];                      // byte offsets into the gathered vector
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int s_ = wave + NW * k;
-    row[k] = (s_ << 6) + lane;
-    const int base = s_ < nsl ? sl_off[s_] : 0;
-    const int wid = s_ < nsl ? (sl_off[s_ + 1] - base) >> 6 : 0;
-    const int self = min(row[k], n - 1);
-#pragma unroll
-    for (int j = 0; j < RW; ++j) {
-      const bool in = j < wid;
-      av[k][j] = in ? A[base + lane + j * 64] : 0.0;
-      co[k][j] = 8 * (in ? sl_col[base + lane + j * 64] : self);
-    }
-  }
-  auto spmv = [&](const double* vec, double(&y)[2]) {
-    const char* vb = reinterpret_cast<const char*>(vec);
-    double g[2][RW];
-#pragma unroll
-    for (int j = 0; j < RW; ++j) {
-      g[0][j] = *reinterpret_cast<const double*>(vb + co[0][j]);
-      g[1][j] = *reinterpret_cast<const double*>(vb + co[1][j]);
-    }
-    double y0 = 0.0, y1 = 0.0;
-#pragma unroll
-    for (int j = 0; j < RW; ++j) {
-      y0 += av[0][j] * g[0][j];
-      y1 += av[1][j] * g[1][j];
-    }
-    y[0] = y0;
-    y[1] = y1;
-  };
-  __syncthreads();
-  double y[2], xv[2], rv[2], pv[2];
-  spmv(x, y);
-  double acc[2] = {0.0, 0.0};
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    xv[k] = rv[k] = pv[k] = 0.0;
-    if (row[k] < n) {
-      const double b = r[row[k]];
-      xv[k] = x[row[k]];
-      rv[k] = pv[k] = b - y[k];
-      p[row[k]] = pv[k];
-      acc[0] += b * b;
-      acc[1] += rv[k] * rv[k];
-    }
-  }
-  block_sum<2, NW>(acc, red);
-  const double bb = acc[0], tol2 = rtol * rtol * bb;
-  double rr = acc[1];
-  int it = 0;
-  if (rr > tol2 && bb != 0.0) {
-    while (it < maxit) {
-      ++it;
-      double q[2];
-      spmv(p, q);
-      double a1[1] = {pv[0] * q[0] + pv[1] * q[1]};
-      block_sum1<1, NW>(a1, red, rsel);
-      if (!(a1[0] > 0.0)) break;
-      const double alpha = rr / a1[0];
-      double a2[1] = {0.0};
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        xv[k] += alpha * pv[k];
-        rv[k] -= alpha * q[k];
-        a2[0] += rv[k] * rv[k];
-      }
-      block_sum1<1, NW>(a2, red, rsel);
-      const double rr_new = a2[0];
-      if (!(rr_new > tol2)) break;
-      const double beta = rr_new / rr;
-      rr = rr_new;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        pv[k] = rv[k] + beta * pv[k];
-        if (row[k] < n) p[row[k]] = pv[k];
-      }
-      __syncthreads();
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    if (row[k] < n) x[row[k]] = xv[k];
-  __syncthreads();
-  return it;
-}
-
-// cg_pressure_regm_w at the environment's width.  Every thread reads ALL slice offsets (at most 2 * NTH / 64 + 1 words,
-// the same addresses in every lane), so the widest slice - and with it the variant - is the same value in every thread of
-// the workgroup without a reduction: the barriers inside the variants are reached by all waves or by none.
-template <int NTH>
-__device__ inline int cg_pressure_regm(int n, const int32_t* sl_off, const int32_t* sl_col, const double* A, double rtol,
-                                       int maxit, double* x, double* r, double* p, double* red, int& rsel) {
-  const int nsl = (n + 63) >> 6;
-  int wmax = 0, o0 = sl_off[0];
-  for (int s_ = 0; s_ < nsl; ++s_) {
-    const int o1 = sl_off[s_ + 1];
-    wmax = max(wmax, (o1 - o0) >> 6);
-    o0 = o1;
-  }
-  wmax = __builtin_amdgcn_readfirstlane(wmax);
-  if (wmax <= 10) return cg_pressure_regm_w<NTH, 10>(n, sl_off, sl_col, A, rtol, maxit, x, r, p, red, rsel);
-  if (wmax <= 12) return cg_pressure_regm_w<NTH, 12>(n, sl_off, sl_col, A, rtol, maxit, x, r, p, red, rsel);
-  if (wmax <= 16) return cg_pressure_regm_w<NTH, 16>(n, sl_off, sl_col, A, rtol, maxit, x, r, p, red, rsel);
-  return -1;
-}
-
-// The same CG with the matrix rows of a thread in REGISTERS (values + column offsets of its two rows: they do not change
-// over the iterations, and the LDS-resident version paid two dependent LDS round trips per entry - column, then vector
-// element) and, for degree > 1, a CHEBYSHEV polynomial preconditioner on top of the Jacobi scaling: z = p_m(A) r with
-// p_m the degree-(m - 1) Chebyshev approximation of 1 / lambda on [lmax / CHEB_RATIO, lmax] (lmax: Gershgorin bound of the
-// scaled matrix, computed here).  p_m(A) is symmetric positive definite for any spectrum inside (0, lmax], so this is a
-// plain preconditioned CG; it trades reductions (two workgroup barriers each) for operator applications (one barrier):
-// m - 1 extra applications per iteration, roughly m times fewer iterations.  Needs n <= 2 * NTH and SELL slices of at
-// most PCG_W entries per row (else: returns -1 and the caller takes cg_pressure_reg).
-constexpr int PCG_W = 12;
-constexpr double CHEB_RATIO = 30.0;
-template <int NTH>
-__device__ inline int cg_pressure_cheb(int n, const int32_t* sl_off, const int32_t* sl_col, const double* A, double rtol,
-                                       int maxit, int degree, double* x, double* r, double* p, double* red, int& rsel) {
-  constexpr int NW = NTH / 64;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nsl = (n + 63) >> 6;
-  int row[2], wid[2];
-  double av[2][PCG_W];
-  int cv[2][PCG_W];
-  bool fits = true;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int s_ = wave + NW * k;
-    row[k] = (s_ << 6) + lane;
-    const int base = s_ < nsl ? sl_off[s_] : 0;
-    wid[k] = s_ < nsl ? (sl_off[s_ + 1] - base) >> 6 : 0;
-    fits = fits && wid[k] <= PCG_W;
-#pragma unroll
-    for (int j = 0; j < PCG_W; ++j) {
-      const bool in = j < wid[k];
-      av[k][j] = in ? A[base + lane + j * 64] : 0.0;
-      cv[k][j] = in ? sl_col[base + lane + j * 64] : 0;
-    }
-  }
-  // workgroup-wide OR of `!fits` through the (still unused) search-direction vector: __syncthreads_or would add a static
-  // LDS word to kernels that already ask for the whole 160 KB dynamically
-  if (threadIdx.x == 0) p[NW] = 0.0;
-  __syncthreads();
-  if (!fits) p[NW] = 1.0;
-  __syncthreads();
-  const bool toowide = p[NW] != 0.0;
-  __syncthreads();
-  if (toowide) return -1;
-  auto spmv = [&](const double* vec, double(&y)[2]) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      double y0 = 0.0, y1 = 0.0;
-#pragma unroll
-      for (int j = 0; j < PCG_W; j += 2) {
-        if (j < wid[k]) y0 += av[k][j] * vec[cv[k][j]];            // (wid is uniform over the wave: scalar branches)
-        if (j + 1 < wid[k]) y1 += av[k][j + 1] * vec[cv[k][j + 1]];
-      }
-      y[k] = y0 + y1;
-    }
-  };
-  // Gershgorin bound of the largest eigenvalue (the scaled matrix has a unit diagonal; rows of constrained vertices are
-  // identity rows)
-  double lmax = 0.0;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    double s_ = 0.0;
-#pragma unroll
-    for (int j = 0; j < PCG_W; ++j) s_ += fabs(av[k][j]);
-    lmax = fmax(lmax, row[k] < n ? s_ : 0.0);
-  }
-  for (int off = 32; off > 0; off >>= 1) lmax = fmax(lmax, __shfl_xor(lmax, off));
-  {
-    double* buf = p;                          // (the search direction is not in use yet)
-    if (lane == 0) buf[wave] = lmax;
-    __syncthreads();
-    double m_ = 0.0;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) m_ = fmax(m_, buf[i]);
-    lmax = m_;
-    __syncthreads();
-  }
-  const int M = degree < 1 ? 1 : degree;
-  const double lmin = lmax / CHEB_RATIO, theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma = theta / delta;
-  double y[2], xv[2], rv[2], pv[2], zv[2];
-  spmv(x, y);
-  double acc[2] = {0.0, 0.0};
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    xv[k] = rv[k] = pv[k] = zv[k] = 0.0;
-    if (row[k] < n) {
-      const double b = r[row[k]];
-      xv[k] = x[row[k]];
-      rv[k] = b - y[k];
-      acc[0] += b * b;
-      acc[1] += rv[k] * rv[k];
-    }
-  }
-  block_sum<2, NW>(acc, red);
-  const double bb = acc[0], tol2 = rtol * rtol * bb;
-  double rr = acc[1];
-  int it = 0;
-  if (rr > tol2 && bb != 0.0) {
-    double rz_old = 1.0;
-    // `r` (LDS) is free from here on: the polynomial's iterates are staged there for the gathers
-    double* zs = r;
-    while (it < maxit) {
-      // z = p_M(A) r  (Chebyshev iteration for A z = r from z = 0, M - 1 further applications)
-      double dv[2];
-      double rho = 1.0 / sigma;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        dv[k] = rv[k] / theta;
-        zv[k] = dv[k];
-      }
-      for (int m_ = 1; m_ < M; ++m_) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-          if (row[k] < n) zs[row[k]] = zv[k];
-        __syncthreads();
-        double az[2];
-        spmv(zs, az);
-        const double rho_n = 1.0 / (2.0 * sigma - rho);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          dv[k] = rho_n * rho * dv[k] + (2.0 * rho_n / delta) * (rv[k] - az[k]);
-          zv[k] += dv[k];
-        }
-        rho = rho_n;
-        __syncthreads();                         // (everybody has gathered from zs before the next round rewrites it)
-      }
-      double a0[1] = {rv[0] * zv[0] + rv[1] * zv[1]};
-      block_sum1<1, NW>(a0, red, rsel);
-      const double rz = a0[0];
-      const double beta = it == 0 ? 0.0 : rz / rz_old;
-      rz_old = rz;
-      ++it;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        pv[k] = zv[k] + beta * pv[k];
-        if (row[k] < n) p[row[k]] = pv[k];
-      }
-      __syncthreads();
-      double q[2];
-      spmv(p, q);
-      double a1[1] = {pv[0] * q[0] + pv[1] * q[1]};
-      block_sum1<1, NW>(a1, red, rsel);
-      if (!(a1[0] > 0.0)) break;
-      const double alpha = rz / a1[0];
-      double a2[1] = {0.0};
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        xv[k] += alpha * pv[k];
-        rv[k] -= alpha * q[k];
-        a2[0] += rv[k] * rv[k];
-      }
-      block_sum1<1, NW>(a2, red, rsel);
-      rr = a2[0];
-      if (!(rr > tol2)) break;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    if (row[k] < n) x[row[k]] = xv[k];
-  __syncthreads();
-  return it;
-}
-
-// The register-resident CG (cg_pressure_reg) with a TWO-LEVEL additive preconditioner on top of the Jacobi scaling:
-//      z = r + P A_c^-1 P^T r,     A_c = P^T A P,
-// P = piecewise constants over NAGX x NAGY geometric aggregates: vertices ranked by x into NAGX strips of equal
-// population, every strip ranked by y into NAGY cells (compact patches of ~16 vertices; aggregates of consecutive INDICES
-// do nothing for this matrix: tools + HISTORY 8.1).  A_c (56 x 56) is accumulated with LDS atomics, inverted in LDS by
-// Gauss-Jordan (SPD: no pivoting) once per solve and kept in fp32 (a preconditioner may be approximate; it is stored
-// exactly symmetric).  Per iteration: per-wave partial restrictions by LDS atomics (rows of one aggregate are scattered
-// over the waves), one 56^2 product spread over 448 threads, prolongation by one LDS read per row: two extra barriers.
-// Iterations on ys930 (developed flow): 154 -> 86, same answers.  MEASURED (tools/time_pcg.py): 465 us per solve against 247 us of
-// the plain Jacobi-CG - the O(n^2) rank counts of the aggregation and the 56-step inversion cost ~0.1 ms per solve, and
-// every iteration pays two more barriers, the atomics and a 63-read coarse product per thread.  An O(n) aggregation
-// (histograms) and one shared restriction vector would bring it to ~200 us (-18 %): kept as an OPTION (pcg_degree < 0), the
-// default stays the Jacobi-CG.  LDS: the four pressure vectors' space (x, r, p, q = 4 NVp doubles, NVp >= 1024):
-// x and r live in registers during the iterations.  Needs n <= 2 NTH, n <= 1024 and at least NAG vertices; else -1.
+// aggregates of the two-level preconditioners (cg_pressure_2l in mdq_ipcs_pcg_reg.hip; tl_build and its users below)
 constexpr int NAGX = 8, NAGY = 7, NAG = NAGX * NAGY;
-template <int NTH>
-__device__ inline int cg_pressure_2l(int n, const int32_t* sl_off, const int32_t* sl_col, const double* A, const double* coords,
-                                     double rtol, int maxit, double* x, double* r, double* p, int NVp, double* red, int& rsel) {
-  constexpr int NW = NTH / 64;
-  if (n > 2 * NTH || n > 1024 || n < 4 * NAG || NVp < 1024) return -1;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nsl = (n + 63) >> 6;
-  int base[2], wid[2], row[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int s_ = wave + NW * k;
-    row[k] = (s_ << 6) + lane;
-    base[k] = s_ < nsl ? sl_off[s_] : 0;
-    wid[k] = s_ < nsl ? (sl_off[s_ + 1] - base[k]) >> 6 : 0;
-  }
-  auto spmv = [&](const double* vec, double(&y)[2]) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const double* a = A + base[k] + lane;
-      const int32_t* c = sl_col + base[k] + lane;
-      double y0 = 0.0;
-#pragma unroll 4
-      for (int j = 0; j < wid[k]; ++j) y0 += a[j * 64] * vec[c[j * 64]];
-      y[k] = y0;
-    }
-  };
-  // LDS carve-up of the 4 NVp doubles behind x (x | r | p | q are contiguous in every caller)
-  double* W = x;
-  double* AC = W;                                            // [NAG][NAG] fp64 while it is built and inverted
-  float* AI = reinterpret_cast<float*>(W);                   // ... then fp32 in its first half
-  double* YV = W + NAG * NAG / 2 + 8;                        // [NAG] coarse result       (behind the fp32 inverse)
-  double* PG = W + 2 * NVp;                                  // the gather copy of the search direction (= p)
-  double* WP = W + 3 * NVp;                                  // [NW][NAG] per-wave partial restrictions
-  unsigned char* AG = reinterpret_cast<unsigned char*>(W + 3 * NVp + NW * NAG);   // [n] aggregate of a vertex
-  static_assert(NAG * NAG <= 3 * 1024 + 64 && 16 * NAG + 128 <= 1024, "two-level scratch");
-  __syncthreads();
-  double y[2], xv[2], rv[2], pv[2], zv[2];
-  spmv(x, y);
-  double acc[2] = {0.0, 0.0};
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    xv[k] = rv[k] = pv[k] = zv[k] = 0.0;
-    if (row[k] < n) {
-      const double b = r[row[k]];
-      xv[k] = x[row[k]];
-      rv[k] = b - y[k];
-      acc[0] += b * b;
-      acc[1] += rv[k] * rv[k];
-    }
-  }
-  block_sum<2, NW>(acc, red);                                // (its barriers: x and r are in registers, their LDS space is free)
-  const double bb = acc[0], tol2 = rtol * rtol * bb;
-  double rr = acc[1];
-  int it = 0;
-  if (rr > tol2 && bb != 0.0) {
-    // ---- aggregates: rank by x -> strip, rank by y inside the strip -> cell
-    double* XC = W;                                          // coordinates staged in LDS for the counting loops
-    double* YC = W + 1024;
-    unsigned char* ST = reinterpret_cast<unsigned char*>(W + 2048);
-    for (int i = tid; i < n; i += NTH) {
-      XC[i] = coords[2 * i];
-      YC[i] = coords[2 * i + 1];
-    }
-    __syncthreads();
-    int strip[2] = {0, 0};
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-      if (row[k] < n) {
-        const double xi = XC[row[k]];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {
-          const double xj = XC[j];
-          rank += (xj < xi) | ((xj == xi) & (j < row[k]));
-        }
-        strip[k] = rank * NAGX / n;
-        ST[row[k]] = (unsigned char)strip[k];
-      }
-    __syncthreads();
-    int agg[2] = {0, 0};
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-      if (row[k] < n) {
-        const double yi = YC[row[k]];
-        int rank = 0, cnt = 0;
-        for (int j = 0; j < n; ++j) {
-          const bool same = ST[j] == strip[k];
-          const double yj = YC[j];
-          cnt += same;
-          rank += same & ((yj < yi) | ((yj == yi) & (j < row[k])));
-        }
-        agg[k] = strip[k] * NAGY + rank * NAGY / cnt;
-      }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-      if (row[k] < n) AG[row[k]] = (unsigned char)agg[k];
-    for (int e = tid; e < NAG * NAG; e += NTH) AC[e] = 0.0;
-    __syncthreads();
-    // ---- coarse matrix
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-      if (row[k] < n) {
-        const double* a = A + base[k] + lane;
-        const int32_t* c = sl_col + base[k] + lane;
-        for (int j = 0; j < wid[k]; ++j) {
-          const double av = a[j * 64];
-          if (av != 0.0) atomicAdd(&AC[agg[k] * NAG + AG[c[j * 64]]], av);
-        }
-      }
-    __syncthreads();
-    // ---- in-place Gauss-Jordan inverse (every thread owns the elements e = tid + m NTH)
-    constexpr int EPT = (NAG * NAG + NTH - 1) / NTH;
-    int ei_[EPT], ej_[EPT];
-#pragma unroll
-    for (int m = 0; m < EPT; ++m) {
-      const int e = tid + m * NTH;
-      ei_[m] = e / NAG;
-      ej_[m] = e - ei_[m] * NAG;
-    }
-    for (int kk = 0; kk < NAG; ++kk) {
-      const double ip = 1.0 / AC[kk * NAG + kk];
-      double nv_[EPT];
-#pragma unroll
-      for (int m = 0; m < EPT; ++m) {
-        const int e = tid + m * NTH;
-        nv_[m] = 0.0;
-        if (e < NAG * NAG) {
-          const int i = ei_[m], j = ej_[m];
-          const double aij = AC[e], aik = AC[i * NAG + kk], akj = AC[kk * NAG + j];
-          nv_[m] = i == kk ? (j == kk ? ip : akj * ip) : (j == kk ? -aik * ip : aij - aik * akj * ip);
-        }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int m = 0; m < EPT; ++m) {
-        const int e = tid + m * NTH;
-        if (e < NAG * NAG) AC[e] = nv_[m];
-      }
-      __syncthreads();
-    }
-    {  // fp32 copy, exactly symmetric: the entry of the upper triangle for both (i, j) and (j, i)
-      float f_[EPT];
-#pragma unroll
-      for (int m = 0; m < EPT; ++m) {
-        const int e = tid + m * NTH;
-        f_[m] = 0.f;
-        if (e < NAG * NAG) {
-          const int i = e / NAG, j = e - i * NAG;
-          f_[m] = (float)AC[min(i, j) * NAG + max(i, j)];
-        }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int m = 0; m < EPT; ++m) {
-        const int e = tid + m * NTH;
-        if (e < NAG * NAG) AI[e] = f_[m];
-      }
-    }
-    __syncthreads();
-    double rz_old = 1.0;
-    while (it < maxit) {
-      // ---- z = r + P A_c^-1 P^T r
-      if (lane < NAG) WP[wave * NAG + lane] = 0.0;
-#pragma unroll
-      for (int k = 0; k < 2; ++k)
-        if (row[k] < n) atomicAdd(&WP[wave * NAG + agg[k]], rv[k]);
-      __syncthreads();
-      if (tid < NAG * 8) {
-        const int I = tid >> 3, part = tid & 7;
-        double s_ = 0.0;
-        for (int J = part; J < NAG; J += 8) {
-          double w_ = 0.0;
-#pragma unroll
-          for (int q = 0; q < NW; ++q) w_ += WP[q * NAG + J];
-          s_ += (double)AI[I * NAG + J] * w_;
-        }
-        s_ += dpp_get<0xB1, 0xF>(s_);      // quad_perm [1,0,3,2]
-        s_ += dpp_get<0x4E, 0xF>(s_);      // quad_perm [2,3,0,1]
-        s_ += dpp_get<0x141, 0xF>(s_);     // row_half_mirror: the other quad of the group of 8
-        if (part == 0) YV[I] = s_;
-      }
-      __syncthreads();
-      double a0[1] = {0.0};
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        zv[k] = row[k] < n ? rv[k] + YV[agg[k]] : 0.0;
-        a0[0] += rv[k] * zv[k];
-      }
-      block_sum1<1, NW>(a0, red, rsel);
-      const double rz = a0[0];
-      const double beta = it == 0 ? 0.0 : rz / rz_old;
-      rz_old = rz;
-      ++it;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        pv[k] = zv[k] + beta * pv[k];
-        if (row[k] < n) PG[row[k]] = pv[k];
-      }
-      __syncthreads();
-      double q[2];
-      spmv(PG, q);
-      double a1[1] = {pv[0] * q[0] + pv[1] * q[1]};
-      block_sum1<1, NW>(a1, red, rsel);
-      if (!(a1[0] > 0.0)) break;
-      const double alpha = rz / a1[0];
-      double a2[1] = {0.0};
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        xv[k] += alpha * pv[k];
-        rv[k] -= alpha * q[k];
-        a2[0] += rv[k] * rv[k];
-      }
-      block_sum1<1, NW>(a2, red, rsel);
-      rr = a2[0];
-      if (!(rr > tol2)) break;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    if (row[k] < n) x[row[k]] = xv[k];
-  __syncthreads();
-  return it;
-}
+#if MDQ_IN_PART(0)
+}  // namespace mdq
+#include "mdq_ipcs_pcg_reg.hip"
+namespace mdq {
+#endif
 
 // The two-level preconditioner for the meshes BEYOND the register-resident solvers (cg_pressure: four LDS vectors, 512
 // threads, any n up to the LDS): where Jacobi-CG needs hundreds of iterations (refined ys930, 3 322 vertices: 320-343).
@@ -2196,31 +1580,10 @@ __device__ inline int pressure_krylov_lds(const mdq_ipcs_desc& d, bool k1_lds, i
 // debug build only: s_memtime deltas of thread 0 of environment 0 at the phase boundaries of at_velocity_kernel
 static __device__ long long mdq_at_trace_buf[16];
 #define AT_STAMP(k) { const long long tn_ = __builtin_amdgcn_s_memtime(); if (tid == 0 && b == 0) mdq_at_trace_buf[k] += tn_ - tq_; tq_ = tn_; }
-#if MDQ_IN_PART(0)
-extern "C" MDQ_API int mdq_at_trace_host(long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mdq_at_trace_buf), sizeof(long long) * 16) != hipSuccess) return -1;
-  if (reset) { long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(mdq_at_trace_buf), z, sizeof z) != hipSuccess) return -1; }
-  return 0;
-}
-#endif
 static __device__ long long mdq_pt_trace_buf[16];
 #define PT_STAMP(k) { const long long tn_ = __builtin_amdgcn_s_memtime(); if (threadIdx.x == 0 && blockIdx.x == 0) mdq_pt_trace_buf[k] += tn_ - tqp_; tqp_ = tn_; }
-#if MDQ_IN_PART(0)
-extern "C" MDQ_API int mdq_pt_trace_host(long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mdq_pt_trace_buf), sizeof(long long) * 16) != hipSuccess) return -1;
-  if (reset) { long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(mdq_pt_trace_buf), z, sizeof z) != hipSuccess) return -1; }
-  return 0;
-}
-#endif
 static __device__ long long mdq_ct_trace_buf[16];
 #define CT_STAMP(k) { const long long tn_ = __builtin_amdgcn_s_memtime(); if (tid == 0 && b == 0) mdq_ct_trace_buf[k] += tn_ - tq_; tq_ = tn_; }
-#if MDQ_IN_PART(0)
-extern "C" MDQ_API int mdq_ct_trace_host(long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mdq_ct_trace_buf), sizeof(long long) * 16) != hipSuccess) return -1;
-  if (reset) { long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(mdq_ct_trace_buf), z, sizeof z) != hipSuccess) return -1; }
-  return 0;
-}
-#endif
 #else
 #define AT_STAMP(k)
 #define CT_STAMP(k)
@@ -3429,14 +2792,6 @@ static hipError_t launch_evolve_team_tiles(const mdq_ipcs_desc* d, size_t lds, i
 // touched only for the element metadata (dofs, tile maps, geometry) and once per time step for
 // the state vectors.
 
-// float kept in a register -> double at the point of use: the asm stops the compiler from hoisting the conversion
-// out of the Krylov loop, which turns 4-byte loop invariants into 8-byte ones (measured: they were then spilled to
-// scratch and re-read one by one in every vector phase of every iteration)
-__device__ __forceinline__ double f2d(float f) {
-  asm volatile("" : "+v"(f));
-  return (double)f;
-}
-
 // a lane index the compiler cannot see through: the per-row addresses (7 rows x 6 slab vectors x 64 bits) are then
 // computed where they are used - hoisted out of the Krylov loop they were what the register allocator spilled
 __device__ __forceinline__ int opaque_lane(int x) {
@@ -3949,943 +3304,10 @@ static hipError_t launch_evolve_mf(const mdq_ipcs_desc* d, size_t lds, int nstep
   return hipGetLastError();
 }
 
-// ================================================================== matrix-free kernel, LDS-atomic accumulation (mode 3)
-//
-// Same element operators as mode 2, but the element results are accumulated straight into an LDS
-// result vector with hardware LDS fp64 atomics (ds_add_f64) instead of going through a tile and an
-// ordered row gather.  That frees the 96 KB tile: the search direction p, the residual r (= s) AND
-// the result vector all live in LDS, only v stays in registers, so the element phase can interleave
-// several triangles per thread (FP64 ILP) without register spills, with two barriers per operator
-// application.  Price: the summation order of the <= 8 contributions per row depends on timing, so
-// results are reproducible to round-off only (modes 0-2 are bitwise reproducible).
-
-constexpr int AT_PAIR = 2;  // triangles interleaved per thread per round
-
-template <int TPAIR = AT_PAIR>
-struct AtMetaT {
-  int w[TPAIR][6];
-  Geo g[TPAIR];
-};
-using AtMeta = AtMetaT<AT_PAIR>;
-
-template <int TW = WG, int TPAIR = AT_PAIR>
-__device__ __forceinline__ void at_prefetch(const EnvView& v, AtMetaT<TPAIR>& m, int round) {
-#pragma unroll
-  for (int j = 0; j < TPAIR; ++j) {
-    const int e = threadIdx.x + (round * TPAIR + j) * TW;
-    if (e < v.nt) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) m.w[j][i] = v.mf_scat[i * v.NT + e];
-      m.g[j] = load_geo(v, e);
-    }
-  }
-}
-
-// Y[dof] += element results for every triangle (Y zeroed and published by the caller).
-// op(e, geo, dofs, outflow_edge, ye).  On entry m holds round 0; on exit again (rolling prefetch).
-// INTERLEAVE = true computes the AT_PAIR triangles of a round side by side (FP64 ILP for the hot
-// operator applications); false runs them one after the other (register-hungry right-hand sides).
-template <bool INTERLEAVE, int TW = WG, int TPAIR = AT_PAIR, class ElemOp>
-__device__ __forceinline__ void atomic_accumulate(const EnvView& v, double* Yd, AtMetaT<TPAIR>& m, ElemOp op) {
-  const int nrounds = (v.nt + TPAIR * TW - 1) / (TPAIR * TW);
-  // (delaying the odd waves by 256-1536 cycles to de-phase LDS and FP64 phases only added the delay: measured)
-  for (int round = 0; round < nrounds; ++round) {
-    if (INTERLEAVE) {
-      double2 ye[TPAIR][6];
-      int dof[TPAIR][6];
-#pragma unroll
-      for (int j = 0; j < TPAIR; ++j) {
-        const int e = threadIdx.x + (round * TPAIR + j) * TW;
-        if (e < v.nt) {
-          ElemIdx E;
-#pragma unroll
-          for (int i = 0; i < 6; ++i) E.dof[i] = dof[j][i] = m.w[j][i] & 0xFFF;
-          op(e, m.g[j], E, ((m.w[j][0] >> 28) & 3) - 1, ye[j]);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < TPAIR; ++j) {
-        const int e = threadIdx.x + (round * TPAIR + j) * TW;
-        if (e < v.nt) {
-#pragma unroll
-          for (int i = 0; i < 6; ++i) {
-            unsafeAtomicAdd(Yd + 2 * dof[j][i], ye[j][i].x);
-            unsafeAtomicAdd(Yd + 2 * dof[j][i] + 1, ye[j][i].y);
-          }
-        }
-      }
-    } else {
-#pragma unroll 1
-      for (int j = 0; j < TPAIR; ++j) {
-        const int e = threadIdx.x + (round * TPAIR + j) * TW;
-        if (e < v.nt) {
-          ElemIdx E;
-          double2 ye[6];
-          // (explicit selects: a runtime index into the register arrays would demote them to scratch)
-          const int* wj = (TPAIR == 1 || j == 0) ? m.w[0] : m.w[TPAIR - 1];
-          const Geo gj = (TPAIR == 1 || j == 0) ? m.g[0] : m.g[TPAIR - 1];
-#pragma unroll
-          for (int i = 0; i < 6; ++i) E.dof[i] = wj[i] & 0xFFF;
-          op(e, gj, E, ((wj[0] >> 28) & 3) - 1, ye);
-#pragma unroll
-          for (int i = 0; i < 6; ++i) {
-            unsafeAtomicAdd(Yd + 2 * E.dof[i], ye[i].x);
-            unsafeAtomicAdd(Yd + 2 * E.dof[i] + 1, ye[i].y);
-          }
-        }
-      }
-    }
-    at_prefetch<TW, TPAIR>(v, m, round + 1 < nrounds ? round + 1 : 0);
-  }
-}
-
-// Outflow rows owned by this thread (row % WG == tid): at most BO_OWN of them, found once per launch.
-constexpr int BO_OWN = 2;
-struct BoOwn {
-  int t[BO_OWN];
-};
-template <int TW = WG>
-__device__ __forceinline__ BoOwn outflow_rows_owned(const EnvView& v) {
-  BoOwn o;
-#pragma unroll
-  for (int q = 0; q < BO_OWN; ++q) o.t[q] = -1;
-  for (int t = 0; t < v.nbo; ++t) {
-    if ((v.bo_rows[t] % TW) == (int)threadIdx.x) {
-      if (o.t[0] < 0) o.t[0] = t;
-      else o.t[1] = t;  // (a third owned row cannot occur: outflow rows are < 2*WG apart in practice; checked on the host)
-    }
-  }
-  return o;
-}
-
-// Y[row] += coef * sum_entries B x[col] for the outflow rows owned by this thread.
-// Called between the barrier that completes the atomic accumulation and the owner's read of Y;
-// x must not be modified by other threads before the next barrier.
-__device__ __forceinline__ void outflow_rows_add(const EnvView& v, const BoOwn& own, double coef, const double2* x,
-                                                 double2* Y) {
-#pragma unroll
-  for (int q = 0; q < BO_OWN; ++q) {
-    const int t = own.t[q];
-    if (t >= 0) {
-      const int row = v.bo_rows[t];
-      double sx = 0.0, sy = 0.0;
-      for (int k = v.bo_ptr[t]; k < v.bo_ptr[t + 1]; ++k) {
-        const double4 bv = reinterpret_cast<const double4*>(v.bo_val)[k];
-        const double2 xc = x[v.bo_col[k]];
-        sx += bv.x * xc.x + bv.y * xc.y;
-        sy += bv.z * xc.x + bv.w * xc.y;
-      }
-      const double2 y = Y[row];
-      Y[row] = make_double2(y.x + coef * sx, y.y + coef * sy);
-    }
-  }
-}
-
-
-// The same outflow-facet term, one ENTRY per thread (18 entries per outflow facet, a few hundred per mesh): every
-// thread adds coef * B_entry x[col] to Y[row] with LDS atomics, between the barrier that publishes the zeroed Y
-// and the element loop, so that the term costs one global-load latency of the waves that own entries instead of a
-// serial per-row chain of them between two barriers.  (row, col) of entry `tid` is found once per launch from the
-// element slot list (bo_src = cell * 36 + i * 6 + j) and kept packed in one register; entries beyond the
-// workgroup size (never on the training meshes) are looked up on the fly.
-struct BoEnt {
-  int rc;   // row << 12 | col of entry threadIdx.x, -1 if none
-  int nbe;  // entries of this environment
-};
-__device__ __forceinline__ int outflow_entry_rc(const EnvView& v, int t) {
-  const int slot = v.bo_src[t];
-  const int e = slot / 36, ij = slot - e * 36, i = ij / 6, j = ij - i * 6;
-  return ((v.mf_scat[i * v.NT + e] & 0xFFF) << 12) | (v.mf_scat[j * v.NT + e] & 0xFFF);
-}
-__device__ __forceinline__ BoEnt outflow_entries_owned(const EnvView& v) {
-  BoEnt o;
-  o.nbe = v.nbo > 0 ? v.bo_ptr[v.nbo] : 0;
-  o.rc = (int)threadIdx.x < o.nbe ? outflow_entry_rc(v, threadIdx.x) : -1;
-  return o;
-}
-__device__ __forceinline__ void outflow_entry_apply(const EnvView& v, int t, int rc, double coef, const double2* x,
-                                                    double* Yd) {
-  const double4 bv = reinterpret_cast<const double4*>(v.bo_val)[t];
-  const double2 xc = x[rc & 0xFFF];
-  const int row = rc >> 12;
-  unsafeAtomicAdd(Yd + 2 * row, coef * (bv.x * xc.x + bv.y * xc.y));
-  unsafeAtomicAdd(Yd + 2 * row + 1, coef * (bv.z * xc.x + bv.w * xc.y));
-}
-template <int TW>
-__device__ __forceinline__ void outflow_entries_add(const EnvView& v, const BoEnt& o, double coef, const double2* x,
-                                                    double* Yd) {
-  if (o.rc >= 0) outflow_entry_apply(v, threadIdx.x, o.rc, coef, x, Yd);
-  for (int t = threadIdx.x + TW; t < o.nbe; t += TW) outflow_entry_apply(v, t, outflow_entry_rc(v, t), coef, x, Yd);
-}
-
-
-// ---- mode 3 as three kernels per time step (separate register allocation per phase: the BiCGStab
-// loop then runs without spill reloads; state is handed over through global memory as before) ----
-template <int TW, int TROWS, int TPAIR>
-__global__ __launch_bounds__(TW) void at_velocity_kernel(mdq_ipcs_desc d, int32_t* iters, const double* inflow_scale, int nsteps,
-                                                         int step, int fresh) {
-  extern __shared__ __align__(16) double smem[];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const EnvView v = env_view(d, b);
-  const double ai = inflow_factor(inflow_scale, b, nsteps, step);
-  const int n2 = v.n2, nv = v.nv;
-  const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
-  const double a = uniform_double(v.rho / v.dt), mu = v.mu;
-  (void)a; (void)mu; (void)nv; (void)n2;
-  double* red = smem;  // 64 doubles
-  double* U = smem + 64;
-  double* w = v.work;
-  double2* xs = reinterpret_cast<double2*>(w + 12 * (int64_t)d.NT);  // x of the velocity solve = u*
-  double* pnew = reinterpret_cast<double*>(xs + 6 * (int64_t)d.N2);
-  int rsel = 0;  // parity of the one-barrier reductions
-  (void)rsel; (void)pnew; (void)red;
-  double2* Pl = reinterpret_cast<double2*>(U);  // search direction p / staged operator input
-  double2* Rl = Pl + P.N2p;                      // residual r (= s)
-  double2* Yl = Rl + P.N2p;                      // operator result (atomic accumulation)
-  double* Yd = reinterpret_cast<double*>(Yl);
-  AtMetaT<TPAIR> tm;
-  at_prefetch<TW, TPAIR>(v, tm, 0);
-  const BoEnt bo_ent = outflow_entries_owned(v);
-  int it_u = 0;
-  double2* hist = xs + d.N2;                                          // u* of the step before the last
-  double2* hist2 = xs + 2 * (int64_t)d.N2;                            // and of the one before that
-  double2* hist3 = xs + 4 * (int64_t)d.N2;                            // and one more (slot 3 holds the counter)
-  double2* hist4 = xs + 5 * (int64_t)d.N2;
-  double* histc = reinterpret_cast<double*>(xs + 3 * (int64_t)d.N2);  // [0]: tentative velocities stored so far
-  // `fresh` (all three kernels, step 0 of mdq_ipcs_evolve_fresh): a new mesh - the stored history counts as empty and the
-  // iteration words are assigned, what a reset_history_kernel launch in front of this one would have left
-  const int nhist = (fresh && step == 0) ? 0 : (int)histc[0];
-#ifdef MDQ_AT_TRACE
-  long long tq_ = __builtin_amdgcn_s_memtime();
-#endif
-  __syncthreads();
-  AT_STAMP(0)
-  {
-    // ================= step 1: tentative velocity
-    // Row loops: thread `tid` owns rows tid + k * TW.  All reads use the clamped row (rows past n2 re-read row
-    // n2 - 1, value unused) and come first, so that the TROWS loads of a phase are in flight together instead of
-    // one conditional block (and one LDS / L2 round trip) per row; only the writes are predicated.
-    int rc[TROWS];
-    float2 idg[TROWS];
-    unsigned flm = 0;  // bit k: row k of this thread carries a Dirichlet value
-#pragma unroll
-    for (int k = 0; k < TROWS; ++k) rc[k] = min(tid + k * TW, n2 - 1);
-    {
-      // u_n and p_n staged in LDS (p and r are free until the solve starts): the right-hand-side element loop
-      // gathers 6 + 3 values per triangle from LDS instead of from L2
-      double2 un_[TROWS], dg_[TROWS];
-      unsigned char fl_[TROWS];
-#pragma unroll
-      for (int k = 0; k < TROWS; ++k) {
-        un_[k] = v.u_n[rc[k]];
-        dg_[k] = v.idiag1[rc[k]];
-        fl_[k] = v.bcu_flag[rc[k]];
-      }
-      double* Pn = reinterpret_cast<double*>(Rl);
-      for (int i = tid; i < nv; i += TW) Pn[i] = v.p_n[i];
-#pragma unroll
-      for (int k = 0; k < TROWS; ++k) {
-        const int row = tid + k * TW;
-        idg[k] = (row < n2 && !fl_[k]) ? make_float2((float)dg_[k].x, (float)dg_[k].y) : make_float2(0.f, 0.f);
-        flm |= fl_[k] ? 1u << k : 0u;
-        if (row < n2) {
-          Pl[row] = un_[k];
-          Yl[row] = make_double2(0.0, 0.0);
-        }
-      }
-    }
-    __syncthreads();
-    outflow_entries_add<TW>(v, bo_ent, 0.5 * mu, Pl, Yd);  // + mu/2 <nabla_grad(u_n) n, v> on the outflow rows
-    {
-      const double* Pn = reinterpret_cast<const double*>(Rl);
-      atomic_accumulate<false, TW, TPAIR>(v, Yd, tm, [&](int e, const Geo& g, const ElemIdx& E, int ko, double2(&ye)[6]) {
-        double2 ue[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) ue[i] = Pl[E.dof[i]];
-        double pe[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) pe[i] = Pn[E.dof[i]];
-        elem_rhs1_vol(g, a, mu, v.rho, ue, pe, ye);
-      });
-    }
-    // initial guess: polynomial extrapolation in time of the previous tentative velocities (xs still holds
-    // u*_n, hist.. hist4 the four before it), up to quartic as the history fills; u_n while there is none.
-    // dt is far below the flow's time scales, so every order removes about two digits of initial residual
-    // (11 BiCGStab iterations without, 8 linear, 6 quadratic, 3 cubic, 2.6 quartic; beyond that the 1e-10
-    // solver noise of the history, amplified by the coefficients, is the floor).  Dirichlet values hold.
-    // The history loads are issued here, in front of the barrier that ends the element loop.
-    double2 x0[TROWS];
-    {
-      // binomial coefficients of the order in use: x0 = c1 u*_n + c2 u*_{n-1} + ... (alternating signs)
-      const double c1 = nhist >= 5 ? 5.0 : nhist == 4 ? 4.0 : nhist == 3 ? 3.0 : 2.0;
-      const double c2 = nhist >= 5 ? -10.0 : nhist == 4 ? -6.0 : nhist == 3 ? -3.0 : -1.0;
-      const double c3 = nhist >= 5 ? 10.0 : nhist == 4 ? 4.0 : 1.0;
-      const double c4 = nhist >= 5 ? -5.0 : -1.0;
-      double2 us1[TROWS];
-#pragma unroll
-      for (int k = 0; k < TROWS; ++k) us1[k] = xs[rc[k]];
-      if (nhist >= 2) {
-        double2 h[TROWS];
-#pragma unroll
-        for (int k = 0; k < TROWS; ++k) h[k] = hist[rc[k]];
-#pragma unroll
-        for (int k = 0; k < TROWS; ++k) x0[k] = make_double2(c1 * us1[k].x + c2 * h[k].x, c1 * us1[k].y + c2 * h[k].y);
-        if (nhist >= 3) {
-          double2 h2[TROWS];
-#pragma unroll
-          for (int k = 0; k < TROWS; ++k) h2[k] = hist2[rc[k]];
-#pragma unroll
-          for (int k = 0; k < TROWS; ++k) x0[k] = make_double2(x0[k].x + c3 * h2[k].x, x0[k].y + c3 * h2[k].y);
-          if (nhist >= 4) {
-            double2 h3[TROWS];
-#pragma unroll
-            for (int k = 0; k < TROWS; ++k) h3[k] = hist3[rc[k]];
-#pragma unroll
-            for (int k = 0; k < TROWS; ++k) x0[k] = make_double2(x0[k].x + c4 * h3[k].x, x0[k].y + c4 * h3[k].y);
-            if (nhist >= 5) {
-#pragma unroll
-              for (int k = 0; k < TROWS; ++k) {
-                const double2 h4 = hist4[rc[k]];
-                x0[k] = make_double2(x0[k].x + h4.x, x0[k].y + h4.y);
-              }
-            }
-#pragma unroll
-            for (int k = 0; k < TROWS; ++k)
-              if (tid + k * TW < n2) hist4[tid + k * TW] = h3[k];
-          }
-#pragma unroll
-          for (int k = 0; k < TROWS; ++k)
-            if (tid + k * TW < n2) hist3[tid + k * TW] = h2[k];
-        }
-#pragma unroll
-        for (int k = 0; k < TROWS; ++k)
-          if (tid + k * TW < n2) hist2[tid + k * TW] = h[k];
-      } else {
-#pragma unroll
-        for (int k = 0; k < TROWS; ++k) x0[k] = v.u_n[rc[k]];
-      }
-#pragma unroll
-      for (int k = 0; k < TROWS; ++k)
-        if (tid + k * TW < n2) hist[tid + k * TW] = us1[k];
-    }
-    double2 lf[TROWS];
-    double gx[TROWS];
-#pragma unroll
-    for (int k = 0; k < TROWS; ++k) {
-      lf[k] = scaled2(ai, v.lift1[rc[k]]);
-      gx[k] = ai * v.bcu_gx[rc[k]];
-    }
-    __syncthreads();
-    AT_STAMP(1)
-    double acc[2] = {0.0, 0.0};
-    double2 f[TROWS];
-#pragma unroll
-    for (int k = 0; k < TROWS; ++k) f[k] = Yl[rc[k]];
-#pragma unroll
-    for (int k = 0; k < TROWS; ++k) {
-      const int row = tid + k * TW;
-      const bool fl = (flm >> k) & 1u;
-      const double2 g = make_double2(gx[k], 0.0);
-      if (fl) x0[k] = g;
-      if (row < n2) {
-        Yl[row] = make_double2(0.0, 0.0);
-        xs[row] = x0[k];
-        Pl[row] = x0[k];
-        const double2 bi = fl ? g : make_double2((f[k].x - lf[k].x) * f2d(idg[k].x), (f[k].y - lf[k].y) * f2d(idg[k].y));
-        acc[0] += bi.x * bi.x + bi.y * bi.y;
-      }
-    }
-    __syncthreads();
-    AT_STAMP(2)
-    outflow_entries_add<TW>(v, bo_ent, -0.5 * mu, Pl, Yd);
-    atomic_accumulate<(TPAIR > 1), TW, TPAIR>(v, Yd, tm, [&](int e, const Geo& g, const ElemIdx& E, int ko, double2(&ye)[6]) {
-      double2 xe[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) xe[i] = Pl[E.dof[i]];
-      elem_velocity(g, a, mu, xe, ye);
-    });
-    __syncthreads();
-    AT_STAMP(3)
-    double2 vv[TROWS];
-#pragma unroll
-    for (int k = 0; k < TROWS; ++k) {
-      const int row = tid + k * TW;
-      vv[k] = make_double2(0.0, 0.0);
-      if (row < n2) {
-        const double2 ax = Yl[row];
-        // r0 = D^-1 (f - A_full x0) on free rows, 0 on constrained rows (idg = 0 there)
-        const double2 r0 = make_double2((f[k].x - ax.x) * f2d(idg[k].x), (f[k].y - ax.y) * f2d(idg[k].y));
-        Rl[row] = r0;
-        acc[1] += r0.x * r0.x + r0.y * r0.y;
-      }
-    }
-    block_sum<2, TW / 64>(acc, red);
-    // p = 0 (only now: the outflow rows above still gathered x0 from Pl until the barriers of the reduction)
-#pragma unroll
-    for (int k = 0; k < TROWS; ++k) {
-      const int row = tid + k * TW;
-      if (row < n2) Pl[row] = make_double2(0.0, 0.0);
-    }
-    {
-      const double bb = acc[0], tol2 = uniform_double(d.rtol * d.rtol * bb);
-      double rr = acc[1];
-      if (rr > tol2 && bb != 0.0) {
-        double rho = rr, rho_old = 1.0, alpha = 1.0, omega = 1.0;
-        int it = 0;
-        // shadow residual in registers (own rows).  BiCGStab accepts ANY fixed shadow vector with
-        // (rh, r0) != 0; we take r0 rounded to fp32, which halves its register footprint.
-        float2 rh[TROWS];
-        {
-          double a0[1] = {0.0};
-#pragma unroll
-          for (int k = 0; k < TROWS; ++k) {
-            const int row = tid + k * TW;
-            rh[k] = make_float2(0.f, 0.f);
-            if (row < n2) {
-              const double2 r0 = Rl[row];
-              rh[k] = make_float2((float)r0.x, (float)r0.y);
-              a0[0] += (double)rh[k].x * r0.x + (double)rh[k].y * r0.y;
-            }
-          }
-          block_sum1<1, TW / 64>(a0, red, rsel);
-          rho = a0[0];  // (rh, r0)
-        }
-        AT_STAMP(4)
-        while (it < d.maxit_u) {
-          ++it;
-          const double beta = (rho / rho_old) * (alpha / omega);
-#pragma unroll
-          for (int k = 0; k < TROWS; ++k) {
-            const int row = tid + k * TW;
-            if (row < n2) {
-              const double2 ri = Rl[row], pi = Pl[row];
-              Pl[row] = make_double2(ri.x + beta * (pi.x - omega * vv[k].x), ri.y + beta * (pi.y - omega * vv[k].y));
-              Yl[row] = make_double2(0.0, 0.0);
-            }
-          }
-          __syncthreads();
-          AT_STAMP(5)
-          outflow_entries_add<TW>(v, bo_ent, -0.5 * mu, Pl, Yd);
-          atomic_accumulate<(TPAIR > 1), TW, TPAIR>(v, Yd, tm, [&](int e, const Geo& g, const ElemIdx& E, int ko, double2(&ye)[6]) {
-            double2 xe[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) xe[i] = Pl[E.dof[i]];
-            elem_velocity(g, a, mu, xe, ye);
-          });
-          __syncthreads();
-          AT_STAMP(6)
-          double a1[1] = {0.0};
-#pragma unroll
-          for (int k = 0; k < TROWS; ++k) {
-            const int row = tid + k * TW;
-            if (row < n2) {
-              const double2 yv = Yl[row];
-              vv[k] = make_double2(yv.x * f2d(idg[k].x), yv.y * f2d(idg[k].y));
-              a1[0] += f2d(rh[k].x) * vv[k].x + f2d(rh[k].y) * vv[k].y;
-            }
-          }
-          block_sum1<1, TW / 64>(a1, red, rsel);
-          AT_STAMP(7)
-          if (a1[0] == 0.0) break;
-          alpha = rho / a1[0];
-          // s = r - alpha v ; no early exit on |s| (saves a reduction; the check on |r| follows)
-#pragma unroll
-          for (int k = 0; k < TROWS; ++k) {
-            const int row = tid + k * TW;
-            if (row < n2) {
-              const double2 ri = Rl[row];
-              Rl[row] = make_double2(ri.x - alpha * vv[k].x, ri.y - alpha * vv[k].y);
-              Yl[row] = make_double2(0.0, 0.0);
-            }
-          }
-          __syncthreads();  // publish s and the zeroed result vector
-          AT_STAMP(8)
-          outflow_entries_add<TW>(v, bo_ent, -0.5 * mu, Rl, Yd);
-          atomic_accumulate<(TPAIR > 1), TW, TPAIR>(v, Yd, tm, [&](int e, const Geo& g, const ElemIdx& E, int ko, double2(&ye)[6]) {
-            double2 xe[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) xe[i] = Rl[E.dof[i]];
-            elem_velocity(g, a, mu, xe, ye);
-          });
-          // x of the own rows: issue the global reads now, they are consumed after the reduction
-          double2 xo[TROWS];
-#pragma unroll
-          for (int k = 0; k < TROWS; ++k) {
-            const int row = tid + k * TW;
-            xo[k] = row < n2 ? xs[row] : make_double2(0.0, 0.0);
-          }
-          __syncthreads();
-          AT_STAMP(9)
-          double a3[2] = {0.0, 0.0};
-          double2 t[TROWS];
-#pragma unroll
-          for (int k = 0; k < TROWS; ++k) {
-            const int row = tid + k * TW;
-            t[k] = make_double2(0.0, 0.0);
-            if (row < n2) {
-              const double2 yv = Yl[row], sv = Rl[row];
-              t[k] = make_double2(yv.x * f2d(idg[k].x), yv.y * f2d(idg[k].y));
-              a3[0] += t[k].x * sv.x + t[k].y * sv.y;
-              a3[1] += t[k].x * t[k].x + t[k].y * t[k].y;
-            }
-          }
-          block_sum1<2, TW / 64>(a3, red, rsel);
-          AT_STAMP(10)
-          if (a3[1] == 0.0) break;
-          omega = a3[0] / a3[1];
-          double a4[2] = {0.0, 0.0};
-#pragma unroll
-          for (int k = 0; k < TROWS; ++k) {
-            const int row = tid + k * TW;
-            if (row < n2) {
-              const double2 pi = Pl[row], sv = Rl[row];
-              xs[row] = make_double2(xo[k].x + alpha * pi.x + omega * sv.x, xo[k].y + alpha * pi.y + omega * sv.y);
-              const double2 rn = make_double2(sv.x - omega * t[k].x, sv.y - omega * t[k].y);
-              Rl[row] = rn;
-              a4[0] += rn.x * rn.x + rn.y * rn.y;
-              a4[1] += f2d(rh[k].x) * rn.x + f2d(rh[k].y) * rn.y;
-            }
-          }
-          block_sum1<2, TW / 64>(a4, red, rsel);
-          AT_STAMP(11)
-          rr = a4[0];
-          if (!(rr > tol2)) break;
-          rho_old = rho;
-          rho = a4[1];
-          if (rho == 0.0 || omega == 0.0) break;
-        }
-        it_u += it;
-      }
-    }
-    __syncthreads();  // xs (= u*) complete: the element loops of steps 2 and 3 gather it
-    AT_STAMP(12)
-  }
-  if (tid == 0) {
-    histc[0] = (double)(nhist < 5 ? nhist + 1 : 5);
-    if (iters) iters[3 * b + 0] = ((fresh && step == 0) ? 0 : iters[3 * b + 0]) + it_u;
-  }
-}
-
-// NTH = 1024 for the direct solver (its dense phases are latency-bound streams of 0.8 MB of factors: twice the loads
-// in flight per CU); the CG variant keeps the 512-thread shape its reductions are written for.
-template <bool K1_LDS, int NTH = WG>
-__global__ __launch_bounds__(NTH) void at_pressure_kernel(mdq_ipcs_desc d, int32_t* iters, int fresh) {
-  extern __shared__ __align__(16) double smem[];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  // (`fresh`: the first step of mdq_ipcs_evolve_fresh - the iteration word starts from zero; cleared HERE by the thread that
-  //  adds to it at the end, so that the flag is not live across the solve: this kernel sits at its register cap)
-  if (fresh && tid == 0 && iters) iters[3 * b + 1] = 0;
-  const EnvView v = env_view(d, b);
-  const int n2 = v.n2, nv = v.nv;
-  const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
-  const double a = v.rho / v.dt, mu = v.mu;
-  (void)a; (void)mu; (void)nv; (void)n2;
-  double* red = smem;  // 64 doubles
-  double* U = smem + 64;
-  double* w = v.work;
-  double2* xs = reinterpret_cast<double2*>(w + 12 * (int64_t)d.NT);  // x of the velocity solve = u*
-  double* pnew = reinterpret_cast<double*>(xs + 6 * (int64_t)d.N2);
-  int rsel = 0;  // parity of the one-barrier reductions
-  (void)rsel; (void)pnew; (void)red;
-  double* px = U;
-  double* pr = px + P.NVp;
-  double* pp = pr + P.NVp;
-  double* pq = pp + P.NVp;
-  double* lK = pq + P.NVp;
-  int32_t* lci = reinterpret_cast<int32_t*>(lK + d.NSE1);
-  int32_t* lso = lci + d.NSE1 + (d.NSE1 & 1);
-  double* escr1 = w;
-  const int nsl1 = (nv + 63) >> 6;
-  const int32_t* so1 = K1_LDS ? lso : v.sl1_off;
-  const int32_t* ci1 = K1_LDS ? lci : v.sl1_col;
-  const double* K1 = K1_LDS ? lK : v.K1s;
-  int it_p = 0;
-#ifdef MDQ_AT_TRACE
-  const long long tq0_ = __builtin_amdgcn_s_memtime();
-#endif
-  {
-    // ================= step 2: pressure
-    if (K1_LDS && !d.pd_enabled) {
-      const int ne1 = v.sl1_off[nsl1];
-      for (int kk = tid; kk < ne1; kk += NTH) {
-        lK[kk] = v.K1s[kk];
-        lci[kk] = v.sl1_col[kk];
-      }
-      for (int kk = tid; kk <= nsl1; kk += NTH) lso[kk] = v.sl1_off[kk];
-    }
-    (void)escr1;
-    for (int i = tid; i < nv; i += NTH) pr[i] = 0.0;
-    __syncthreads();
-    rhs2_accumulate_lds<NTH>(v, d, xs, v.p_n, pr);
-    // own-row data of the scaling, loaded in front of the barrier that ends the accumulation
-    constexpr int PRW = 2048 / NTH;   // own rows per thread held in registers (vertex capacity of the LDS modes < 2048)
-    double sd_[PRW], pn_[PRW];
-    unsigned fl_ = 0;
-#pragma unroll
-    for (int k = 0; k < PRW; ++k) {
-      const int i = min(tid + k * NTH, nv - 1);
-      sd_[k] = v.sdiagK[i];
-      pn_[k] = v.p_n[i];
-      fl_ |= v.bcp_flag[i] ? 1u << k : 0u;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PRW; ++k) {
-      const int i = tid + k * NTH;
-      if (i < nv) {
-        pr[i] = ((fl_ >> k) & 1u) ? 0.0 : pr[i] / sd_[k];
-        px[i] = pn_[k] * sd_[k];
-      }
-    }
-    for (int i = tid + PRW * NTH; i < nv; i += NTH) {   // (nv beyond 2048: generic tail)
-      const double sd = v.sdiagK[i];
-      pr[i] = v.bcp_flag[i] ? 0.0 : pr[i] / sd;
-      px[i] = v.p_n[i] * sd;
-    }
-    // (an environment whose factors could not be built on the device - mdq_ipcs_factorize_pressure, header nparts = 0 -
-    // falls back to the Krylov solve)
-    if (d.pd_enabled && d.pd_hdr[4 * (int64_t)b + 2] > 0) {
-      const PdView pd = pd_view(d, b);
-#ifdef MDQ_AT_TRACE
-      { const long long tn_ = __builtin_amdgcn_s_memtime(); if (tid == 0 && b == 0) mdq_pt_trace_buf[0] += tn_ - tq0_; }
-#endif
-      pressure_direct<NTH>(pd, nv, pr, px, pp, pq, lK);
-    } else {
-      int itc = -1;
-      // (the 1024-thread instance is the direct solver's shape - 128 VGPRs per thread: the register-hungry Krylov variants
-      //  compiled into it cost 272 B of scratch per lane in round 3 without ever running there; an environment without
-      //  factors takes the plain register CG below)
-      if constexpr (NTH <= 512) {
-        if (d.pcg_degree < 0)                    // two-level additive preconditioner (geometric aggregates)
-          itc = cg_pressure_2l<NTH>(nv, so1, ci1, K1, v.coords, d.rtol, d.maxit_p, px, pr, pp, P.NVp, red, rsel);
-        else if (nv <= 2 * NTH && d.pcg_degree > 0)   // rows in registers, Chebyshev-preconditioned (degree 1: Jacobi only)
-          itc = cg_pressure_cheb<NTH>(nv, so1, ci1, K1, d.rtol, d.maxit_p, d.pcg_degree, px, pr, pp, red, rsel);
-        if (itc < 0 && nv <= 2 * NTH && d.pcg_degree == 0 && MDQ_PCG_REGM)   // rows in registers, branch-free application
-          itc = cg_pressure_regm<NTH>(nv, so1, ci1, K1, d.rtol, d.maxit_p, px, pr, pp, red, rsel);
-      }
-      if (itc >= 0)
-        it_p += itc;
-      else if (nv <= 2 * NTH)
-        it_p += cg_pressure_reg<NTH>(nv, so1, ci1, K1, d.rtol, d.maxit_p, px, pr, pp, red, rsel);
-      else
-        it_p += cg_pressure(nv, so1, ci1, K1, d.rtol, d.maxit_p, px, pr, pp, pq, red);
-    }
-    for (int i = tid; i < nv; i += NTH) pnew[i] = px[i] / v.sdiagK[i];
-    __syncthreads();
-
-  }
-  if (tid == 0 && iters) iters[3 * b + 1] += it_p;
-}
-
 #if MDQ_IN_PART(0)
-static __global__ __launch_bounds__(WG) void at_correction_kernel(mdq_ipcs_desc d, int nsteps, int step, double* drag,
-                                                            double* lift, int32_t* iters, const double* inflow_scale,
-                                                            int fresh) {
-  extern __shared__ __align__(16) double smem[];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const EnvView v = env_view(d, b);
-  const double ai = inflow_factor(inflow_scale, b, nsteps, step);
-  const bool fresh0 = fresh && step == 0;
-  const int n2 = v.n2, nv = v.nv;
-  const LdsPlan P = lds_plan(d.N2, d.NV, d.NSE1);
-  const double a = v.rho / v.dt, mu = v.mu;
-  (void)a; (void)mu; (void)nv; (void)n2;
-  double* red = smem;  // 64 doubles
-  double* U = smem + 64;
-  double* w = v.work;
-  double2* xs = reinterpret_cast<double2*>(w + 12 * (int64_t)d.NT);  // x of the velocity solve = u*
-  double* pnew = reinterpret_cast<double*>(xs + 6 * (int64_t)d.N2);
-  int rsel = 0;  // parity of the one-barrier reductions
-  (void)rsel; (void)pnew; (void)red;
-  double2* Pl = reinterpret_cast<double2*>(U);
-  double2* Yl = Pl + P.N2p;
-  double* Yd = reinterpret_cast<double*>(Yl);
-  AtMeta tm;
-  at_prefetch(v, tm, 0);
-  int it_m = 0;
-  // ring of the last three corrections u_{n+1} - u* (in the slab region the assembled modes use for their history)
-  double2* cring = reinterpret_cast<double2*>(w + work_hist_offset(d.NV, d.NT, d.NE));
-  double* ccnt = reinterpret_cast<double*>(cring + 3 * (int64_t)d.N2);  // [0]: corrections stored, [1]: ring position
-  const int nc = fresh0 ? 0 : (int)ccnt[0], rp = fresh0 ? 0 : (int)ccnt[1];
-#ifdef MDQ_AT_TRACE
-  long long tq_ = __builtin_amdgcn_s_memtime();
-#endif
-  __syncthreads();
-  CT_STAMP(0)
-  {
-    // ================= step 3: velocity correction (mass solve, both components)
-    double2 x[MF_ROWS], r[MF_ROWS], p[MF_ROWS];
-    double ism[MF_ROWS];
-    double am[2] = {0.0, 0.0};
-    // Row loops as in at_velocity_kernel: clamped rows, all loads of a phase issued before their first use.
-    int rc[MF_ROWS];
-#pragma unroll
-    for (int k = 0; k < MF_ROWS; ++k) rc[k] = min(tid + k * WG, n2 - 1);
-    double* Dp = reinterpret_cast<double*>(Yl + P.N2p);   // [nv] pressure increment, staged for the element loop
-    // initial guess of the correction: extrapolation in time of the stored ones (constant, linear, quadratic as the
-    // ring fills): 5.0 CG iterations per step with the previous correction alone, 1.7 with the quadratic guess (the
-    // velocity solve then needs 2.9 instead of 2.6 iterations: u_n now carries the full 1e-10 solver noise).
-    // Dirichlet rows keep u* = g (their stored corrections are 0).
-    auto load_delta = [&](double2(&dl)[MF_ROWS]) {
-#pragma unroll
-      for (int k = 0; k < MF_ROWS; ++k) dl[k] = make_double2(0.0, 0.0);
-      if (nc >= 1) {
-        const double2* c1 = cring + (int64_t)((rp + 2) % 3) * d.N2;   // newest
-        const double2* c2 = cring + (int64_t)((rp + 1) % 3) * d.N2;
-        const double2* c3 = cring + (int64_t)rp * d.N2;               // oldest (overwritten at the end of this launch)
-#pragma unroll
-        for (int k = 0; k < MF_ROWS; ++k) dl[k] = c1[rc[k]];
-        if (nc >= 2) {
-          const double w1 = nc >= 3 ? 3.0 : 2.0, w2 = nc >= 3 ? -3.0 : -1.0;
-#pragma unroll
-          for (int k = 0; k < MF_ROWS; ++k) {
-            const double2 b2 = c2[rc[k]];
-            dl[k] = make_double2(w1 * dl[k].x + w2 * b2.x, w1 * dl[k].y + w2 * b2.y);
-          }
-          if (nc >= 3) {
-#pragma unroll
-            for (int k = 0; k < MF_ROWS; ++k) {
-              const double2 b3 = c3[rc[k]];
-              dl[k] = make_double2(dl[k].x + b3.x, dl[k].y + b3.y);
-            }
-          }
-        }
-      }
-    };
-    // FUSED start (15 of 16 steps once the ring is full): with x0 = u* + delta0 the initial residual is
-    //   f3 - M x0 = (M u* - g) - M (u* + delta0) = -g - M delta0,
-    // ONE element loop (the right-hand-side operator applied to -delta0) instead of two (f3, then M x0), and no
-    // lifting vector (delta0 vanishes on the Dirichlet rows).  What it cannot give is |b| of the stopping test
-    // rtol |b|, which needs f3 itself: the value of the last exact start is used (it changes by < 1e-3 per step);
-    // every 16th step, and while the ring fills, the exact two-loop start runs and refreshes it.
-    const double bb_lag = fresh0 ? 0.0 : ccnt[2];
-    const int cstep = fresh0 ? 0 : (int)ccnt[3];
-    const bool fused = nc >= 3 && bb_lag > 0.0 && (cstep & 15) != 0;
-    {
-      // operator input (u*, or -delta0) and p_new - p_n staged in LDS: the element loop gathers from LDS, not L2
-      double2 us[MF_ROWS];
-      if (!fused) {
-#pragma unroll
-        for (int k = 0; k < MF_ROWS; ++k) us[k] = xs[rc[k]];
-      } else {
-        load_delta(us);
-#pragma unroll
-        for (int k = 0; k < MF_ROWS; ++k) us[k] = make_double2(-us[k].x, -us[k].y);
-      }
-      for (int i = tid; i < nv; i += WG) Dp[i] = pnew[i] - v.p_n[i];
-#pragma unroll
-      for (int k = 0; k < MF_ROWS; ++k) {
-        const int row = tid + k * WG;
-        if (row < n2) {
-          Pl[row] = us[k];
-          Yl[row] = make_double2(0.0, 0.0);
-        }
-      }
-    }
-    __syncthreads();
-    atomic_accumulate<true>(v, Yd, tm, [&](int, const Geo& g, const ElemIdx& E, int, double2(&ye)[6]) {
-      double2 ue[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) ue[i] = Pl[E.dof[i]];
-      double dp[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) dp[i] = Dp[E.dof[i]];
-      elem_rhs3(g, v.dt, ue, dp, ye);
-    });
-    // own rows of the global vectors of the next phase: issued in front of the barrier that ends the element loop
-    double2 l3[MF_ROWS], dlt[MF_ROWS];
-    unsigned flm = 0;
-    if (!fused) load_delta(dlt);   // (the fused start reads delta0 back from its LDS copy below)
-#pragma unroll
-    for (int k = 0; k < MF_ROWS; ++k) {
-      // fused start: u* of the own rows (the LDS copy holds -delta0; its Dirichlet rows carry this step's a g from step 1)
-      l3[k] = fused ? xs[rc[k]] : scaled2(ai, v.lift3[rc[k]]);
-      ism[k] = v.sdiagM[rc[k]];
-      flm |= v.bcu_flag[rc[k]] ? 1u << k : 0u;
-    }
-    __syncthreads();
-    CT_STAMP(1)
-    double bb;
-    if (fused) {
-#pragma unroll
-      for (int k = 0; k < MF_ROWS; ++k) {
-        r[k] = Yl[rc[k]];
-        const double2 md = Pl[rc[k]];
-        dlt[k] = make_double2(-md.x, -md.y);
-      }
-#pragma unroll
-      for (int k = 0; k < MF_ROWS; ++k) {
-        const int row = tid + k * WG;
-        const bool fl = (flm >> k) & 1u;
-        ism[k] = (row < n2 && !fl) ? 1.0 / ism[k] : 0.0;
-        r[k] = make_double2(r[k].x * ism[k], r[k].y * ism[k]);          // 0 on constrained rows and past n2
-        p[k] = r[k];
-        am[1] += r[k].x * r[k].x + r[k].y * r[k].y;
-        // scaled unknown S x0 on the free rows, u* = g on the Dirichlet rows
-        x[k] = fl ? l3[k] : make_double2((l3[k].x + dlt[k].x) / (ism[k] != 0.0 ? ism[k] : 1.0),
-                                          (l3[k].y + dlt[k].y) / (ism[k] != 0.0 ? ism[k] : 1.0));
-        if (row >= n2) x[k] = make_double2(0.0, 0.0);
-      }
-      double a1r[1] = {am[1]};
-      block_sum<1>(a1r, red);
-      am[1] = a1r[0];
-      bb = bb_lag;
-      CT_STAMP(2)
-      CT_STAMP(3)
-    } else {
-      double2 f3[MF_ROWS];
-#pragma unroll
-      for (int k = 0; k < MF_ROWS; ++k) {
-        f3[k] = Yl[rc[k]];
-        x[k] = Pl[rc[k]];      // u* (own row)
-      }
-#pragma unroll
-      for (int k = 0; k < MF_ROWS; ++k) {
-        const int row = tid + k * WG;
-        const bool fl = (flm >> k) & 1u;
-        ism[k] = (row < n2 && !fl) ? 1.0 / ism[k] : 0.0;
-        if (!fl) x[k] = make_double2(x[k].x + dlt[k].x, x[k].y + dlt[k].y);
-        if (row < n2) {
-          Yl[row] = make_double2(0.0, 0.0);
-          Pl[row] = x[k];      // stage S^-1 (S x0) = x0
-          const double2 bi = fl ? x[k] : make_double2((f3[k].x - l3[k].x) * ism[k], (f3[k].y - l3[k].y) * ism[k]);
-          am[0] += bi.x * bi.x + bi.y * bi.y;
-        } else {
-          f3[k] = make_double2(0.0, 0.0);
-        }
-      }
-      // (x0 is not carried in registers across the element loop below - 28 VGPRs the loop's two interleaved triangles need,
-      //  spilled to scratch in round 3: its own rows are read back from the staged copy, which the loop only reads)
-      __syncthreads();
-      CT_STAMP(2)
-      // (one triangle at a time: beside f3 / ism / the prefetched metadata the two interleaved triangles of the other
-      //  applications did not fit - 180 B of scratch per lane in round 3; this application runs once per launch)
-      atomic_accumulate<MDQ_CORR_MX0_INTERLEAVE>(v, Yd, tm, [&](int, const Geo& g, const ElemIdx& E, int, double2(&ye)[6]) {
-        double2 xe[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) xe[i] = Pl[E.dof[i]];
-        elem_mass(g, xe, ye);
-      });
-      __syncthreads();
-      CT_STAMP(3)
-#pragma unroll
-      for (int k = 0; k < MF_ROWS; ++k) {
-        const int row = tid + k * WG;
-        r[k] = p[k] = x[k] = make_double2(0.0, 0.0);
-        if (row < n2) {
-          const double2 ax = Yl[row];
-          x[k] = Pl[row];
-          r[k] = make_double2((f3[k].x - ax.x) * ism[k], (f3[k].y - ax.y) * ism[k]);  // 0 on constrained rows
-          p[k] = r[k];
-          am[1] += r[k].x * r[k].x + r[k].y * r[k].y;
-          if (ism[k] != 0.0) x[k] = make_double2(x[k].x / ism[k], x[k].y / ism[k]);  // scaled unknown S x
-        }
-      }
-      block_sum<2>(am, red);
-      bb = am[0];
-      if (tid == 0) ccnt[2] = bb;
-    }
-    CT_STAMP(4)
-    {
-      const double tol2 = d.rtol * d.rtol * bb;
-      double rr = am[1];
-      if (rr > tol2 && bb != 0.0) {
-        int it = 0;
-        while (it < d.maxit_m) {
-          ++it;
-#pragma unroll
-          for (int k = 0; k < MF_ROWS; ++k) {
-            const int row = tid + k * WG;
-            if (row < n2) {
-              Pl[row] = make_double2(p[k].x * ism[k], p[k].y * ism[k]);
-              Yl[row] = make_double2(0.0, 0.0);
-            }
-          }
-          __syncthreads();
-          CT_STAMP(5)
-          atomic_accumulate<true>(v, Yd, tm, [&](int, const Geo& g, const ElemIdx& E, int, double2(&ye)[6]) {
-            double2 xe[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) xe[i] = Pl[E.dof[i]];
-            elem_mass(g, xe, ye);
-          });
-          __syncthreads();
-          CT_STAMP(6)
-          double a1[1] = {0.0};
-          double2 q[MF_ROWS];
-#pragma unroll
-          for (int k = 0; k < MF_ROWS; ++k) {
-            const int row = tid + k * WG;
-            q[k] = make_double2(0.0, 0.0);
-            if (row < n2) {
-              const double2 yv = Yl[row];
-              q[k] = make_double2(yv.x * ism[k], yv.y * ism[k]);
-              a1[0] += p[k].x * q[k].x + p[k].y * q[k].y;
-            }
-          }
-          block_sum1<1>(a1, red, rsel);
-          CT_STAMP(7)
-          if (!(a1[0] > 0.0)) break;
-          const double alpha = rr / a1[0];
-          double a2[1] = {0.0};
-#pragma unroll
-          for (int k = 0; k < MF_ROWS; ++k) {
-            x[k] = make_double2(x[k].x + alpha * p[k].x, x[k].y + alpha * p[k].y);
-            r[k] = make_double2(r[k].x - alpha * q[k].x, r[k].y - alpha * q[k].y);
-            a2[0] += r[k].x * r[k].x + r[k].y * r[k].y;
-          }
-          block_sum1<1>(a2, red, rsel);
-          CT_STAMP(8)
-          const double rr_new = a2[0];
-          if (!(rr_new > tol2)) break;
-          const double beta = rr_new / rr;
-          rr = rr_new;
-#pragma unroll
-          for (int k = 0; k < MF_ROWS; ++k)
-            p[k] = make_double2(r[k].x + beta * p[k].x, r[k].y + beta * p[k].y);
-        }
-        it_m += it;
-      }
-    }
-
-    // ================= update state + probes
-    {
-      double2 us[MF_ROWS];
-#pragma unroll
-      for (int k = 0; k < MF_ROWS; ++k) us[k] = xs[rc[k]];
-      double2* cnew = cring + (int64_t)rp * d.N2;
-#pragma unroll
-      for (int k = 0; k < MF_ROWS; ++k) {
-        const int row = tid + k * WG;
-        if (row < n2) {
-          const double2 un = (ism[k] != 0.0) ? make_double2(x[k].x * ism[k], x[k].y * ism[k]) : x[k];
-          v.u_n[row] = un;
-          cnew[row] = (ism[k] != 0.0) ? make_double2(un.x - us[k].x, un.y - us[k].y) : make_double2(0.0, 0.0);
-        }
-      }
-    }
-    if (tid == 0) {
-      ccnt[0] = (double)(nc < 3 ? nc + 1 : 3);
-      ccnt[1] = (double)((rp + 1) % 3);
-      ccnt[3] = (double)((cstep + 1) & 1023);
-      if (fresh0) {   // the history counters of the other operator modes, as reset_history_kernel leaves them
-        double* hcnt = reinterpret_cast<double*>(cring + 5 * (int64_t)d.N2);
-        hcnt[0] = hcnt[1] = 0.0;
-      }
-    }
-    for (int i = tid; i < nv; i += WG) v.p_n[i] = pnew[i];
-    __syncthreads();
-    CT_STAMP(9)
-    double dr, li;
-    forces(v, v.mu, v.u_n, v.p_n, red, dr, li);
-    CT_STAMP(10)
-    if (tid == 0) {
-      drag[(int64_t)b * nsteps + step] = dr;
-      lift[(int64_t)b * nsteps + step] = li;
-    }
-  }
-  if (tid == 0 && iters) iters[3 * b + 2] = (fresh0 ? 0 : iters[3 * b + 2]) + it_m;
-}
+}  // namespace mdq
+#include "mdq_ipcs_mode3.hip"
+namespace mdq {
 #endif
 
 
@@ -4995,347 +3417,8 @@ hipError_t part_launch_mf(bool k1_lds, const EvolveArgs& a) {
 }
 #endif
 
-#if MDQ_IN_PART(0)
-static thread_local std::string g_err;
-
-static int fail(const char* what, hipError_t e) {
-  g_err = std::string(what) + ": " + hipGetErrorString(e);
-  return -1;
-}
-static int fail_msg(const std::string& m) {
-  g_err = m;
-  return -2;
-}
-
-static int ensure_tables() {
-  const hipError_t err = upload_tables();
-  if (err != hipSuccess) return fail("hipMemcpyToSymbol(c_tab)", err);
-  return 0;
-}
-
-static int check_desc(const mdq_ipcs_desc* d) {
-  if (!d) return fail_msg("null descriptor");
-  if (d->B <= 0 || d->NV <= 0 || d->NT <= 0 || d->NE <= 0) return fail_msg("bad batch sizes");
-  if (d->N2 != d->NV + d->NE) return fail_msg("N2 must equal NV+NE");
-  if (d->work_doubles < (int64_t)d->B * work_per_env(d->NV, d->NT, d->NE))
-    return fail_msg("workspace too small (see mdq_ipcs_workspace_doubles)");
-  if (!(d->dt > 0.0) || !(d->rho > 0.0)) return fail_msg("dt and rho must be positive");
-  return 0;
-}
-
-#endif  // part 0
 }  // namespace mdq
 
 #if MDQ_IN_PART(0)
-// shared by the other translation units of the library (mdq_internal.h)
-int mdq_set_error(const char* msg) {
-  mdq::g_err = msg;
-  return -2;
-}
-
-using namespace mdq;
-
-extern "C" {
-
-int mdq_abi_version(void) { return MDQ_ABI_VERSION; }
-
-const char* mdq_last_error(void) { return g_err.c_str(); }
-
-int64_t mdq_ipcs_workspace_doubles(int32_t B, int32_t NV, int32_t NT, int32_t NE) {
-  return (int64_t)B * work_per_env(NV, NT, NE);
-}
-
-int mdq_ipcs_reset_history(const mdq_ipcs_desc* d, int32_t* iters, void* stream) {
-  if (int rc = check_desc(d)) return rc;
-  hipLaunchKernelGGL(reset_history_kernel, dim3((d->B + 63) / 64), dim3(64), 0, (hipStream_t)stream, *d, iters);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail("reset_history_kernel launch", e);
-  return 0;
-}
-
-int mdq_ipcs_assemble(const mdq_ipcs_desc* d, void* stream) {
-  if (int rc = check_desc(d)) return rc;
-  if (int rc = ensure_tables()) return rc;
-  hipLaunchKernelGGL(assemble_kernel, dim3(d->B), dim3(WG), 0, (hipStream_t)stream, *d);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail("assemble_kernel launch", e);
-  return 0;
-}
-
-int mdq_ipcs_setup_matfree(const mdq_ipcs_desc* d, void* stream) {
-  if (int rc = check_desc(d)) return rc;
-  if (!d->coords || !d->cell_dofs || !d->cell_outflow || !d->g1_ptr || !d->g1_src || !d->g2_ptr || !d->g2_src ||
-      !d->sl1_off || !d->sl1_col || !d->bcu_flag || !d->bcu_gx || !d->bcp_flag || !d->geom || !d->lift1 || !d->lift3 ||
-      !d->idiag1 || !d->sdiagM || !d->sdiagK || !d->K1s)
-    return fail_msg("mdq_ipcs_setup_matfree: incomplete descriptor");
-  if (d->nbo && (!d->bo_rows || !d->bo_ptr || !d->bo_col || !d->bo_src || !d->bo_val))
-    return fail_msg("mdq_ipcs_setup_matfree: outflow row list incomplete");
-  if (int rc = ensure_tables()) return rc;
-  // staged instance when the mesh's per-cell / per-dof data fit the LDS beside the kernel's static tables
-  const size_t stage_bytes = 52 * (size_t)d->NT + 9 * (size_t)d->N2 + 9 * (size_t)d->NV + 64;
-  hipError_t e;
-  // + the slot lists (16-bit: slot ids < 6 NT <= 65535, pointers likewise) when they fit as well
-  const size_t list_bytes = 2 * ((size_t)d->N2 + 1 + 6 * (size_t)d->NT + (size_t)d->NV + 1 + 3 * (size_t)d->NT) + 2;
-  if (stage_bytes + list_bytes <= 156 * 1024 && 6 * (size_t)d->NT <= 65535) {
-    const size_t bytes = stage_bytes + list_bytes;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&setup_matfree_kernel<true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return fail("setup_matfree_kernel attribute", e);
-    hipLaunchKernelGGL((setup_matfree_kernel<true, true>), dim3(d->B), dim3(SWG), bytes, (hipStream_t)stream, *d);
-  } else if (stage_bytes <= 156 * 1024) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&setup_matfree_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)stage_bytes);
-    if (e != hipSuccess) return fail("setup_matfree_kernel attribute", e);
-    hipLaunchKernelGGL(setup_matfree_kernel<true>, dim3(d->B), dim3(SWG), stage_bytes, (hipStream_t)stream, *d);
-  } else if (const size_t idx_bytes = 12 * (size_t)d->NT + (size_t)d->N2 + 9 * (size_t)d->NV + 64;
-             idx_bytes <= 156 * 1024 && d->N2 <= 65535 && std::getenv("MDQ_SETUP_UNSTAGED") == nullptr) {
-    // (the index data alone: cell dofs, flags, the P1 scaling; MDQ_SETUP_UNSTAGED=1: the unstaged instance, A / B switch)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&setup_matfree_kernel<true, false, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)idx_bytes);
-    if (e != hipSuccess) return fail("setup_matfree_kernel attribute", e);
-    hipLaunchKernelGGL((setup_matfree_kernel<true, false, false>), dim3(d->B), dim3(SWG), idx_bytes, (hipStream_t)stream, *d);
-  } else {
-    hipLaunchKernelGGL(setup_matfree_kernel<false>, dim3(d->B), dim3(SWG), 0, (hipStream_t)stream, *d);
-  }
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail("setup_matfree_kernel launch", e);
-  return 0;
-}
-
-static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                            const double* inflow_scale, void* stream, double* kernel_ms, int fresh = 0,
-                            const mdq_inflow_profile* prof = nullptr);
-
-// the argument checks of the two inflow-profile entry points (`entry`: the name their messages carry), then the step loop
-static int evolve_profile_checked(const char* entry, int fresh, const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift,
-                                  int32_t* iters, const mdq_inflow_profile* prof, void* stream) {
-  if (prof) {
-    const auto bad = [entry](const char* what) { return fail_msg(std::string(entry) + what); };
-    if (prof->NIN <= 0 || prof->NIR <= 0) return bad(": NIN and NIR must be positive");
-    if (!prof->n_inlet || !prof->inlet_dofs || !prof->n_rows || !prof->rows || !prof->values)
-      return bad(": incomplete inflow profile (n_inlet, inlet_dofs, n_rows, rows, values)");
-    if (d && (!d->cell_dofs || !d->g2_ptr || !d->g2_src || !d->bcu_flag || !d->bcu_gx || !d->geom || !d->lift1 || !d->lift3))
-      return bad(": incomplete descriptor (cell_dofs, g2_ptr, g2_src, bcu_flag, bcu_gx, geom, lift1, lift3)");
-  }
-  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, nullptr, fresh, prof);
-}
-
-int mdq_ipcs_evolve_profile(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                            const mdq_inflow_profile* prof, void* stream) {
-  return evolve_profile_checked("mdq_ipcs_evolve_profile", 0, d, nsteps, drag, lift, iters, prof, stream);
-}
-
-int mdq_ipcs_evolve_fresh_profile(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                                  const mdq_inflow_profile* prof, void* stream) {
-  return evolve_profile_checked("mdq_ipcs_evolve_fresh_profile", 1, d, nsteps, drag, lift, iters, prof, stream);
-}
-
-int mdq_ipcs_build_inlet_map(const mdq_ipcs_desc* d, int32_t NIN, int32_t NIR, const int32_t* n_ref, const double* inlet_y,
-                             int32_t* n_inlet, int32_t* inlet_dofs, int32_t* n_rows, int32_t* rows, int32_t* map_status,
-                             void* stream) {
-  if (!d || d->B <= 0 || d->NV <= 0 || d->NT <= 0 || d->NE <= 0 || d->N2 != d->NV + d->NE)
-    return fail_msg("mdq_ipcs_build_inlet_map: bad batch sizes");
-  if (!d->nv || !d->nt || !d->ne || !d->coords || !d->cell_dofs || !d->cell_outflow || !d->bcu_flag || !d->bcu_gx)
-    return fail_msg("mdq_ipcs_build_inlet_map: incomplete descriptor (nv, nt, ne, coords, cell_dofs, cell_outflow, bcu_flag, bcu_gx)");
-  if (d->N2 > MAP_BITS)
-    return fail_msg("mdq_ipcs_build_inlet_map: N2 > " + std::to_string(MAP_BITS) + " (the inlet map serves the meshes of operator mode 3)");
-  if (NIN <= 0 || NIN > MAP_NIN || NIR <= 0)
-    return fail_msg("mdq_ipcs_build_inlet_map: NIN must be in 1 .. " + std::to_string(MAP_NIN) + " and NIR positive");
-  if (!n_ref || !inlet_y || !n_inlet || !inlet_dofs || !n_rows || !rows || !map_status)
-    return fail_msg("mdq_ipcs_build_inlet_map: null table (n_ref, inlet_y, n_inlet, inlet_dofs, n_rows, rows, map_status)");
-  hipLaunchKernelGGL(inlet_map_kernel, dim3(d->B), dim3(MWG), 0, (hipStream_t)stream, *d, NIN, NIR, n_ref, inlet_y, n_inlet,
-                     inlet_dofs, n_rows, rows, map_status);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail("inlet_map_kernel launch", e);
-  return 0;
-}
-
-int mdq_ipcs_evolve(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                    void* stream) {
-  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, nullptr);
-}
-
-int mdq_ipcs_evolve_inflow(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                           const double* inflow_scale, void* stream) {
-  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, inflow_scale, stream, nullptr);
-}
-
-int mdq_ipcs_evolve_fresh(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                          const double* inflow_scale, void* stream) {
-  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, inflow_scale, stream, nullptr, 1);
-}
-
-int mdq_ipcs_evolve_timed(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                          void* stream, double* kernel_ms) {
-  if (!kernel_ms) return fail_msg("kernel_ms is required");
-  if (d && d->mode != 3 && d->mode != -1) return fail_msg("per-kernel timing exists for the three-kernel mode 3 only");
-  return ipcs_evolve_impl(d, nsteps, drag, lift, iters, nullptr, stream, kernel_ms);
-}
-
-static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag, double* lift, int32_t* iters,
-                            const double* inflow_scale, void* stream, double* kernel_ms, int fresh,
-                            const mdq_inflow_profile* prof) {
-  if (int rc = check_desc(d)) return rc;
-  if (nsteps <= 0) return fail_msg("nsteps must be positive");
-  if (!drag || !lift) return fail_msg("drag/lift output pointers are required");
-  if (int rc = ensure_tables()) return rc;
-  const LdsPlan P = lds_plan(d->N2, d->NV, d->NSE1);
-  const size_t LDS_MAX = 160 * 1024, red_bytes = 64 * sizeof(double);
-  // pressure CG vectors beyond the LDS: kept in the workspace slab (modes 0 / 5; Jacobi-CG only - the factorisation has
-  // its own, smaller limits and reports such a mesh through pd_status)
-  const bool pg = red_bytes + P.prs_vec_bytes > LDS_MAX;
-  // (pd_enabled with pg: the factors' own limits are far below this size - every such environment has nparts = 0 and
-  //  takes the Krylov branch anyway; a small mesh riding along in the big layout is solved by CG as well)
-  const bool k1_lds = !pg && !d->pd_enabled && red_bytes + P.prs_vec_bytes + P.prs_mat_bytes <= LDS_MAX;
-  int mode = d->mode;
-  // mode 5: the element tile (+ the stage of a chunk's input rows behind it when the packed local maps are given and fit)
-  const size_t tile_bytes = tile_lds_bytes(*d);
-  if (mode == 6) return fail_msg("unknown operator mode 6");
-  if (mode < 0 || mode > 7) {  // auto: fastest variant that fits
-    mode = 0;
-    if (red_bytes + P.vel1_bytes <= LDS_MAX) mode = 1;
-    if (red_bytes + P.vel2_bytes <= LDS_MAX && d->N2 <= MF_ROWS * WG) mode = 2;
-    // (mode -2 = auto among the BITWISE REPRODUCIBLE variants: everything but the LDS-atomic mode 3)
-    if (d->mode != -2 && red_bytes + P.vel3_bytes <= LDS_MAX && d->N2 <= MF_ROWS * WG) mode = 3;
-    // a mesh beyond the LDS-resident vectors: the element tiles with global vectors (mode 5: ~5x less memory traffic than
-    // the assembled operators and no sparsity pattern), when the tile maps were handed over
-    if (mode == 0 && d->cell_outflow && ((d->mf_scat && d->mf_tptr) || (d->g2_ptr && d->g2_src)) && std::getenv("MDQ_NO_MODE5") == nullptr) mode = 5;
-    if (mode == 0) {
-      // a mesh that only fits the assembled global-memory path: two workgroups per environment while the batch leaves
-      // at least half of the chip idle even so (measured on ys930 red-refined, ms per step one / two workgroups: B = 1
-      // 13.7 / 8.0, 32: 16.7 / 11.9, 64: 24.5 / 22.0, 96: 26.0 / 29.3, 128: 20.0 / 26.1 - from ~64 environments on the
-      // step is bound by the memory system as a whole, and the team barriers' cache write-backs / invalidations only add)
-      const int ncu = team_cus((hipStream_t)stream);
-      if (!pg && 2 * TEAM * d->B <= ncu) mode = 4;
-    }
-    // the element tiles with TWO workgroups per environment while the batch leaves half of the chip idle (BASELINE batch of
-    // 128 refined meshes: 11.3 -> ms per step; MDQ_NO_TEAM_TILES=1 is the A / B switch)
-    if (mode == 5 && !pg && std::getenv("MDQ_NO_TEAM_TILES") == nullptr) {
-      if (TEAM * d->B <= team_cus((hipStream_t)stream)) mode = 7;
-    }
-  }
-  if (kernel_ms && mode != 3) return fail_msg("per-kernel timing exists for the three-kernel mode 3 only");
-  // an inflow profile is rewritten BETWEEN the steps of a launch sequence: the modes that loop over the steps inside one kernel
-  // have no such place
-  if (prof && mode != 2 && mode != 3)
-    return fail_msg("mdq_ipcs_evolve_profile: operator mode " + std::to_string(mode) + " runs the steps of a call inside one kernel; "
-                    "an inflow profile is served by the per-step path (operator modes 2 and 3, or mdq_ipcs_setup_matfree + "
-                    "mdq_ipcs_evolve one step at a time)");
-  // a fresh history: mode 3 drops it inside the kernels of its first step; the one-kernel modes take the reset launch
-  if (fresh && mode != 3) {
-    hipLaunchKernelGGL(reset_history_kernel, dim3((d->B + 63) / 64), dim3(64), 0, (hipStream_t)stream, *d, iters);
-    if (hipError_t e_ = hipGetLastError(); e_ != hipSuccess) return fail("reset_history_kernel launch", e_);
-  }
-  if (mode == 3 && (red_bytes + P.vel3_bytes > LDS_MAX || d->N2 > MF_ROWS * WG))
-    return fail_msg("mode 3 needs N2 <= 3584 and three velocity vectors in LDS");
-  if (mode == 2 && (red_bytes + P.vel2_bytes > LDS_MAX || d->N2 > MF_ROWS * WG))
-    return fail_msg("matrix-free tile mode needs N2 <= 3584 and the x stage + element tile in LDS");
-  if (mode == 1 && red_bytes + P.vel1_bytes > LDS_MAX) return fail_msg("LDS gather vectors do not fit");
-  if ((mode == 5 || mode == 7) && (!d->cell_outflow || !((d->mf_scat && d->mf_tptr) || (d->g2_ptr && d->g2_src))))
-    return fail_msg("modes 5 / 7 need cell_outflow and the tile maps (mf_scat, mf_tptr) or the dof <- slot lists (g2_ptr, g2_src)");
-  if (pg && mode != 0 && mode != 5)
-    return fail_msg("mesh too large for the LDS-resident pressure vectors of this operator mode (use mode -1, 0 or 5)");
-  // (K1 values alias the scratch vector: CG does not use it; pg: the tables of the two-level preconditioner)
-  size_t u = pg ? tl_extra_bytes(d->NV) + sizeof(double) * NAG * NAG : P.prs_vec_bytes + (k1_lds ? P.prs_mat_bytes : 0);
-  const size_t vel = mode == 3 ? P.vel3_bytes : (mode == 2 ? P.vel2_bytes : (mode == 1 ? P.vel1_bytes : ((mode == 5 || mode == 7) ? tile_bytes : 0)));
-  if (vel > u) u = vel;
-  const size_t lds = red_bytes + u;
-  hipError_t e;
-  hipStream_t st = (hipStream_t)stream;
-  if (mode == 3) {
-    const size_t lds_v = red_bytes + P.vel3_bytes;
-    const size_t lds_p = red_bytes + P.prs_vec_bytes + (k1_lds ? P.prs_mat_bytes : 0);
-    const size_t lds_c = red_bytes + 2 * sizeof(double2) * (size_t)P.N2p + sizeof(double) * (size_t)P.NVp;  // p, result, dp
-    // once per process (thread-safe: several env groups call this entry point concurrently)
-    static const hipError_t attr_err = [] {
-      hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&at_velocity_kernel<WG, MF_ROWS, AT_PAIR>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e_ == hipSuccess)
-        e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&at_velocity_kernel<768, 5, 1>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e_ == hipSuccess)
-        e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&at_pressure_kernel<true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e_ == hipSuccess)
-        e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&at_pressure_kernel<false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e_ == hipSuccess)
-        e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&at_pressure_kernel<false, 1024>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e_ == hipSuccess)
-        e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&at_correction_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      return e_;
-    }();
-    if (attr_err != hipSuccess) return fail("hipFuncSetAttribute(mode 3 kernels)", attr_err);
-    // velocity kernel variant: 12 waves x 1 triangle stream (3 waves per SIMD, <= 170 VGPRs) or 8 waves x 2 interleaved
-    // triangle streams (2 per SIMD, 256 VGPRs); MDQ_AT_WG=512|768 overrides
-    static const int vel_wg = [] {
-      const char* s_ = std::getenv("MDQ_AT_WG");
-      const int w_ = s_ ? std::atoi(s_) : 768;
-      return w_ == 512 ? 512 : 768;
-    }();
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (kernel_ms) {
-      for (int i = 0; i < 4; ++i)
-        if ((e = hipEventCreate(&ev[i])) != hipSuccess) return fail("hipEventCreate", e);
-      kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0.0;
-    }
-    for (int step = 0; step < nsteps; ++step) {
-      if (prof)
-        if ((e = launch_inflow_lift(d, prof, nsteps, step, st)) != hipSuccess) return fail("inflow_lift_kernel launch", e);
-      if (kernel_ms) hipEventRecord(ev[0], st);
-      if (vel_wg == 768)
-        hipLaunchKernelGGL((at_velocity_kernel<768, 5, 1>), dim3(d->B), dim3(768), lds_v, st, *d, iters, inflow_scale, nsteps, step, fresh);
-      else
-        hipLaunchKernelGGL((at_velocity_kernel<WG, MF_ROWS, AT_PAIR>), dim3(d->B), dim3(WG), lds_v, st, *d, iters, inflow_scale, nsteps, step, fresh);
-      if (kernel_ms) hipEventRecord(ev[1], st);
-      if (d->pd_enabled)
-        hipLaunchKernelGGL((at_pressure_kernel<false, 1024>), dim3(d->B), dim3(1024), lds_p, st, *d, iters, fresh && step == 0);
-      else if (k1_lds)
-        hipLaunchKernelGGL(at_pressure_kernel<true>, dim3(d->B), dim3(WG), lds_p, st, *d, iters, fresh && step == 0);
-      else
-        hipLaunchKernelGGL(at_pressure_kernel<false>, dim3(d->B), dim3(WG), lds_p, st, *d, iters, fresh && step == 0);
-      if (kernel_ms) hipEventRecord(ev[2], st);
-      hipLaunchKernelGGL(at_correction_kernel, dim3(d->B), dim3(WG), lds_c, st, *d, nsteps, step, drag, lift, iters, inflow_scale, fresh);
-      if (kernel_ms) {
-        hipEventRecord(ev[3], st);
-        if ((e = hipEventSynchronize(ev[3])) != hipSuccess) return fail("hipEventSynchronize", e);
-        for (int i = 0; i < 3; ++i) {
-          float ms = 0.f;
-          hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-          kernel_ms[i] += ms;
-        }
-      }
-    }
-    if (kernel_ms)
-      for (int i = 0; i < 4; ++i) hipEventDestroy(ev[i]);
-    e = hipGetLastError();
-  } else {
-    const EvolveArgs a{d, lds, nsteps, drag, lift, iters, inflow_scale, st, prof};
-    if (mode == 2)
-      e = part_launch_mf(k1_lds, a);
-    else if (mode == 4 || mode == 5 || mode == 7)
-      e = part_launch_tiles(mode, k1_lds, pg, a);
-    else
-      e = part_launch_assembled(mode, k1_lds, pg, a);
-  }
-  if (e != hipSuccess) return fail("evolve_kernel launch", e);
-  return 0;
-}
-
-int mdq_probe_forces(const mdq_ipcs_desc* d, int32_t nfields, const double* u, const double* p, double* drag,
-                     double* lift, void* stream) {
-  // needs only: B, NV, NT, NE, N2, NAF, mu, nv, nt, ne, naf, coords, cell_dofs, af_facets
-  if (!d || d->B <= 0 || d->N2 != d->NV + d->NE || !d->coords || !d->cell_dofs || !d->af_facets)
-    return fail_msg("mdq_probe_forces: incomplete mesh descriptor");
-  if (nfields <= 0 || !u || !p || !drag || !lift) return fail_msg("bad probe arguments");
-  if (int rc = ensure_tables()) return rc;
-  hipLaunchKernelGGL(probe_kernel, dim3(d->B), dim3(WG), 0, (hipStream_t)stream, *d, nfields, u, p, drag, lift);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail("probe_kernel launch", e);
-  return 0;
-}
-
-}  // extern "C"
-#endif  // part 0
+#include "mdq_ipcs_entry.hip"
+#endif
