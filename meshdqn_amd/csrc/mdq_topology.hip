@@ -101,6 +101,33 @@ __device__ __forceinline__ int scan_excl(int* a, int n, int* part) {
   return total;
 }
 
+// Ordered compaction / scan at the width of its domain (K = 1): thread `tid` holds `run` = the number of flagged entries
+// (or the sum of the values) of ITS consecutive entries tid * per .. tid * per + per - 1 in registers; returns the exclusive
+// prefix over the threads and the total.  Nothing goes through `scanb`: no zero-fill, no read-back of the flags, no passes
+// that hold nothing - two barriers and the TW / 64 wave totals in `part` (scan_excl over TNS entries: the flag pass, the
+// read-back and three barriers with 18 LDS accesses per thread, whatever the domain is).
+__device__ __forceinline__ int scan_threads(int run, int* part, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int v = run;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int u = __shfl_up(v, off, 64);
+    if (lane >= off) v += u;
+  }
+  __syncthreads();   // (the previous call's readers of `part` are done)
+  if (lane == 63) part[wave] = v;
+  __syncthreads();
+  int pre = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < TW / 64; ++w) {
+    const int wt = part[w];
+    if (w < wave) pre += wt;
+    tot += wt;
+  }
+  total = tot;
+  return pre + v - run;
+}
+
 template <int SH>
 __device__ __forceinline__ uint32_t hslot_t(uint32_t key) { return (key * 2654435761u) >> SH; }
 
@@ -116,11 +143,12 @@ __device__ __forceinline__ double seg_dist2(double px, double py, double ax, dou
 
 #ifdef MDQ_TOPO_TRACE
 // debug build only: s_memtime deltas of thread 0 of mesh 0 at the section boundaries
-__device__ long long mdq_topo_trace_buf[16];
-#define TT_STAMP(k) { const long long tn_ = __builtin_amdgcn_s_memtime(); if (threadIdx.x == 0 && blockIdx.x == 0) mdq_topo_trace_buf[k] += tn_ - tq_; tq_ = tn_; }
+// (slots 0-15: launches without the flow_only index section - the env step's main stream -, 16-31: the flow stream's launch)
+__device__ long long mdq_topo_trace_buf[32];
+#define TT_STAMP(k) { const long long tn_ = __builtin_amdgcn_s_memtime(); if (threadIdx.x == 0 && blockIdx.x == 0) mdq_topo_trace_buf[(has_ipcs && O.flow_only ? 16 : 0) + k] += tn_ - tq_; tq_ = tn_; }
 extern "C" int mdq_topo_trace_host(long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mdq_topo_trace_buf), sizeof(long long) * 16) != hipSuccess) return -1;
-  if (reset) { long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(mdq_topo_trace_buf), z, sizeof z) != hipSuccess) return -1; }
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mdq_topo_trace_buf), sizeof(long long) * 32) != hipSuccess) return -1;
+  if (reset) { long long z[32] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(mdq_topo_trace_buf), z, sizeof z) != hipSuccess) return -1; }
   return 0;
 }
 #else
@@ -157,6 +185,12 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
   // (always inlined: with a seventh call site the compiler kept it as a FUNCTION - a call inside the kernel, 288 B of stack
   //  per lane and every section slower)
   auto scan_excl = [](int* a_, int n_, int* part_) __attribute__((always_inline)) { return mdq_topo::scan_excl<CP::PER>(a_, n_, part_); };
+  auto scan_threads = [](int run_, int* part_, int& total_) __attribute__((always_inline)) { return mdq_topo::scan_threads(run_, part_, total_); };
+  // The K = 1 instance's shorter sections, each with its parent's code behind a bit of idx_parent (MDQ_TOPO_INDEX_PARENT, see
+  // mdq_env_topology); the large-mesh instances keep the general paths.
+  const bool edge_pos = K == 1 && !(idx_parent & 4);       // the hash position of a slot kept from its insert
+  const bool narrow = K == 1 && !(idx_parent & 8);         // compactions at the width of their domain, flags in registers
+  static_assert(K != 1 || (TNV <= TW && TNS <= 32 * TW), "one vertex per thread, a thread's flags in one word");
   extern __shared__ __align__(16) unsigned char lds_[];
   unsigned char* smem = K == 1 ? lds_ : slab + (size_t)blockIdx.x * ((CP::BYTES + 255) & ~(size_t)255);
   double2* X = reinterpret_cast<double2*>(smem);                              // [TNV]
@@ -306,6 +340,11 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
         if (old == EMPTY || old == key || n_ >= HT) break;
         h = (h + 1) & (HT - 1);
       }
+      // The insert knows where its slot's key lives: the position (13 bits) is kept in eid_slot - free until the last pass
+      // below writes it - and the three later passes read hkey / hval there.  Each of them walked probe(slot_key(s)) again:
+      // two global loads of the cell and a dependent chain of hkey reads per slot and pass.  (In LDS, not in registers: the
+      // passes around the scan own different slots.  Written for a refused slot too: always a position inside the table.)
+      if (edge_pos) eid_slot[s] = (uint16_t)h;
       if (n_ >= HT) {
         status[b] = -1;                                    // more distinct edges than hash slots: not a mesh within the capacities
         continue;
@@ -318,7 +357,7 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
       int first = 0;
       if (s < nslots) {
         int a, c;
-        const uint32_t h = probe(slot_key(s, a, c));
+        const uint32_t h = edge_pos ? (uint32_t)eid_slot[s] : probe(slot_key(s, a, c));
         const uint32_t m = hval[h] & 0x7FFFFFFFu;
         first = m == (uint32_t)s;
         if (!first) atomicOr(&hval[h], 0x80000000u);  // a second owner: interior edge
@@ -341,7 +380,15 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
       const int s = tid * PER + i;
       if (s < nslots && isfirst.get(i)) {
         int a, c;
-        const uint32_t h = probe(slot_key(s, a, c));
+        uint32_t h;
+        if (edge_pos) {                                    // (the key at the slot's position holds the edge's two vertices)
+          h = eid_slot[s];
+          const uint32_t key = hkey[h];
+          a = (int)(key >> CP::VBITS);
+          c = (int)(key & ((1u << CP::VBITS) - 1u));
+        } else {
+          h = probe(slot_key(s, a, c));
+        }
         const int e = scanb[s];
         const bool shared = (hval[h] & 0x80000000u) != 0;
         ea[e] = (uint16_t)a;
@@ -353,7 +400,7 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
     __syncthreads();
     for (int s = tid; s < nslots; s += TW) {
       int a, c;
-      const uint32_t h = probe(slot_key(s, a, c));
+      const uint32_t h = edge_pos ? (uint32_t)eid_slot[s] : probe(slot_key(s, a, c));
       const int e = scanb[hval[h] & 0x7FFFFFFFu];
       eid_slot[s] = (uint16_t)e;
       const int t = s / 3, k = s - 3 * t;
@@ -432,13 +479,34 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
   const double bot = dist[0], top = dist[TW];
   __syncthreads();
   // airfoil facets in edge order
+  Flags<PER> flg;
+  int naf;
+  if (narrow) {
+    // (flags of the thread's consecutive edges in registers, the thread totals scanned: see scan_threads)
+    const int per = (ne + TW - 1) / TW;
+    uint32_t bits = 0u;
+    for (int i = 0; i < per; ++i) {
+      const int e = tid * per + i;
+      bits |= (e < ne && (eflag[e] >> 4) == 2) ? 1u << i : 0u;
+    }
+    int q = scan_threads(__popc(bits), part, naf);
+    if (naf > D.NAF) {
+      if (tid == 0) status[b] = -2;
+      return;
+    }
+    int32_t* af = D.af_facets + Bq * D.NAF * 2;
+    for (; bits != 0u; bits &= bits - 1u, ++q) {
+      const int e = tid * per + __ffs((int)bits) - 1;
+      af[2 * q] = eown[e] / 3;
+      af[2 * q + 1] = eown[e] % 3;
+    }
+  } else {
   for (int e = tid; e < TNS; e += TW) scanb[e] = (e < ne && (eflag[e] >> 4) == 2) ? 1 : 0;
   __syncthreads();
-  Flags<PER> flg;
 #pragma unroll
   for (int i = 0; i < PER; ++i) flg.set(i, scanb[tid * PER + i] != 0);
   __syncthreads();
-  const int naf = scan_excl(scanb, TNS, part);
+  naf = scan_excl(scanb, TNS, part);
   if (naf > D.NAF) {
     if (tid == 0) status[b] = -2;
     return;
@@ -455,21 +523,29 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
       }
     }
   }
+  }
   if (tid == 0) D.naf[b] = naf;
   __syncthreads();
   TT_STAMP(2)
   if (!(has_ipcs && O.flow_only)) {   // (an engine that only feeds the IPCS step skips the selection and the state graph)
   // ================= removable: neither x nor y equals ANY boundary vertex's x / y (numpy `in` quirk)
+  int nb;
+  if (narrow) {                                              // (one vertex per thread)
+    const bool f = tid < nv && onb[tid];
+    const int q = scan_threads(f ? 1 : 0, part, nb);
+    if (f) blist[q] = (uint16_t)tid;
+  } else {
   for (int v = tid; v < TNS; v += TW) scanb[v] = (v < nv && onb[v]) ? 1 : 0;
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < PER; ++i) flg.set(i, scanb[tid * PER + i] != 0);
   __syncthreads();
-  const int nb = scan_excl(scanb, TNS, part);
+  nb = scan_excl(scanb, TNS, part);
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int v = tid * PER + i;
     if (v < nv && flg.get(i)) blist[scanb[v]] = (uint16_t)v;
+  }
   }
   __syncthreads();
   // Two hash SETS of the boundary vertices' x and y values (bit patterns; x + 0.0 folds -0 into +0, the one pair of
@@ -520,7 +596,7 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
   if (packed && !hashed)
     for (int j = tid; j < nb; j += TW) bxy[j] = X[blist[j]];
   __syncthreads();
-  for (int v = tid; v < TNS; v += TW) {
+  auto is_removable = [&](int v) {
     int r = 0;
     if (v < nv) {
       const double px = X[v].x, py = X[v].y;
@@ -541,17 +617,25 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
       }
       r = hit ? 0 : 1;
     }
-    scanb[v] = r;
-  }
+    return r;
+  };
+  int nrem;
+  if (narrow) {
+    const int f = is_removable(tid);
+    const int q = scan_threads(f, part, nrem);
+    if (f) remv[q] = (uint16_t)tid;
+  } else {
+  for (int v = tid; v < TNS; v += TW) scanb[v] = is_removable(v);
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < PER; ++i) flg.set(i, scanb[tid * PER + i] != 0);
   __syncthreads();
-  const int nrem = scan_excl(scanb, TNS, part);
+  nrem = scan_excl(scanb, TNS, part);
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int v = tid * PER + i;
     if (v < nv && flg.get(i)) remv[scanb[v]] = (uint16_t)v;
+  }
   }
   if (tid == 0) D.nremovable[b] = nrem;
   TT_STAMP(3)
@@ -1007,6 +1091,17 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
   __syncthreads();
   TT_STAMP(4)
   // ================= state graph: cells whose three vertices are all selected, in cell order
+  int ngood, gper = PER, gat = 0;
+  if (narrow) {                                              // (the thread's consecutive cells, two at the most)
+    gper = (nt + TW - 1) / TW;
+    uint32_t bits = 0u;
+    for (int i = 0; i < gper; ++i) {
+      const int t = tid * gper + i;
+      if (t < nt) bits |= (inv[tri[3 * t]] >= 0 && inv[tri[3 * t + 1]] >= 0 && inv[tri[3 * t + 2]] >= 0) ? 1u << i : 0u;
+    }
+    flg.w[0] = bits;
+    gat = scan_threads(__popc(bits), part, ngood);
+  } else {
   for (int t = tid; t < TNS; t += TW) {
     int f = 0;
     if (t < nt) f = (inv[tri[3 * t]] >= 0 && inv[tri[3 * t + 1]] >= 0 && inv[tri[3 * t + 2]] >= 0) ? 1 : 0;
@@ -1016,7 +1111,8 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
 #pragma unroll
   for (int i = 0; i < PER; ++i) flg.set(i, scanb[tid * PER + i] != 0);
   __syncthreads();
-  const int ngood = scan_excl(scanb, TNS, part);
+  ngood = scan_excl(scanb, TNS, part);
+  }
   if (3 * ngood > D.EMAX) {
     if (tid == 0) status[b] = -3;
     return;
@@ -1027,12 +1123,12 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
     double* el = D.edge_len + Bq * D.EMAX;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-      const int t = tid * PER + i;
-      if (t < nt && flg.get(i)) {
+      const int t = tid * gper + i;
+      if (i < gper && t < nt && flg.get(i)) {
         const int v0 = tri[3 * t], v1 = tri[3 * t + 1], v2 = tri[3 * t + 2];
         const int vs[3] = {v0, v1, v2}, id[3] = {inv[v0], inv[v1], inv[v2]};
         const int pa[3] = {0, 0, 1}, pb[3] = {1, 2, 2};
-        const int base = 3 * scanb[t];
+        const int base = 3 * (narrow ? gat++ : scanb[t]);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           es[base + q] = id[pa[q]];
@@ -1085,12 +1181,24 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
   }
   TT_STAMP(7)
   // outflow facets: pressure Dirichlet vertices, cell -> local facet, entries (row, col, src) of the facet term
+  int nof, oper = PER, oat = 0;
+  if (narrow) {
+    oper = (ne + TW - 1) / TW;
+    uint32_t bits = 0u;
+    for (int i = 0; i < oper; ++i) {
+      const int e = tid * oper + i;
+      bits |= (e < ne && (eflag[e] >> 4) == 4) ? 1u << i : 0u;
+    }
+    flg.w[0] = bits;
+    oat = scan_threads(__popc(bits), part, nof);
+  } else {
   for (int e = tid; e < TNS; e += TW) scanb[e] = (e < ne && (eflag[e] >> 4) == 4) ? 1 : 0;
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < PER; ++i) flg.set(i, scanb[tid * PER + i] != 0);
   __syncthreads();
-  const int nof = scan_excl(scanb, TNS, part);
+  nof = scan_excl(scanb, TNS, part);
+  }
   const int nent = 18 * nof;
   if (nent > O.NBE || nent > 2 * TNV) {
     if (tid == 0) status[b] = -5;
@@ -1112,12 +1220,12 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
   int* ofe = reinterpret_cast<int*>(R + ROFE);               // [nof] outflow edges in edge order
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
-    const int e = tid * PER + i;
-    if (e < ne && flg.get(i)) {
+    const int e = tid * oper + i;
+    if (i < oper && e < ne && flg.get(i)) {
       pf[ea[e]] = 1;
       pf[eb[e]] = 1;
       cof[eown[e] / 3] = (int8_t)(eown[e] % 3);
-      ofe[scanb[e]] = e;
+      ofe[narrow ? oat++ : scanb[e]] = e;
     }
   }
   __syncthreads();
@@ -1162,12 +1270,26 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
     }
     __syncthreads();
     TT_STAMP(15)
+    int nbo;
+    if (narrow) {                                            // (nent <= 1024: one sorted entry per thread)
+      const bool f = tid < nent && (tid == 0 || cntd[tid] != cntd[tid - 1]);
+      const int q = scan_threads(f ? 1 : 0, part, nbo);
+      if (nbo > O.NBO) {
+        if (tid == 0) status[b] = -5;
+        return;
+      }
+      if (f) {
+        bo_rows[q] = cntd[tid];
+        lrow[q] = cntd[tid];
+        bo_ptr[q] = tid;
+      }
+    } else {
     for (int t = tid; t < TNS; t += TW) scanb[t] = (t < nent && (t == 0 || cntd[t] != cntd[t - 1])) ? 1 : 0;
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < PER; ++i) flg.set(i, scanb[tid * PER + i] != 0);
     __syncthreads();
-    const int nbo = scan_excl(scanb, TNS, part);
+    nbo = scan_excl(scanb, TNS, part);
     if (nbo > O.NBO) {
       if (tid == 0) status[b] = -5;
       return;
@@ -1180,6 +1302,7 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
         lrow[scanb[t]] = cntd[t];
         bo_ptr[scanb[t]] = t;
       }
+    }
     }
     if (tid == 0) {
       bo_ptr[nbo] = nent;
@@ -1303,6 +1426,27 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
   uint16_t* adjl = reinterpret_cast<uint16_t*>(R);           // [2 ne] <= 2 TNE entries (blist .. poly are dead)
   int* rptr = cntd;                                          // [nv + 1] row pointers of adjl (cntd is dead)
   int* rcur = cntd + TNV + 8;                                // [nv] fill cursors
+  if (narrow) {
+    // (one vertex per thread: the degrees are counted in scanb[0 .. nv) alone and scanned as thread values - no zero-fill of
+    //  the other 5 000 entries, no scan over them)
+    if (tid < nv) scanb[tid] = 0;
+    __syncthreads();
+    for (int e = tid; e < ne; e += TW) {
+      atomicAdd(&scanb[ea[e]], 1);
+      atomicAdd(&scanb[eb[e]], 1);
+    }
+    __syncthreads();
+    const int dg = tid < nv ? scanb[tid] : 0;
+    int tot;
+    const int q = scan_threads(dg, part, tot);
+    if (tid < nv) {
+      fill[tid] = dg + 1;   // row lengths (the diagonal + the incident edges)
+      rcur[tid] = 0;
+      rptr[tid] = q;
+    }
+    if (tid == 0) rptr[nv] = 2 * ne;
+    __syncthreads();
+  } else {
   for (int i = tid; i < TNS; i += TW) scanb[i] = 0;
   __syncthreads();
   for (int e = tid; e < ne; e += TW) {
@@ -1318,6 +1462,7 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
   scan_excl(scanb, TNS, part);
   for (int i = tid; i <= nv; i += TW) rptr[i] = i < nv ? scanb[i] : 2 * ne;
   __syncthreads();
+  }
   for (int e = tid; e < ne; e += TW) {
     const int a_ = ea[e], b_ = eb[e];
     adjl[rptr[a_] + atomicAdd(&rcur[a_], 1)] = (uint16_t)b_;
@@ -1330,8 +1475,10 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
     const int ns = (nv + 63) / 64;
     // slice widths -> offsets (one wave per slice: the longest of its 64 rows by a shuffle reduction; as one THREAD per
     // slice walking 64 rows the 14 slices of a mesh cost 64 dependent LDS reads each)
-    for (int s_ = tid; s_ < TNS; s_ += TW) scanb[s_] = 0;
-    __syncthreads();
+    if (!narrow) {
+      for (int s_ = tid; s_ < TNS; s_ += TW) scanb[s_] = 0;
+      __syncthreads();
+    }
     for (int s_ = tid >> 6; s_ < ns; s_ += TW / 64) {
       const int r = 64 * s_ + (tid & 63);
       int w = r < nv ? fill[r] : 0;
@@ -1340,7 +1487,25 @@ __global__ __launch_bounds__(TW) void topology_kernel(mdq_env_topo_desc D, mdq_i
       if ((tid & 63) == 0) scanb[s_] = 64 * w;
     }
     __syncthreads();
-    const int total = scan_excl(scanb, TNS, part);
+    int total;
+    if (narrow) {
+      // at most 16 slices: scanned by the first wave in registers (read, shuffles, write: in order within a wave); entry ns
+      // takes the total
+      if (tid < 64) {
+        const int w = tid < ns ? scanb[tid] : 0;
+        int v = w;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const int u = __shfl_up(v, o, 64);
+          if (tid >= o) v += u;
+        }
+        if (tid <= ns) scanb[tid] = v - w;
+      }
+      __syncthreads();
+      total = scanb[ns];
+    } else {
+      total = scan_excl(scanb, TNS, part);
+    }
     if (total > O.NSE1) {
       if (tid == 0) status[b] = -6;
       return;
@@ -1409,10 +1574,11 @@ extern "C" int mdq_env_topology(const mdq_env_topo_desc* d, void* stream, int32_
   }
   // (MDQ_TOPO_INDEX_PARENT, a bit mask read once per process: 1 - the dof <- slot gather lists of the IPCS index section all
   //  through count / fill / sort, 2 - the SELL rows of the P1 Laplacian ranked by loops of LDS reads; the A / B switches of
-  //  the two sections and the references of their test.  Every table is the same either way.)
+  //  the two sections and the references of their test; 4 - the edge hash probed again by every pass over the slots, 8 - every
+  //  compaction as a scan over all 6 144 entries of `scanb`: 15 is the general code everywhere.  Every table is the same either way.)
   static const int idx_parent = [] {
     const char* e = std::getenv("MDQ_TOPO_INDEX_PARENT");
-    return e ? std::atoi(e) & 3 : 0;
+    return e ? std::atoi(e) & 15 : 0;
   }();
   mdq_ipcs_topo_out o = {};
   if (d->ipcs) o = *d->ipcs;
