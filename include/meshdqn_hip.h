@@ -84,7 +84,12 @@ typedef struct mdq_ipcs_desc {
                            meshes beyond the LDS-resident vectors of 2 / 3 when mf_scat / mf_tptr are given; bitwise reproducible),
                            7 the element tiles of 5 with TWO workgroups per environment (chunks dealt out alternately, one
                            accumulation vector per workgroup; bitwise reproducible run to run, a row's sum associated
-                           differently from 5; what auto takes instead of 5 while 2 B <= CUs).  6 is not a mode. */
+                           differently from 5; what auto takes instead of 5 while 2 B <= CUs).  6 is not a mode.
+                           Size limits (160 KB of LDS): 1 up to N2 = 5104, 2 up to 3584, 3 up to 3402 (three vectors).  A mode
+                           is chosen (auto) or accepted (explicit) only when the descriptor carries the arrays its kernels
+                           read - 0 / 1 / 4: A1, Ms, sl2_off, sl2_col; 2: mf_scat + mf_tptr; 3: mf_scat; 5 / 7: cell_outflow
+                           with mf_scat + mf_tptr or g2_ptr + g2_src - and every refusal comes before the first launch: a
+                           matrix-free descriptor (no assembled operators) beyond mode 3 runs the element tiles. */
   /* per-environment counts, device int32[B] */
   const int32_t* nv;
   const int32_t* nt;

@@ -2261,7 +2261,12 @@ __device__ __forceinline__ void team_sync(Team& t) {
   }
   __syncthreads();
   if (t.local)
-    asm volatile("buffer_inv sc0" ::: "memory");            // every wave: no stale lines of the partner's data in this CU's L1
+    // every wave: no stale lines of the partner's data in this CU's L1.  Device scope (sc1): the partner is ANOTHER workgroup on
+    // another CU, and the workgroup-scope form (sc0) left this CU's lines in place - a mesh small enough for its vectors and the
+    // reduction slots to stay in the L1 between two barriers (under ~500 rows: tests/test_ipcs_ladder_gpu.py, mode 7) then read
+    // the values of the application before; larger meshes only evicted them in time.  Memory local to the device is never
+    // stale in the XCD's L2, so nothing there is dropped: the L2 keeps what an environment re-reads.
+    asm volatile("buffer_inv sc1" ::: "memory");
   else
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }

@@ -38,6 +38,14 @@ static int ensure_tables() {
   return 0;
 }
 
+// the largest N2 whose vectors fit the LDS of mode 3 (p, r, result) / mode 1 (p, r) behind the reduction scratch - what the
+// error texts state; ipcs_batch.operator_mode_limits mirrors these and lds_plan
+static int mode3_max_rows() {
+  const int lds = (int)((160 * 1024 - 64 * sizeof(double)) / (3 * sizeof(double2))) & ~1;
+  return lds < MF_ROWS * WG ? lds : MF_ROWS * WG;
+}
+static int mode1_max_rows() { return (int)((160 * 1024 - 64 * sizeof(double)) / (2 * sizeof(double2))) & ~1; }
+
 static int check_desc(const mdq_ipcs_desc* d) {
   if (!d) return fail_msg("null descriptor");
   if (d->B <= 0 || d->NV <= 0 || d->NT <= 0 || d->NE <= 0) return fail_msg("bad batch sizes");
@@ -214,15 +222,27 @@ static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
   // mode 5: the element tile (+ the stage of a chunk's input rows behind it when the packed local maps are given and fit)
   const size_t tile_bytes = tile_lds_bytes(*d);
   if (mode == 6) return fail_msg("unknown operator mode 6");
+  // what the descriptor carries: a mode is chosen (auto) or accepted (explicit) only with the arrays its kernels read - a
+  // matrix-free descriptor (flow leg, device-built index data) has no assembled operators and no tile pointers
+  const bool has_asm = d->A1 && d->Ms && d->sl2_off && d->sl2_col;                      // modes 0 / 1 / 4
+  const bool has_mf = d->mf_scat && d->mf_tptr;                                         // mode 2 (packed words + tile pointers)
+  const bool has_tiles = d->cell_outflow && (has_mf || (d->g2_ptr && d->g2_src));       // modes 5 / 7
+  const bool fits1 = red_bytes + P.vel1_bytes <= LDS_MAX;
+  const bool fits2 = red_bytes + P.vel2_bytes <= LDS_MAX && d->N2 <= MF_ROWS * WG;
+  const bool fits3 = red_bytes + P.vel3_bytes <= LDS_MAX && d->N2 <= MF_ROWS * WG;
   if (mode < 0 || mode > 7) {  // auto: fastest variant that fits
     mode = 0;
-    if (red_bytes + P.vel1_bytes <= LDS_MAX) mode = 1;
-    if (red_bytes + P.vel2_bytes <= LDS_MAX && d->N2 <= MF_ROWS * WG) mode = 2;
+    if (has_asm && fits1) mode = 1;
+    if (has_mf && fits2) mode = 2;
     // (mode -2 = auto among the BITWISE REPRODUCIBLE variants: everything but the LDS-atomic mode 3)
-    if (d->mode != -2 && red_bytes + P.vel3_bytes <= LDS_MAX && d->N2 <= MF_ROWS * WG) mode = 3;
-    // a mesh beyond the LDS-resident vectors: the element tiles with global vectors (mode 5: ~5x less memory traffic than
-    // the assembled operators and no sparsity pattern), when the tile maps were handed over
-    if (mode == 0 && d->cell_outflow && ((d->mf_scat && d->mf_tptr) || (d->g2_ptr && d->g2_src)) && std::getenv("MDQ_NO_MODE5") == nullptr) mode = 5;
+    if (d->mode != -2 && d->mf_scat && fits3) mode = 3;
+    // a mesh beyond the LDS-resident vectors, or a descriptor without the arrays of the modes above: the element tiles with
+    // global vectors (mode 5: ~5x less memory traffic than the assembled operators and no sparsity pattern), when the tile
+    // maps or the slot lists were handed over
+    if (mode == 0 && has_tiles && std::getenv("MDQ_NO_MODE5") == nullptr) mode = 5;
+    if (mode == 0 && !has_asm)
+      return fail_msg("no operator mode fits this descriptor: the assembled operators (A1, Ms, sl2_off, sl2_col) are missing and so "
+                      "are cell_outflow with the tile maps (mf_scat, mf_tptr) or the dof <- slot lists (g2_ptr, g2_src)");
     if (mode == 0) {
       // a mesh that only fits the assembled global-memory path: two workgroups per environment while the batch leaves
       // at least half of the chip idle even so (measured on ys930 red-refined, ms per step one / two workgroups: B = 1
@@ -244,20 +264,28 @@ static int ipcs_evolve_impl(const mdq_ipcs_desc* d, int32_t nsteps, double* drag
     return fail_msg("mdq_ipcs_evolve_profile: operator mode " + std::to_string(mode) + " runs the steps of a call inside one kernel; "
                     "an inflow profile is served by the per-step path (operator modes 2 and 3, or mdq_ipcs_setup_matfree + "
                     "mdq_ipcs_evolve one step at a time)");
+  // every refusal comes before the first launch
+  if (mode == 3 && !fits3)
+    return fail_msg("mode 3 needs N2 <= " + std::to_string(mode3_max_rows()) + " (three velocity vectors of N2 rows in " +
+                    std::to_string(LDS_MAX / 1024) + " KB of LDS, at most " + std::to_string(MF_ROWS * WG) + " rows)");
+  if (mode == 3 && !d->mf_scat) return fail_msg("mode 3 needs the packed element words (mf_scat)");
+  if (mode == 2 && !fits2)
+    return fail_msg("matrix-free tile mode needs N2 <= " + std::to_string(MF_ROWS * WG) + " and the x stage + element tile in LDS");
+  if (mode == 2 && !has_mf) return fail_msg("mode 2 needs the packed element words and the tile pointers (mf_scat, mf_tptr)");
+  if (mode == 1 && !fits1)
+    return fail_msg("LDS gather vectors do not fit (mode 1 needs N2 <= " + std::to_string(mode1_max_rows()) + ")");
+  if ((mode == 0 || mode == 1 || mode == 4) && !has_asm)
+    return fail_msg("modes 0 / 1 / 4 need the assembled operators (A1, Ms, sl2_off, sl2_col): this descriptor is matrix-free only "
+                    "(use mode -1, 5 or 7)");
+  if ((mode == 5 || mode == 7) && !has_tiles)
+    return fail_msg("modes 5 / 7 need cell_outflow and the tile maps (mf_scat, mf_tptr) or the dof <- slot lists (g2_ptr, g2_src)");
+  if (pg && mode != 0 && mode != 5)
+    return fail_msg("mesh too large for the LDS-resident pressure vectors of this operator mode (use mode -1, 0 or 5)");
   // a fresh history: mode 3 drops it inside the kernels of its first step; the one-kernel modes take the reset launch
   if (fresh && mode != 3) {
     hipLaunchKernelGGL(reset_history_kernel, dim3((d->B + 63) / 64), dim3(64), 0, (hipStream_t)stream, *d, iters);
     if (hipError_t e_ = hipGetLastError(); e_ != hipSuccess) return fail("reset_history_kernel launch", e_);
   }
-  if (mode == 3 && (red_bytes + P.vel3_bytes > LDS_MAX || d->N2 > MF_ROWS * WG))
-    return fail_msg("mode 3 needs N2 <= 3584 and three velocity vectors in LDS");
-  if (mode == 2 && (red_bytes + P.vel2_bytes > LDS_MAX || d->N2 > MF_ROWS * WG))
-    return fail_msg("matrix-free tile mode needs N2 <= 3584 and the x stage + element tile in LDS");
-  if (mode == 1 && red_bytes + P.vel1_bytes > LDS_MAX) return fail_msg("LDS gather vectors do not fit");
-  if ((mode == 5 || mode == 7) && (!d->cell_outflow || !((d->mf_scat && d->mf_tptr) || (d->g2_ptr && d->g2_src))))
-    return fail_msg("modes 5 / 7 need cell_outflow and the tile maps (mf_scat, mf_tptr) or the dof <- slot lists (g2_ptr, g2_src)");
-  if (pg && mode != 0 && mode != 5)
-    return fail_msg("mesh too large for the LDS-resident pressure vectors of this operator mode (use mode -1, 0 or 5)");
   // (K1 values alias the scratch vector: CG does not use it; pg: the tables of the two-level preconditioner)
   size_t u = pg ? tl_extra_bytes(d->NV) + sizeof(double) * NAG * NAG : P.prs_vec_bytes + (k1_lds ? P.prs_mat_bytes : 0);
   const size_t vel = mode == 3 ? P.vel3_bytes : (mode == 2 ? P.vel2_bytes : (mode == 1 ? P.vel1_bytes : ((mode == 5 || mode == 7) ? tile_bytes : 0)));

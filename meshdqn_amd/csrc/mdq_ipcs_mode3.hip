@@ -106,55 +106,13 @@ __device__ __forceinline__ void atomic_accumulate(const EnvView& v, double* Yd, 
   }
 }
 
-// Outflow rows owned by this thread (row % WG == tid): at most BO_OWN of them, found once per launch.
-constexpr int BO_OWN = 2;
-struct BoOwn {
-  int t[BO_OWN];
-};
-template <int TW = WG>
-__device__ __forceinline__ BoOwn outflow_rows_owned(const EnvView& v) {
-  BoOwn o;
-#pragma unroll
-  for (int q = 0; q < BO_OWN; ++q) o.t[q] = -1;
-  for (int t = 0; t < v.nbo; ++t) {
-    if ((v.bo_rows[t] % TW) == (int)threadIdx.x) {
-      if (o.t[0] < 0) o.t[0] = t;
-      else o.t[1] = t;  // (a third owned row cannot occur: outflow rows are < 2*WG apart in practice; checked on the host)
-    }
-  }
-  return o;
-}
-
-// Y[row] += coef * sum_entries B x[col] for the outflow rows owned by this thread.
-// Called between the barrier that completes the atomic accumulation and the owner's read of Y;
-// x must not be modified by other threads before the next barrier.
-__device__ __forceinline__ void outflow_rows_add(const EnvView& v, const BoOwn& own, double coef, const double2* x,
-                                                 double2* Y) {
-#pragma unroll
-  for (int q = 0; q < BO_OWN; ++q) {
-    const int t = own.t[q];
-    if (t >= 0) {
-      const int row = v.bo_rows[t];
-      double sx = 0.0, sy = 0.0;
-      for (int k = v.bo_ptr[t]; k < v.bo_ptr[t + 1]; ++k) {
-        const double4 bv = reinterpret_cast<const double4*>(v.bo_val)[k];
-        const double2 xc = x[v.bo_col[k]];
-        sx += bv.x * xc.x + bv.y * xc.y;
-        sy += bv.z * xc.x + bv.w * xc.y;
-      }
-      const double2 y = Y[row];
-      Y[row] = make_double2(y.x + coef * sx, y.y + coef * sy);
-    }
-  }
-}
-
-
-// The same outflow-facet term, one ENTRY per thread (18 entries per outflow facet, a few hundred per mesh): every
+// The outflow-facet term, one ENTRY per thread (18 entries per outflow facet, a few hundred per mesh): every
 // thread adds coef * B_entry x[col] to Y[row] with LDS atomics, between the barrier that publishes the zeroed Y
 // and the element loop, so that the term costs one global-load latency of the waves that own entries instead of a
 // serial per-row chain of them between two barriers.  (row, col) of entry `tid` is found once per launch from the
 // element slot list (bo_src = cell * 36 + i * 6 + j) and kept packed in one register; entries beyond the
-// workgroup size (never on the training meshes) are looked up on the fly.
+// workgroup size (more than 28 / 42 outflow facets; not on the training meshes) are looked up on the fly.  No thread owns
+// outflow rows: any number of them may share a residue modulo the workgroup size.
 struct BoEnt {
   int rc;   // row << 12 | col of entry threadIdx.x, -1 if none
   int nbe;  // entries of this environment

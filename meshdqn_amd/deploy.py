@@ -52,7 +52,7 @@ def resimulate_batch(env, meshes):
     factorisation for solver_type 'lu'), `solver_steps` steps from rest, forces every `save_steps` steps.
     Returns (drags (M, S), lifts (M, S)).  Every mesh is re-simulated under the flow solver's inflow schedule
     (`flow_params['inflow']` as a dict, inflow.py) or its CALLABLE inflow profile - the latter where the batch's operator
-    mode launches per step (modes 2 / 3, `IpcsBatch.mode_serves_profile`: every mesh within 3 584 velocity dofs); in the other
+    mode launches per step (modes 2 / 3, `IpcsBatch.mode_serves_profile`: every mesh within the 3 584 velocity dofs of mode 2); in the other
     modes a callable is not passed on and the batch re-simulates under the constant parabola, as before (`batched=False`
     steps such a profile through the flow solver)."""
     from .ipcs_batch import IpcsBatch

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ipcs_batch import IpcsBatch, pd_device_tables
+from .ipcs_batch import MF_ROWS, MODE3_MAX_N2, WG, IpcsBatch, operator_mode_limits, pd_device_tables
 from .mesh_ops import HostTopologyBatch
 from .streams import role_streams
 
@@ -55,9 +55,11 @@ class FlowLeg:
         d.NSE1, d.NBO, d.NBE = tp.NSE1, tp.NBO, tp.NBE
         d.mu, d.rho, d.dt, d.rtol = solver.mu, solver.rho, solver.dt_value, float(rtol)
         d.maxit_u, d.maxit_p, d.maxit_m = 200, 4000, 200
-        # mode 3 (LDS-resident vectors) on the lab meshes; a mesh beyond its limits (the red-refined ones): auto, i.e. the
-        # element tiles with global vectors (mode 5, here without tile maps: the dof <- slot lists of the topology engine)
-        d.mode, d.pd_enabled = (3 if NP <= 3584 else -1), 0
+        # mode 3 (LDS-resident vectors) on the lab meshes; a capacity beyond its limits (`operator_mode_limits`: 3 402 rows; the
+        # red-refined meshes): auto, which for this descriptor - no assembled operators, no tile pointers - is the element tiles
+        # with global vectors (modes 5 / 7, here through the dof <- slot lists of the topology engine or the maps built below)
+        self.mode3 = bool(operator_mode_limits(NP, NV, tp.NSE1)["mode3"])
+        d.mode, d.pd_enabled = (3 if self.mode3 else -1), 0
         d.pcg_degree = int(pcg_degree)
         for name, _typ in _lib.IpcsDesc._fields_:
             if name in t:
@@ -91,12 +93,13 @@ class FlowLeg:
             for kk, a in self.inlet_map.items():
                 setattr(pr, kk, a.data_ptr())
             pr.values = inflow_profile["values"].data_ptr()
-        # meshes beyond the LDS-resident modes (auto: the element tiles, modes 5 / 7): the tile maps of every coarsened mesh are
+        # meshes beyond the topology engine's small-mesh instance (MF_ROWS * WG = 3 584 rows; auto: the element tiles, modes 5 / 7;
+        # a capacity between mode 3's limit and that one runs them through the slot lists): the tile maps of every coarsened mesh are
         # built on the device in front of the IPCS step (mdq_ipcs_build_tile_maps: row lists + packed local maps) - without
         # them the element results of every operator application go through 0.6 MB of global scratch per environment
         # (MDQ_NO_DEVICE_TILE_MAPS=1: that path, A / B switch)
         self.tile_maps = False
-        if NP > 3584 and not self.host_index and os.environ.get("MDQ_NO_DEVICE_TILE_MAPS", "") != "1":
+        if NP > MF_ROWS * WG and not self.host_index and os.environ.get("MDQ_NO_DEVICE_TILE_MAPS", "") != "1":
             nch = (NT + 1023) // 1024
             nrl = min(self.NRL, NP)
             if (nch + 4) * ((NP + 15) & ~15) + 256 <= 160 * 1024:
@@ -310,11 +313,12 @@ class FlowLeg:
 
 def profile_leg_refusal(NP: int):
     """None when a flow leg on meshes of capacity NP rows can take an inflow profile, else the reason: the profile is
-    rewritten BETWEEN the steps of a launch sequence, which only the leg's mode 3 (NP <= 3584) has - the refined meshes run
-    modes 5 / 7, which loop over the steps inside one kernel."""
-    if int(NP) <= 3584:
+    rewritten BETWEEN the steps of a launch sequence, which only the leg's mode 3 has (`operator_mode_limits`: NP <= 3402,
+    three velocity vectors in LDS; the leg's descriptor has no tile pointers for mode 2) - larger meshes run modes 5 / 7, which
+    loop over the steps inside one kernel."""
+    if operator_mode_limits(int(NP))["mode3"]:
         return None
-    return (f"inflow_profile: a flow leg on meshes of {int(NP)} P2 rows (> 3584) runs the element-tile operator modes 5 / 7, which "
+    return (f"inflow_profile: a flow leg on meshes of {int(NP)} P2 rows (> {MODE3_MAX_N2}) runs the element-tile operator modes 5 / 7, which "
             "loop over the steps inside one kernel; a non-separable inflow on such meshes is served by the per-step path "
             "(FlowSolver.evolve / IpcsBatch.update_inflow, one step per call)")
 

@@ -74,6 +74,48 @@ def flow_table(mu, rho, dt, B: int) -> np.ndarray | None:
     return table if per_env else None
 
 
+# ---- the LDS plan of the IPCS kernels and the entry point's mode conditions, mirrored (csrc/mdq_ipcs.hip `lds_plan`,
+# csrc/mdq_ipcs_entry.hip `ipcs_evolve_impl`): the ONE place the Python side takes the operator modes' size limits from
+LDS_MAX, RED_BYTES = 160 * 1024, 64 * 8     # dynamic LDS of a workgroup; the reduction scratch in front of every layout
+WG, MF_ROWS, MF_CH = 512, 7, 1024           # threads of the one-kernel modes, own rows per thread (modes 2 / 3), triangles per tile
+
+
+def lds_plan(N2: int, NV: int, NSE1: int = 0) -> dict:
+    """`lds_plan` of the kernels: padded lengths and the bytes of every layout behind the reduction scratch."""
+    N2p = (int(N2) + 1) & ~1
+    NVp = (max(int(NV), 1024) + 63) & ~63        # (>= the 1024 threads of the direct pressure kernel)
+    NSE1 = int(NSE1)
+    return dict(N2p=N2p, NVp=NVp, vel1_bytes=2 * 16 * N2p, vel2_bytes=16 * (N2p + 6 * MF_CH), vel3_bytes=3 * 16 * N2p,
+                prs_vec_bytes=5 * 8 * NVp,
+                prs_mat_bytes=8 * max(NSE1, WG) + 4 * (NSE1 + (NSE1 & 1)) + 4 * (((int(NV) // 64 + 2) + 1) & ~1))
+
+
+def operator_mode_limits(N2: int, NV: int = 0, NSE1: int = 0) -> dict:
+    """What the entry point decides from the capacities N2 (P2 rows), NV (vertices) and NSE1 (SELL entries of the P1
+    Laplacian) alone, for a descriptor that carries every array:
+      mode1 / mode2 / mode3   the LDS-resident mode is accepted (vectors in LDS; modes 2 / 3 also N2 <= MF_ROWS * WG = 3 584;
+                              three vectors of mode 3 fit up to N2 = 3 402, the stage + tile of mode 2 up to 3 584, the two
+                              vectors of mode 1 up to 5 104)
+      auto, auto_repro        what modes -1 / -2 choose among them; 0 = beyond them (the element tiles 5 / 7 when the tile maps
+                              or slot lists are given, else the assembled operators 0 / 4)
+      per_step                that choice launches once per step (modes 2 / 3: what an inflow profile needs)
+      pressure_global         the pressure CG vectors do not fit the LDS (modes 0 / 5 only)
+      k1_lds                  the P1 Laplacian fits the LDS beside them (Krylov pressure solve)."""
+    P = lds_plan(N2, NV, NSE1)
+    rows_ok = int(N2) <= MF_ROWS * WG
+    m1 = RED_BYTES + P["vel1_bytes"] <= LDS_MAX
+    m2 = RED_BYTES + P["vel2_bytes"] <= LDS_MAX and rows_ok
+    m3 = RED_BYTES + P["vel3_bytes"] <= LDS_MAX and rows_ok
+    repro = 2 if m2 else (1 if m1 else 0)
+    auto = 3 if m3 else repro
+    pg = RED_BYTES + P["prs_vec_bytes"] > LDS_MAX
+    return dict(mode1=m1, mode2=m2, mode3=m3, auto=auto, auto_repro=repro, per_step=auto in (2, 3), pressure_global=pg,
+                k1_lds=(not pg) and RED_BYTES + P["prs_vec_bytes"] + P["prs_mat_bytes"] <= LDS_MAX, **P)
+
+
+MODE3_MAX_N2 = max(n for n in range(MF_ROWS * WG + 1) if operator_mode_limits(n)["mode3"])      # 3 402
+
+
 class IpcsBatch:
     """Device-resident batch of Taylor-Hood IPCS problems.  `mu`, `rho` and `dt` are scalars (one flow condition for the
     batch) or sequences of length B (one per environment: `self.env_phys`, see `flow_table`).  `inflow`: None (the constant
@@ -103,11 +145,11 @@ class IpcsBatch:
             raise ValueError("inflow_profile cannot be combined with inflow schedules (inflow=): a batch has one kind of "
                              "time-dependent inflow")
         if cell_order == "auto":
-            # the LDS-resident operator modes (every mesh of the batch within 3 584 velocity dofs): the conflict-free order of the
-            # LDS-atomic mode 3; beyond them (element tiles, modes 5 / 7): a spatial order, so that a chunk of 1 024 triangles
-            # shares its rows (2 200 touched rows per chunk on the red-refined ys930 instead of 5 100: the chunk's input rows fit
-            # the kernels' LDS stage, and a row meets 1.06 chunks instead of 2.4)
-            cell_order = "conflictfree" if max(t.np2 for t in self.topos) <= 3584 else "morton"
+            # every mesh of the batch within the LDS-atomic mode 3 (`operator_mode_limits`: 3 402 velocity dofs): its
+            # conflict-free order; beyond it (tiles of 1 024 triangles: mode 2, the element tiles 5 / 7): a spatial order, so that
+            # a chunk of 1 024 triangles shares its rows (2 200 touched rows per chunk on the red-refined ys930 instead of 5 100:
+            # the chunk's input rows fit the kernels' LDS stage, and a row meets 1.06 chunks instead of 2.4)
+            cell_order = "conflictfree" if operator_mode_limits(max(t.np2 for t in self.topos))["mode3"] else "morton"
         if cell_order == "morton":
             cache = {}
             for t in self.topos:
@@ -303,10 +345,6 @@ class IpcsBatch:
         d.NBO, d.NBE = NBO, NBE
         d.mu, d.rho, d.dt, d.rtol = self.mu, self.rho, self.dt, self.rtol
         d.maxit_u, d.maxit_p, d.maxit_m = self.maxit
-        if int(mode) in (-1, 3) and max(p["bo_max_per_thread"] for p in per) > 2:
-            mode = -2 if int(mode) == -1 else mode      # (auto without the LDS-atomic mode 3)
-            if int(mode) == 3:
-                raise ValueError("mode 3 supports at most 2 outflow rows per row-owner thread")
         d.mode = int(mode)
         for name, _typ in _lib.IpcsDesc._fields_:
             if name in t:
@@ -372,7 +410,6 @@ class IpcsBatch:
         bo_col = np.array([e[1] for e in ent], np.int32)
         bo_src = np.array([e[2] for e in ent], np.int32)
         bo_rows = np.array(bo_rows, np.int32)
-        bo_max_per_thread = int(np.bincount(bo_rows % 512, minlength=512).max()) if bo_rows.size else 0
         if topo.np2 <= 4096:
             mf_scat, mf_tptr = topo.matfree_packed(cell_outflow, 1024)
         else:  # matrix-free mode unavailable for this size (kernel falls back to the SELL operators)
@@ -383,7 +420,7 @@ class IpcsBatch:
                     rowptr2=rowptr2, colidx2=colidx2, asm2_ptr=asm2_ptr, asm2_src=asm2_src,
                     rowptr1=rowptr1, colidx1=colidx1, asm1_ptr=asm1_ptr, asm1_src=asm1_src,
                     sl2_off=sl2_off, sl2_col=sl2_col, sl1_off=sl1_off, sl1_col=sl1_col, pos2=pos2, pos1=pos1,
-                    bo_max_per_thread=bo_max_per_thread, mf_scat=mf_scat, mf_tptr=mf_tptr, bo_rows=bo_rows, bo_ptr=bo_ptr, bo_col=bo_col, bo_src=bo_src,
+                    mf_scat=mf_scat, mf_tptr=mf_tptr, bo_rows=bo_rows, bo_ptr=bo_ptr, bo_col=bo_col, bo_src=bo_src,
                     g2_ptr=gat["p2"][0], g2_src=gat["p2"][1], g1_ptr=gat["p1"][0], g1_src=gat["p1"][1],
                     bcu_flag=bc["bcu_flag"], bcu_gx=bc["bcu_gx"], bcp_flag=bc["bcp_flag"],
                     af=af, af_edges=af_edges, tags=bc["tags"])
@@ -525,10 +562,11 @@ class IpcsBatch:
     @classmethod
     def mode_serves_profile(cls, mode: int, n2: int) -> bool:
         """Whether a batch of operator mode `mode` whose largest mesh has `n2` velocity dofs takes an inflow profile: modes
-        2 / 3, asked for or what the auto modes -1 / -2 choose for meshes within the LDS-resident vectors (N2 <= 3584, the
-        choice of `ipcs_evolve_impl`)."""
+        2 / 3, asked for or what the auto modes -1 / -2 choose (`operator_mode_limits`: mode 3 up to 3 402 dofs, mode 2 up to
+        3 584 - the choice of `ipcs_evolve_impl` for a batch that carries the tile pointers, as every IpcsBatch does)."""
         mode = int(mode)
-        return mode in cls.PROFILE_MODES or ((mode < 0 or mode > 7) and int(n2) <= 3584)
+        # (an explicit mode 2 / 3 beyond its own limit is refused by the entry point, with the limit in the message)
+        return mode in cls.PROFILE_MODES or ((mode < 0 or mode > 7) and operator_mode_limits(n2)["per_step"])
 
     def serves_profile(self) -> bool:
         return self.mode_serves_profile(self.desc.mode, self.N2)

@@ -91,9 +91,11 @@ def test_leg_table_refuses_a_profile_that_is_not_finite_or_has_the_wrong_shape(i
 
 def test_profile_leg_predicate_is_the_mode_3_limit():
     from meshdqn_amd.flow_leg import profile_leg_refusal
-    assert profile_leg_refusal(3584) is None and profile_leg_refusal(3322) is None
-    why = profile_leg_refusal(3585)
-    assert why is not None and "per-step path" in why and "3585" in why
+    # mode 3 keeps three velocity vectors in LDS: 3 402 rows, not the 3 584 of its row loops (ipcs_batch.operator_mode_limits)
+    assert profile_leg_refusal(3402) is None and profile_leg_refusal(3322) is None
+    for np_ in (3403, 3584, 3585):
+        why = profile_leg_refusal(np_)
+        assert why is not None and "per-step path" in why and str(np_) in why and "> 3402" in why
 
 
 class _FakeDev:
