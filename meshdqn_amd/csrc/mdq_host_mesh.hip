@@ -381,6 +381,11 @@ static int remesh_one(double* x, int32_t* tri, int32_t* nv, int32_t* nt, int rem
   auto canonical = [&] {
     for (int t = 0; t < m.nt; ++t) std::sort(m.tri + 3 * t, m.tri + 3 * t + 3);
   };
+  // remove_vertex leaves the mesh alone when it fails, make_delaunay cannot: by then the vertex is gone from the caller's
+  // arrays and flips may have been made.  "Mesh untouched" on EVERY failure (as the device kernel, which writes nothing
+  // back before its last phase) needs the oriented mesh from before the removal.
+  const std::vector<double> x0(x, x + 2 * (size_t)m.nv);
+  const std::vector<int32_t> tri0(tri, tri + 3 * (size_t)m.nt);
   int rc = 0;
   if (remove_idx >= 0) {
     rc = remove_vertex(m, remove_idx);
@@ -391,6 +396,10 @@ static int remesh_one(double* x, int32_t* tri, int32_t* nv, int32_t* nt, int rem
   }
   const int flips = make_delaunay(m);
   if (flips < 0) {
+    std::memcpy(x, x0.data(), sizeof(double) * x0.size());
+    std::memcpy(tri, tri0.data(), sizeof(int32_t) * tri0.size());
+    m.nv = *nv;
+    m.nt = *nt;
     canonical();
     return -10 + flips;
   }
