@@ -846,6 +846,30 @@ MDQ_API int mdq_env_result(int32_t B, int32_t N, int32_t S, const double* new_dr
                    double negative_reward, int32_t auto_reset, double* reward, uint8_t* done, int32_t* err_flag,
                    int32_t* nv_out /* optional [B]: copy of nv (the vertex counts of this step) */, void* stream);
 
+/*
+ * mdq_env_result with the LIFT in the reward and in the accuracy stop (appended within ABI 8; not in the reference, whose
+ * calculate_reward fills new_lifts and ignores them), and the reason of the stop.  With gl_s = gt_lift[s], nl_s =
+ * new_lifts[b][s], w = lift_weight, T = lift_threshold, F = lift_floor, all in fp64, in this order, uncontracted:
+ *     el_s        = |gl_s - nl_s| / fmax(|gl_s|, F)            (F: airfoils whose lift passes near zero)
+ *     sl          = sum_s el_s^2 (s ascending),  accl = any_s (el_s > T)
+ *     lift_reward = 2 exp(-(2 ln 2 / T) sqrt(sl)) - 1
+ *     reward (code 0) = (drag_reward + w lift_reward) / (1 + w) + time_reward,    done (code 0) = acc || accl || vert
+ * Everything else - drag_reward, time_reward, acc, vert, codes 1 and 2, the step limit - is mdq_env_result's.  The reward stays in
+ * [-1, 1] + the time term; a NaN lift gives a NaN reward, as a NaN drag does.  new_lifts [B][S] and gt_lift [S] are both set or
+ * both NULL; NULL: the three numbers are not read and every output has the bits of mdq_env_result (which IS this call with
+ * NULL lifts and NULL reason); w = 0, T = +inf with finite lifts gives those bits too.  Refused before the launch: one of the
+ * two arrays alone; with lifts, w negative / not finite, T not > 0 (+inf is allowed), F negative / not finite.
+ * reason [B] (optional, with or without lifts): the bitmask of what ended the step - 1 drag accuracy (acc), 2 lift accuracy
+ * (accl), 4 vertex goal (vert), these three for code 0 only; 8 failed step (code neither 0 nor 1); 16 step limit reached (any
+ * code) - so that done[b] == (reason[b] != 0).
+ */
+MDQ_API int mdq_env_result_forces(int32_t B, int32_t N, int32_t S, const double* new_drags, const double* gt_drag,
+                   const int32_t* nv, int32_t nv0, const int32_t* rstat, const int32_t* topo_status, const int32_t* nsel,
+                   int32_t* code, int32_t* steps, double threshold, double time_reward, double goal_vertices, int32_t timesteps,
+                   double negative_reward, int32_t auto_reset, double* reward, uint8_t* done, int32_t* err_flag, int32_t* nv_out,
+                   const double* new_lifts /* [B][S] */, const double* gt_lift /* [S] */, double lift_weight,
+                   double lift_threshold, double lift_floor, int32_t* reason /* [B] or NULL */, void* stream);
+
 /* mdq_restore_rows for the environments with mask[b] != 0 (device array): the in-place reset without a host-side list. */
 MDQ_API int mdq_restore_rows_masked(int32_t n, void* const* dst, const void* const* src, const int64_t* row_bytes, int32_t B,
                             const uint8_t* mask, void* stream);
@@ -854,8 +878,9 @@ MDQ_API int mdq_restore_rows_masked(int32_t n, void* const* dst, const void* con
  * The END of a device-resident env step in ONE launch (round 4; before: mdq_copy_strided + mdq_env_result +
  * mdq_restore_rows_masked + mdq_state_features, four launches of 5-9 us each on the latency chain of the step), one
  * environment per workgroup row:
- *   1. reward / terminal flag / codes / step counters exactly as mdq_env_result (Env2DAirfoil.py:380-428, :342-377); the step
- *      counters and codes are read from *_in and written to *_out (several workgroups of an environment read them);
+ *   1. reward / terminal flag / codes / step counters exactly as mdq_env_result (Env2DAirfoil.py:380-428, :342-377; with
+ *      new_lifts set: as mdq_env_result_forces); the step counters and codes are read from *_in and written to *_out
+ *      (several workgroups of an environment read them);
  *   2. every row array t < n_rows (dst[t] laid out [B][row_bytes[t]]): the part [handover_off, + handover_bytes) of
  *      environment b's row is first copied to handover_dst[t] ([B][handover_bytes[t]]; NULL: none) - the meshes and warm-start
  *      fields the flow stream's IPCS leg of THIS step works on, taken before a reset rewrites them - and then, where the
@@ -913,6 +938,14 @@ typedef struct {
   const int32_t* src_of_env;
   const int32_t* nv0_of;
   int64_t src_stride[MDQ_FINISH_MAX_ROWS];
+  /* optional (appended within ABI 8), the lift in the reward and in the accuracy stop, exactly as mdq_env_result_forces:
+   * new_lifts [B][S] and gt_lift ([S]; with src_of_env [A][S], the row of the environment's airfoil, like gt_drag) are both
+   * set or both NULL (then the three numbers are not read: a zero-initialised tail is the drag-only step); a stop on the
+   * lift alone resets the environment in place like any other.  reason [B] or NULL: the bitmask of what ended the step. */
+  const double* new_lifts;
+  const double* gt_lift;
+  double lift_weight, lift_threshold, lift_floor;
+  int32_t* reason;
 } mdq_env_finish_desc;
 MDQ_API int mdq_env_finish(const mdq_env_finish_desc* d, void* stream);
 

@@ -3,6 +3,9 @@
 // `v_func.interpolate(original_u)`, `p_func.interpolate(original_p)` and the vertex evaluations).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <string>
+
 #include "../../include/meshdqn_hip.h"
 #include "mdq_internal.h"
 
@@ -500,11 +503,15 @@ __global__ void env_smooth_iters_kernel(int B, const int32_t* rem, const int32_t
 // Codes as in Env2DAirfoil.py:342-364: 0 = removed (reward from calculate_reward), 1 = "already removed" (reward -1, NOT
 // terminal), 2 = broken / out of vertices (reward -1, terminal).  The reference's _remove_vertex / _check_mesh only ever
 // return 0 or 2 (:458,:491,:573,:587,:598,:602) and nothing here produces 1 either; the branch is kept for parity.
+// new_lifts / gt_lift (both or neither; not in the reference, whose calculate_reward fills new_lifts and ignores them): the
+// lift part of the reward and of the accuracy stop, header: mdq_env_result_forces.  NULL: the drag-only step, bit for bit.
 __global__ void env_result_kernel(int B, int N, int S, const double* new_drags, const double* gt_drag, const int32_t* nv,
                                   int32_t nv0, const int32_t* rstat, const int32_t* topo_status, const int32_t* nsel,
                                   int32_t* code, int32_t* steps, double threshold, double time_reward, double goal_vertices,
                                   int32_t timesteps, double negative_reward, int32_t auto_reset, double* reward,
-                                  uint8_t* done, int32_t* err_flag, int32_t* nv_out) {
+                                  uint8_t* done, int32_t* err_flag, int32_t* nv_out, const double* new_lifts,
+                                  const double* gt_lift, double lift_weight, double lift_threshold, double lift_floor,
+                                  int32_t* reason) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
@@ -527,13 +534,29 @@ __global__ void env_result_kernel(int B, int N, int S, const double* new_drags, 
   const double tr = (double)(nv0 - nv[b]) * time_reward;
   const bool vert = (double)nv[b] < goal_vertices * (double)nv0;
   const bool ok = c == 0;
-  double r = ok ? drag_reward + tr : negative_reward;
-  bool dn = ok ? (acc || vert) : (c != 1);
+  double r_ok = drag_reward + tr;
+  bool accl = false;
+  if (new_lifts) {
+    const double lift_factor = -2.0 * log(0.5) / lift_threshold;
+    double sl = 0.0;
+    for (int s = 0; s < S; ++s) {
+      const double g = gt_lift[s], l = new_lifts[(int64_t)b * S + s];
+      const double el = fabs(g - l) / fmax(fabs(g), lift_floor);
+      sl += el * el;
+      accl = accl || el > lift_threshold;
+    }
+    const double lift_reward = 2.0 * exp(-lift_factor * sqrt(sl)) - 1.0;
+    r_ok = (drag_reward + lift_weight * lift_reward) / (1.0 + lift_weight) + tr;
+  }
+  double r = ok ? r_ok : negative_reward;
+  bool dn = ok ? (acc || accl || vert) : (c != 1);
   const int st = steps[b] + 1;
   dn = dn || st >= timesteps;
   reward[b] = r;
   if (nv_out) nv_out[b] = nv[b];      // (the vertex count of the step, before an in-place reset rewrites nv)
   done[b] = dn ? 1 : 0;
+  if (reason)
+    reason[b] = (ok ? (acc ? 1 : 0) | (accl ? 2 : 0) | (vert ? 4 : 0) : (c != 1 ? 8 : 0)) | (st >= timesteps ? 16 : 0);
   code[b] = c;
   steps[b] = (dn && auto_reset) ? 0 : st;
 }
@@ -600,18 +623,44 @@ extern "C" int mdq_env_smooth_iters(int32_t B, const int32_t* rem, const int32_t
   return 0;
 }
 
+// the lift arguments of mdq_env_result_forces / mdq_env_finish_desc: NULL when they are acceptable (both arrays absent, or
+// both present with w >= 0 finite, T > 0 (+inf allowed), F >= 0 finite), else what is wrong with them
+static const char* lift_args_error(const double* new_lifts, const double* gt_lift, double w, double T, double F) {
+  if ((new_lifts == nullptr) != (gt_lift == nullptr)) return "new_lifts and gt_lift go together (both or neither)";
+  if (!new_lifts) return nullptr;
+  if (!(w >= 0.0) || std::isinf(w)) return "lift_weight must be finite and >= 0";
+  if (!(T > 0.0)) return "lift_threshold must be > 0 (+inf: no lift stop)";
+  if (!(F >= 0.0) || std::isinf(F)) return "lift_floor must be finite and >= 0";
+  return nullptr;
+}
+
+extern "C" int mdq_env_result_forces(int32_t B, int32_t N, int32_t S, const double* new_drags, const double* gt_drag,
+                                     const int32_t* nv, int32_t nv0, const int32_t* rstat, const int32_t* topo_status,
+                                     const int32_t* nsel, int32_t* code, int32_t* steps, double threshold, double time_reward,
+                                     double goal_vertices, int32_t timesteps, double negative_reward, int32_t auto_reset,
+                                     double* reward, uint8_t* done, int32_t* err_flag, int32_t* nv_out, const double* new_lifts,
+                                     const double* gt_lift, double lift_weight, double lift_threshold, double lift_floor,
+                                     int32_t* reason, void* stream) {
+  if (B <= 0 || S <= 0 || !new_drags || !gt_drag || !nv || !rstat || !nsel || !code || !steps || !reward || !done || !err_flag)
+    return mdq_set_error("mdq_env_result: bad arguments");
+  if (const char* why = lift_args_error(new_lifts, gt_lift, lift_weight, lift_threshold, lift_floor))
+    return mdq_set_error((std::string("mdq_env_result_forces: ") + why).c_str());
+  hipLaunchKernelGGL(mdq_mesh::env_result_kernel, dim3((B + 127) / 128), dim3(128), 0, (hipStream_t)stream, B, N, S, new_drags,
+                     gt_drag, nv, nv0, rstat, topo_status, nsel, code, steps, threshold, time_reward, goal_vertices, timesteps,
+                     negative_reward, auto_reset, reward, done, err_flag, nv_out, new_lifts, gt_lift, lift_weight, lift_threshold,
+                     lift_floor, reason);
+  if (hipGetLastError() != hipSuccess) return mdq_set_error("env_result_kernel launch failed");
+  return 0;
+}
+
 extern "C" int mdq_env_result(int32_t B, int32_t N, int32_t S, const double* new_drags, const double* gt_drag, const int32_t* nv,
                               int32_t nv0, const int32_t* rstat, const int32_t* topo_status, const int32_t* nsel,
                               int32_t* code, int32_t* steps, double threshold, double time_reward, double goal_vertices,
                               int32_t timesteps, double negative_reward, int32_t auto_reset, double* reward, uint8_t* done,
                               int32_t* err_flag, int32_t* nv_out, void* stream) {
-  if (B <= 0 || S <= 0 || !new_drags || !gt_drag || !nv || !rstat || !nsel || !code || !steps || !reward || !done || !err_flag)
-    return mdq_set_error("mdq_env_result: bad arguments");
-  hipLaunchKernelGGL(mdq_mesh::env_result_kernel, dim3((B + 127) / 128), dim3(128), 0, (hipStream_t)stream, B, N, S, new_drags,
-                     gt_drag, nv, nv0, rstat, topo_status, nsel, code, steps, threshold, time_reward, goal_vertices, timesteps,
-                     negative_reward, auto_reset, reward, done, err_flag, nv_out);
-  if (hipGetLastError() != hipSuccess) return mdq_set_error("env_result_kernel launch failed");
-  return 0;
+  return mdq_env_result_forces(B, N, S, new_drags, gt_drag, nv, nv0, rstat, topo_status, nsel, code, steps, threshold, time_reward,
+                               goal_vertices, timesteps, negative_reward, auto_reset, reward, done, err_flag, nv_out, nullptr,
+                               nullptr, 0.0, 0.0, 0.0, nullptr, stream);
 }
 
 extern "C" int mdq_restore_rows_masked(int32_t n, void* const* dst, const void* const* src, const int64_t* row_bytes,
@@ -674,14 +723,31 @@ __global__ __launch_bounds__(256) void env_finish_kernel(mdq_env_finish_desc d) 
     const double tr = (double)(nv0 - nvb) * d.time_reward;
     const bool vert = (double)nvb < d.goal_vertices * (double)nv0;
     const bool ok = c == 0;
-    const double r = ok ? drag_reward + tr : d.negative_reward;
-    bool dn = ok ? (acc || vert) : (c != 1);
+    double r_ok = drag_reward + tr;
+    bool accl = false;
+    if (d.new_lifts) {       // (workgroup-uniform: a kernel argument)
+      const double* gt_lift = d.gt_lift + (int64_t)a * d.S;
+      const double lift_factor = -2.0 * log(0.5) / d.lift_threshold;
+      double sl = 0.0;
+      for (int s = 0; s < d.S; ++s) {
+        const double g = gt_lift[s], l = d.new_lifts[(int64_t)b * d.S + s];
+        const double el = fabs(g - l) / fmax(fabs(g), d.lift_floor);
+        sl += el * el;
+        accl = accl || el > d.lift_threshold;
+      }
+      const double lift_reward = 2.0 * exp(-lift_factor * sqrt(sl)) - 1.0;
+      r_ok = (drag_reward + d.lift_weight * lift_reward) / (1.0 + d.lift_weight) + tr;
+    }
+    const double r = ok ? r_ok : d.negative_reward;
+    bool dn = ok ? (acc || accl || vert) : (c != 1);
     const int st = d.steps_in[b] + 1;
     dn = dn || st >= d.timesteps;
     if (y == 0) {
       d.reward[b] = r;
       if (d.nv_out) d.nv_out[b] = nvb;
       d.done[b] = dn ? 1 : 0;
+      if (d.reason)
+        d.reason[b] = (ok ? (acc ? 1 : 0) | (accl ? 2 : 0) | (vert ? 4 : 0) : (c != 1 ? 8 : 0)) | (st >= d.timesteps ? 16 : 0);
       d.code_out[b] = c;
       d.steps_out[b] = (dn && d.auto_reset) ? 0 : st;
     }
@@ -794,6 +860,8 @@ extern "C" int mdq_env_finish(const mdq_env_finish_desc* d, void* stream) {
       return mdq_set_error("mdq_env_finish: src_stride must be a non-negative multiple of 4 bytes");
   }
   if (d->src_of_env && !d->nv0_of) return mdq_set_error("mdq_env_finish: src_of_env needs nv0_of");
+  if (const char* why = lift_args_error(d->new_lifts, d->gt_lift, d->lift_weight, d->lift_threshold, d->lift_floor))
+    return mdq_set_error((std::string("mdq_env_finish: ") + why).c_str());
   // workgroups per environment: enough lanes for the hand-over copies AND the in-place reset of a terminated environment
   // (16 bytes per lane and pass, ~4 passes; the workgroups of the other environments find nothing to restore and leave);
   // without cached initial features the reset path needs the whole environment in one workgroup

@@ -21,6 +21,7 @@ import torch
 from .data import Data
 from .flow_solver import FlowSolver, Function, Mesh
 from .mesh_ops import LightMeshBatch, SnapshotInterpolator, polygon_distance, remove_vertex_delaunay
+from . import reward as _reward
 
 device = torch.device("cpu")  # the reference forces the state tensors onto the CPU (Env2DAirfoil.py:39)
 
@@ -54,6 +55,11 @@ class Env2DAirfoil(object):
         self.timesteps = ap["timesteps"]
         self.threshold = ap["threshold"]
         self.NEGATIVE_REWARD = -1.0
+        # opt-in (not in the reference): the lift in the reward and in the accuracy stop (reward.py); `end_reason` is the
+        # bitmask (reward.REASON_*) of what ended the last step, 0 while the episode goes on
+        self.lift = _reward.LiftSpec.from_config(ap)
+        self.end_reason = 0
+        self._mesh_name = str(config["flow_config"]["geometry_params"]["mesh"])
         self.removed_coordinates = []
         self.do_nothing_offset = 0
         self.gt_drag = np.array(ap["gt_drag"])
@@ -121,6 +127,7 @@ class Env2DAirfoil(object):
             topo, topo.coords, torch.stack([u.data for u in self.original_u]),
             torch.stack([p.data for p in self.original_p]), device=self.compute_device)
         self._light = None
+        self.lift.check_gt_lift(self.gt_lift, len(self.gt_drag), names=[self._mesh_name])
         self._calculate_velocities()
         self._calculate_pressures()
         self.steps = 0
@@ -248,6 +255,7 @@ class Env2DAirfoil(object):
         else:
             removed = self._remove_vertex(action)
         state = self.get_state()
+        self.end_reason = 0
         if self.out_of_vertices:
             print("OUT OF VERTICES")
             removed = 2
@@ -258,16 +266,19 @@ class Env2DAirfoil(object):
             if broken:
                 rew = self.NEGATIVE_REWARD
                 self.terminal = True
+                self.end_reason = _reward.REASON_FAILED
         elif removed == 1:
             rew = self.NEGATIVE_REWARD
         else:
             rew = self.NEGATIVE_REWARD
             self.terminal = True
             broken = True
+            self.end_reason = _reward.REASON_FAILED
         self.steps += 1
         if self.steps >= self.timesteps:
             self.terminal = True
             self.episodes += 1
+            self.end_reason |= _reward.REASON_STEP_LIMIT
         if isinstance(rew, float) and np.isnan(rew):
             rew = self.NEGATIVE_REWARD
         return state, rew, self.terminal, {}
@@ -294,15 +305,15 @@ class Env2DAirfoil(object):
         except Exception:
             print("\n\nSAMPLING BROKE\n\n")
             return self.NEGATIVE_REWARD, True, True
-        drag_factor = -2 * np.log(0.5) / self.threshold
-        error_val = np.linalg.norm(np.abs(self.gt_drag - self.new_drags) / np.abs(self.gt_drag))
-        drag_reward = 2 * np.exp(-drag_factor * error_val) - 1
+        value, acc_thresh, lift_thresh = _reward.accuracy_terms(self.lift, self.gt_drag, self.new_drags, self.threshold,
+                                                                self.gt_lift, self.new_lifts)
         time_reward = (self.initial_num_node - len(self.coordinate_list)) * self.TIME_REWARD
-        acc_thresh = any(np.abs(np.abs(self.gt_drag - self.new_drags) / self.gt_drag) > self.threshold)
         vert_thresh = len(self.flow_solver.mesh.coordinates()) < self.goal_vertices * self.initial_num_node
         if vert_thresh:
             print("\nMAXIMUM REMOVALS REACHED\n")
-        return float(drag_reward + time_reward), False, bool(acc_thresh or vert_thresh)
+        self.end_reason = int(bool(acc_thresh) * _reward.REASON_DRAG | bool(lift_thresh) * _reward.REASON_LIFT |
+                              bool(vert_thresh) * _reward.REASON_VERTICES)
+        return float(value + time_reward), False, bool(acc_thresh or lift_thresh or vert_thresh)
 
     def set_plot_dir(self, plot_dir):
         self.plot_dir = plot_dir

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import reward as _reward
 from .env import Env2DAirfoil
 from .flow_leg import FlowLeg, check_flow_forces
 from .inflow import canonical_inlet, inflow_factors, leg_profile_table, spec_table
@@ -188,6 +189,8 @@ class VecEnv2DAirfoil:
         self.goal_vertices = float(ap["goal_vertices"])
         self.timesteps = int(ap["timesteps"])
         self.NEGATIVE_REWARD = -1.0
+        # opt-in (not in the reference): the lift in the reward and in the accuracy stop - batch-wide numbers, like `threshold`
+        self.lift = _reward.LiftSpec.from_config(ap)
         self.S = len(base.original_u)
         if any(len(bb.original_u) != self.S or np.asarray(bb.gt_drag).shape != (self.S,) for bb in bases):
             raise ValueError("snapshots: every airfoil needs the same S = solver_steps // save_steps snapshots and gt_drag values")
@@ -338,6 +341,10 @@ class VecEnv2DAirfoil:
         # in a batch over several airfoils)
         self.initial_num_node = NV if A == 1 else self.nv0s[self.airfoil].astype(np.int64)
         self._gt_drag_env = self.gt_drags[self.airfoil]          # (B, S): the ground truth of every environment's airfoil
+        self._gt_lift_env = self._gt_lift_dev = None
+        if self.lift.on:
+            self.lift.check_gt_lift(self.gt_lift, self.S, names=[bb._mesh_name for bb in bases])
+            self._gt_lift_env = np.asarray(self.gt_lift, dtype=np.float64).reshape(A, self.S)[self.airfoil]
         self.new_drags = np.zeros((B, self.S))
         self.new_lifts = np.zeros((B, self.S))
         self.reset_all()
@@ -704,23 +711,13 @@ class VecEnv2DAirfoil:
             status = self._rstat_host.numpy()
         code[status != 0] = 2
         code[h["nsel"] < N] = 2  # out of vertices
-        rewards = np.zeros(B)
-        dones = np.zeros(B, bool)
-        drag_factor = -2 * np.log(0.5) / self.threshold
-        gt = self._gt_drag_env          # (B, S): every environment's own airfoil
-        err = np.abs(gt - self.new_drags) / np.abs(gt)
-        drag_reward = 2 * np.exp(-drag_factor * np.linalg.norm(err, axis=1)) - 1
-        time_reward = (self.initial_num_node - self.nv) * self.TIME_REWARD
-        acc = (np.abs(np.abs(gt - self.new_drags) / gt) > self.threshold).any(axis=1)
-        vert = self.nv < self.goal_vertices * self.initial_num_node
-        ok = code == 0
-        rewards[ok] = (drag_reward + time_reward)[ok]
-        dones[ok] = (acc | vert)[ok]
-        rewards[~ok] = self.NEGATIVE_REWARD
-        dones[~ok] = code[~ok] != 1        # (code 1 = "already removed": -1, not terminal, Env2DAirfoil.py:359-360; never produced)
         self.steps += 1
-        dones |= self.steps >= self.timesteps
-        infos = dict(code=code, nv=self.nv.copy(), new_drags=self.new_drags.copy(), new_lifts=self.new_lifts.copy())
+        # (B, S) ground truth: every environment's own airfoil; the formula lives in reward.py
+        rewards, dones, reasons = _reward.rewards(self.lift, self._gt_drag_env, self.new_drags, self.nv, self.initial_num_node, code,
+                                                  self.steps, self.threshold, self.TIME_REWARD, self.goal_vertices, self.timesteps,
+                                                  self.NEGATIVE_REWARD, self._gt_lift_env, self.new_lifts)
+        infos = dict(code=code, nv=self.nv.copy(), new_drags=self.new_drags.copy(), new_lifts=self.new_lifts.copy(),
+                     reason=reasons)
         if self.flow_overlap:    # drag / lift of the re-solved flow of the PREVIOUS step's meshes (None at the first step)
             infos.update(flow_lag=1, flow_drag=None if prev_flow is None else prev_flow[0],
                          flow_lift=None if prev_flow is None else prev_flow[1])
@@ -767,7 +764,8 @@ class VecEnv2DAirfoil:
         terminal logic and the in-place resets are all kernels on the current stream (`mdq_env_act`, `mdq_remesh`,
         `mdq_smooth_fast_env`, `mdq_env_topology`, ..., `mdq_env_result`, `mdq_restore_rows_masked`).
         Same semantics as `steps` calls of `step()` (tested against it).  Returns dict(rewards (steps,B), dones,
-        actions, codes, nv) - read back ONCE at the end, when the host mirrors of the environments are refreshed too."""
+        actions, codes, nv, reasons - the bitmask of what ended a step, reward.REASON_*) - read back ONCE at the end, when the
+        host mirrors of the environments are refreshed too."""
         cur = torch.cuda.current_stream(self.device)
         if cur == torch.cuda.default_stream(self.device):
             # not on the legacy default stream: with the main chain there, the factorisation kernel of the flow stream
@@ -874,9 +872,12 @@ class VecEnv2DAirfoil:
                   rem=torch.empty(B, dtype=i32, device=dev), code_act=torch.empty(B, dtype=i32, device=dev),
                   # step counters: read by every workgroup of mdq_env_finish, written to the other array (si: the current one)
                   d_steps=[torch.from_numpy(self.steps.astype(np.int32)).to(dev), torch.empty(B, dtype=i32, device=dev)], si=0,
-                  err=torch.zeros(1, dtype=i32, device=dev))
+                  err=torch.zeros(1, dtype=i32, device=dev), reason=torch.empty((K, B), dtype=i32, device=dev))
         if self._gt_drag_dev is None:       # (A, S): row a = airfoil a
             self._gt_drag_dev = torch.from_numpy(np.ascontiguousarray(self.gt_drags, dtype=np.float64)).to(dev)
+        if self.lift.on and self._gt_lift_dev is None:
+            gl = np.asarray(self.gt_lift, dtype=np.float64).reshape(self.A, self.S)
+            self._gt_lift_dev = torch.from_numpy(np.ascontiguousarray(gl)).to(dev)
         dt.offset.copy_(torch.from_numpy(self.offset))
         ro["state"] = self._state_device()
         return ro
@@ -951,6 +952,9 @@ class VecEnv2DAirfoil:
             d.arrive = self._fin_arrive.data_ptr()
             if self.A > 1:          # per-airfoil ground truth, initial vertex counts, cached rows and features
                 d.src_of_env, d.nv0_of = self._airfoil_dev.data_ptr(), self._nv0_dev.data_ptr()
+            if self.lift.on:        # the lift part of the reward / accuracy stop (off: the tail stays zero, the drag-only step)
+                d.gt_lift = self._gt_lift_dev.data_ptr()
+                d.lift_weight, d.lift_threshold, d.lift_floor = self.lift.weight, self.lift.threshold, self.lift.floor
         c = self._init_cache
         if c.get("x") is None:      # node features of the initial states (what an environment shows right after its reset)
             xi = torch.empty((self.A, N, 2 + 3 * S), dtype=torch.float32, device=self.device)
@@ -978,6 +982,9 @@ class VecEnv2DAirfoil:
             # comes from the cached features (x_init); they stay hand-over sources (the warm start of the flow leg)
             d.src[0] = d.src[1] = None
         d.new_drags = self._dev_drag.data_ptr()
+        if self.lift.on:            # (the array the probe launch of this step wrote beside the drags)
+            d.new_lifts = self._dev_lift.data_ptr()
+        d.reason = ro["reason"][k].data_ptr()
         d.code_in, d.code_out = ro["code_act"].data_ptr(), ro["code"][k].data_ptr()
         d.steps_in, d.steps_out = ro["d_steps"][ro["si"]].data_ptr(), ro["d_steps"][ro["si"] ^ 1].data_ptr()
         d.reward, d.done, d.err_flag, d.nv_out = (ro["rew"][k].data_ptr(), ro["done"][k].data_ptr(), ro["err"].data_ptr(),
@@ -1035,8 +1042,8 @@ class VecEnv2DAirfoil:
         pin["coords"].copy_(dt.coords, non_blocking=True)
         pin["cells"].copy_(dt.cells, non_blocking=True)
         parts = [("rewards", ro["rew"][:K]), ("dones", ro["done"][:K]), ("actions", ro["act"][:K]), ("codes", ro["code"][:K]),
-                 ("nv_steps", ro["nv"][:K]), ("err", ro["err"]), ("nv", dt.nv), ("nt", dt.nt), ("offset", dt.offset),
-                 ("steps", ro["d_steps"][ro["si"]]), ("drag", self._dev_drag), ("lift", self._dev_lift)]
+                 ("nv_steps", ro["nv"][:K]), ("reasons", ro["reason"][:K]), ("err", ro["err"]), ("nv", dt.nv), ("nt", dt.nt),
+                 ("offset", dt.offset), ("steps", ro["d_steps"][ro["si"]]), ("drag", self._dev_drag), ("lift", self._dev_lift)]
         parts += [(k, dt.t[k]) for k in ("nsel", "nedges", "ne", "coord_map", "n_closest")]
         if self.flow_steps > 0:
             parts.append(("flow_status", self.flow_status))        # (legs up to the previous step: the last one may still run)
@@ -1057,7 +1064,7 @@ class VecEnv2DAirfoil:
             got[name] = buf[off:off + f.numel()].view(np_dt).reshape(tuple(t.shape)).copy()
             off += f.numel() + p_
         out = dict(rewards=got["rewards"], dones=got["dones"].astype(bool), actions=got["actions"], codes=got["codes"],
-                   nv=got["nv_steps"])
+                   nv=got["nv_steps"], reasons=got["reasons"])
         if int(got["err"][0]) != 0:
             raise _lib.MeshDQNHipError("topology kernel failed inside rollout_device")
         if K:               # a failed flow leg is an ERROR here, not a NaN in what the caller reads later

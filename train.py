@@ -86,7 +86,24 @@ def parser():
                     help="n-step returns in the device-resident loop, 1 .. 64 (the n-step transition of every drawn record is "
                          "composed from the record ring inside the sampling launch); also the yaml key replay: {n_step: N}; "
                          "default 1")
+    ap.add_argument("--lift-weight", type=float, default=None, metavar="W",
+                    help="weight of the lift in the reward, (drag_reward + W lift_reward) / (1 + W): the yaml key "
+                         "agent_params.lift_weight (not a reference key: its reward reads the drag only); alone, the lift also "
+                         "stops an episode at the drag's `threshold`")
+    ap.add_argument("--lift-threshold", type=float, default=None, metavar="T",
+                    help="relative lift error that ends an episode (agent_params.lift_threshold); alone, a pure stop criterion "
+                         "(W = 0)")
     return ap
+
+
+def lift_options(args, cfgs):
+    """--lift-weight / --lift-threshold written into agent_params of every config (the flags win over the yaml keys) before
+    the environments are built; meshdqn_amd/reward.py reads and validates them."""
+    for c in cfgs:
+        if args.lift_weight is not None:
+            c["agent_params"]["lift_weight"] = float(args.lift_weight)
+        if args.lift_threshold is not None:
+            c["agent_params"]["lift_threshold"] = float(args.lift_threshold)
 
 
 def main():
@@ -113,6 +130,7 @@ def main():
     import torch
     torch.set_num_threads(1)   # (many-core hosts under a CPU quota: the CPU-side tensor ops are tiny, no intra-op pool)
     cfgs = [yaml.safe_load(open(path)) for path in args.config]
+    lift_options(args, cfgs)
     check_airfoil_configs(cfgs, mixed_flow=args.mixed_flow, mixed_inflow=args.mixed_inflow)     # (before any device work: a typo in a yaml ends the run here)
     cfg = cfgs[0]
     ctx = DistContext()
