@@ -26,18 +26,18 @@ OBJ = os.path.join(ROOT, "build", "obj")
 ARCH = "gfx950"
 
 # translation unit -> (source, extra flags, the .hip files it includes besides itself, transitively: they are part of the
-# object cache's key - tests/test_build_units_cpu.py holds the lists to the #include lines).  mdq_ipcs.hip is compiled in
-# parts (-DMDQ_IPCS_PART=k: each part instantiates the kernels of some operator modes and their launchers; part 0 is the
-# set-up, mode 3 and the entry points) because it alone took a minute as one unit.  Its fragments hold what part 0 alone
-# compiles - the file itself keeps what the parts share and the kernels of parts 1-3 - but every part's source names
-# them, so every part lists them.
-IPCS_FRAGMENTS = ["mdq_ipcs_setup.hip", "mdq_ipcs_pcg_reg.hip", "mdq_ipcs_mode3.hip", "mdq_ipcs_inflow.hip",
-                  "mdq_ipcs_entry.hip"]
+# object cache's key - tests/test_build_units_cpu.py holds the lists to the #include lines).  The IPCS code is four units
+# because it took a minute as one: each instantiates the kernels of some operator modes with their launchers (ipcs0 is the
+# set-up, mode 3 and the entry points; ipcs1 modes 0 / 1; ipcs2 modes 5 / 4 / 7; ipcs3 mode 2).  IPCS_SHARED is the text all
+# four include; a kernel family's fragment is listed by the units that include it, so an edit rebuilds those alone.
+IPCS_SHARED = ["mdq_ipcs_views.hip", "mdq_ipcs_ops.hip", "mdq_ipcs_pressure.hip", "mdq_ipcs_step.hip", "mdq_ipcs_tables.hip",
+               "mdq_ipcs_launch.hip"]
 UNITS = {
-    "ipcs0": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=0"], IPCS_FRAGMENTS),
-    "ipcs1": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=1"], IPCS_FRAGMENTS),
-    "ipcs2": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=2"], IPCS_FRAGMENTS),
-    "ipcs3": ("mdq_ipcs.hip", ["-DMDQ_IPCS_PART=3"], IPCS_FRAGMENTS),
+    "ipcs0": ("mdq_ipcs.hip", [], IPCS_SHARED + ["mdq_ipcs_setup.hip", "mdq_ipcs_pcg_reg.hip", "mdq_ipcs_mode3.hip",
+                                                 "mdq_ipcs_inflow.hip", "mdq_ipcs_entry.hip"]),
+    "ipcs1": ("mdq_tu_ipcs_assembled.hip", [], IPCS_SHARED + ["mdq_ipcs_evolve.hip"]),
+    "ipcs2": ("mdq_tu_ipcs_tiles.hip", [], IPCS_SHARED + ["mdq_ipcs_evolve.hip", "mdq_ipcs_team.hip"]),
+    "ipcs3": ("mdq_tu_ipcs_mf.hip", [], IPCS_SHARED + ["mdq_ipcs_mf.hip"]),
     "pressure_factor": ("mdq_pressure_factor.hip", [], []),
     "tilemaps": ("mdq_tilemaps.hip", [], []),
     "gcn": ("mdq_tu_gcn.hip", [], ["mdq_gcn.hip", "mdq_gcn_train.hip"]),

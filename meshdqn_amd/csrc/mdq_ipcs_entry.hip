@@ -1,9 +1,9 @@
 // IPCS: the last-error state, the descriptor check and the entry points (extern "C" API, ipcs_evolve_impl with the launch
-// sequence of mode 3, mdq_probe_forces).  Included by mdq_ipcs.hip in its entry part only, at its end.
+// sequence of mode 3, mdq_probe_forces).  Included by mdq_ipcs.hip (the entry unit) only, at its end.
 namespace mdq {
 
 #ifdef MDQ_AT_TRACE
-// debug build only: the host halves of the AT / PT / CT stamps (buffers and macros: mdq_ipcs.hip)
+// debug build only: the host halves of the AT / PT / CT stamps (buffers and macros: mdq_ipcs_pressure.hip)
 extern "C" MDQ_API int mdq_at_trace_host(long long* out, int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mdq_at_trace_buf), sizeof(long long) * 16) != hipSuccess) return -1;
   if (reset) { long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(mdq_at_trace_buf), z, sizeof z) != hipSuccess) return -1; }

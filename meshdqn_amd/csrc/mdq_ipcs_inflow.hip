@@ -1,5 +1,5 @@
 // IPCS: non-separable inflow profiles (inflow_lift_kernel, launch_inflow_lift) and the inlet map of a device-built mesh.
-// Included by mdq_ipcs.hip in its entry part only, behind the reference tables.
+// Included by mdq_ipcs.hip (the entry unit) only, behind the reference tables.
 namespace mdq {
 
 // ================================================================== inflow profile (mdq_ipcs_evolve_profile)

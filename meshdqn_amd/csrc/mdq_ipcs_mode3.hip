@@ -1,5 +1,5 @@
 // IPCS: the three-kernel LDS-atomic operator mode (mode 3): at_velocity_kernel, at_pressure_kernel, at_correction_kernel
-// and their helpers.  Included by mdq_ipcs.hip in its entry part only, behind launch_evolve_mf.
+// and their helpers.  Included by mdq_ipcs.hip (the entry unit) only, behind its own two kernels.
 #ifndef MDQ_CORR_MX0_INTERLEAVE
 #define MDQ_CORR_MX0_INTERLEAVE false
 #endif

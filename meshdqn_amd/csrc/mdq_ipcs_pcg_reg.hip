@@ -1,5 +1,5 @@
 // IPCS: the register-resident pressure solvers of mode 3 (cg_pressure_reg, cg_pressure_regm_w, cg_pressure_regm,
-// cg_pressure_cheb, cg_pressure_2l).  Included by mdq_ipcs.hip in its entry part only, behind cg_pressure.
+// cg_pressure_cheb, cg_pressure_2l).  Included by mdq_ipcs.hip (the entry unit) only, behind cg_pressure.
 namespace mdq {
 
 // Jacobi-scaled CG on the SELL-64 P1 Laplacian for the three-kernel mode 3: every thread keeps x, r, q of its own

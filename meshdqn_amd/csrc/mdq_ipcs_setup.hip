@@ -1,5 +1,5 @@
 // IPCS: assembly of the SELL operators (assemble_kernel) and the matrix-free operator set-up (setup_matfree_kernel).
-// Included by mdq_ipcs.hip in its entry part only, behind the per-environment views.
+// Included by mdq_ipcs.hip (the entry unit) only, behind the per-environment views.
 namespace mdq {
 
 // ================================================================== assembly

@@ -6,7 +6,7 @@
 //   per subdomain: dense K_II in LDS -> in-place Gauss-Jordan inverse W_s (SPD: no pivoting), F_s = W_s K_IG,
 //   Schur complement S -= K_GI F_s (global, one subdomain after the other), at the end S -> LDS -> inverse.
 // The outputs are the pd_* arrays of mdq_ipcs_desc in exactly the layout the solve phase (pressure_direct in
-// mdq_ipcs.hip) reads; the matrix is the scaled, boundary-eliminated P1 stiffness in SELL-64 as written by
+// mdq_ipcs_pressure.hip) reads; the matrix is the scaled, boundary-eliminated P1 stiffness in SELL-64 as written by
 // mdq_ipcs_assemble / mdq_ipcs_setup_matfree.  An environment whose mesh exceeds the LDS-sized limits below gets
 // nparts = 0 in its header (the pressure kernel then runs its CG) and a negative status.
 #include <hip/hip_runtime.h>

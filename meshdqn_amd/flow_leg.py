@@ -357,7 +357,7 @@ def check_flow_forces(drag, lift, where, status=None, map_status=None):
     """Raises when the inlet map of a leg under an inflow profile failed (`map_status`, codes MAP_STATUS: that environment ran
     under the wrong inflow) or when a flow leg reported a step it could not take: a set status word (mdq_ipcs_desc.status: the two-workgroup
     operator modes 4 / 7 abandon a step when a team barrier times out - the partner workgroup was not resident because another
-    process or stream held its CU; csrc/mdq_ipcs.hip `team_failed`; u_n / p_n of that environment were not advanced) or
+    process or stream held its CU; csrc/mdq_ipcs_team.hip `team_failed`; u_n / p_n of that environment were not advanced) or
     non-finite drag / lift (the same event seen through the forces, or a solve that diverged)."""
     ms = None if map_status is None else np.asarray(map_status)
     if ms is not None and (ms != 0).any():

@@ -74,7 +74,7 @@ def flow_table(mu, rho, dt, B: int) -> np.ndarray | None:
     return table if per_env else None
 
 
-# ---- the LDS plan of the IPCS kernels and the entry point's mode conditions, mirrored (csrc/mdq_ipcs.hip `lds_plan`,
+# ---- the LDS plan of the IPCS kernels and the entry point's mode conditions, mirrored (csrc/mdq_ipcs_step.hip `lds_plan`,
 # csrc/mdq_ipcs_entry.hip `ipcs_evolve_impl`): the ONE place the Python side takes the operator modes' size limits from
 LDS_MAX, RED_BYTES = 160 * 1024, 64 * 8     # dynamic LDS of a workgroup; the reduction scratch in front of every layout
 WG, MF_ROWS, MF_CH = 512, 7, 1024           # threads of the one-kernel modes, own rows per thread (modes 2 / 3), triangles per tile
@@ -646,7 +646,7 @@ class IpcsBatch:
 
     def check(self):
         """Synchronises and raises if any `evolve` since the last call abandoned a step (status words of the descriptor: the
-        two-workgroup operator modes 4 / 7 give a step up when a team barrier times out - csrc/mdq_ipcs.hip `team_failed`; the
+        two-workgroup operator modes 4 / 7 give a step up when a team barrier times out - csrc/mdq_ipcs_team.hip `team_failed`; the
         forces of that step are NaN and u_n / p_n keep the last completed step).  `evolve` itself never synchronises."""
         st = self.status.cpu().numpy()
         if (st != 0).any():
