@@ -35,8 +35,13 @@
 
 #include "../../include/meshdqn_hip.h"
 #include "mdq_internal.h"
+#include "mdq_smooth_shared.hip"
 
 namespace mdq_smoothing {
+using mdq_smooth_shared::d2;
+using mdq_smooth_shared::u4;
+using mdq_smooth_shared::dpp_f64;
+using mdq_smooth_shared::rsqrt_nr;
 // diagnostics (mdq_smooth_stats): [s] = speculative sweeps s that were abandoned for a careful redo
 __device__ unsigned long long g_abandoned[64];
 
@@ -44,7 +49,6 @@ constexpr int SNV = 1024;      // vertex capacity (record offsets must fit 16 bi
 constexpr int SNT = 2048;      // triangle capacity (cell id must fit 12 bits)
 constexpr int SWG = 256;       // threads per workgroup (setup phase; the sweeps run in wave 0)
 constexpr int GRP = 8;         // lanes per vertex update
-constexpr int PER = SNV / SWG; // entries per thread in the setup scans
 constexpr int REC = 32;        // bytes per vertex record: x, y, y, x
 constexpr int ZREC = SNV * REC;        // all-zero record: the unused lanes of a vertex with fewer than 8 cells, empty pass slots
 constexpr int AREC = (SNV + 1) * REC;  // (0, -1000) and
@@ -72,8 +76,6 @@ static_assert(OFF_ROW % 16 == 0 && OFF_PT % 16 == 0 && OFF_PTR % 16 == 0 && OFF_
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 static_assert(SNV * GRP * 4 <= (SNV + 3) * REC, "scheduler scratch inside the record area");
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) unsigned char lds_u8;
 typedef __attribute__((address_space(3))) int lds_i32;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
@@ -81,69 +83,6 @@ typedef __attribute__((address_space(3))) d2 lds_d2;
 typedef __attribute__((address_space(3))) u4 lds_u4;
 typedef __attribute__((address_space(3))) double lds_f64;
 typedef __attribute__((address_space(3))) uint16_t lds_u16;
-
-template <int CTRL>
-__device__ __forceinline__ double dpp8(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-// all-reduce over groups of 8 consecutive lanes: xor 1, xor 2 (quad_perm), then the other quad (row_half_mirror)
-__device__ __forceinline__ double grp_sum(double v) {
-  v += dpp8<0xB1>(v);
-  v += dpp8<0x4E>(v);
-  v += dpp8<0x141>(v);
-  return v;
-}
-__device__ __forceinline__ double grp_min(double v) {
-  v = fmin(v, dpp8<0xB1>(v));
-  v = fmin(v, dpp8<0x4E>(v));
-  v = fmin(v, dpp8<0x141>(v));
-  return v;
-}
-// 1/sqrt(x) and 1/x to double precision (~1 ulp): hardware estimate + two Newton steps (exact path only)
-__device__ __forceinline__ double rsqrt_nr(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  const double h = 0.5 * x;
-  y = y * (1.5 - h * y * y);
-  y = y * (1.5 - h * y * y);
-  return y;
-}
-__device__ __forceinline__ double rcp_nr(double x) {
-  double y = __builtin_amdgcn_rcp(x);
-  y = y * (2.0 - x * y);
-  y = y * (2.0 - x * y);
-  return y;
-}
-
-// inclusive scan of data[0..SNV) in place (the first SWG threads, PER consecutive entries each; part = SWG ints of
-// scratch).  A larger workgroup reaches the barriers with all its threads (smooth_env)
-__device__ __forceinline__ void scan_inclusive(int* data, int* part) {
-  const int tid = threadIdx.x;
-  const bool act = tid < SWG;
-  int loc[PER], run = 0;
-  if (act) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      run += data[tid * PER + i];
-      loc[i] = run;
-    }
-    part[tid] = run;
-  }
-  __syncthreads();
-  for (int off = 1; off < SWG; off <<= 1) {
-    const int add = (act && tid >= off) ? part[tid - off] : 0;
-    __syncthreads();
-    if (act) part[tid] += add;
-    __syncthreads();
-  }
-  if (act) {
-    const int base = part[tid] - run;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) data[tid * PER + i] = base + loc[i];
-  }
-  __syncthreads();
-}
 
 // exact fp64 update of vertex `v` by the 8 lanes of its group (any degree, limited steps): returns the new value of
 // the lane's component (lane 0: x, lane 1: y) in `pn` and whether the vertex moves at all
@@ -153,25 +92,17 @@ __device__ __forceinline__ bool exact_update(const lds_u8* recb, const lds_i32* 
   const double EPS = 3.0e-16;
   const int q0 = ptr[v], k = ptr[v + 1] - q0;
   const d2 p = *reinterpret_cast<const lds_d2*>(recb + v * REC);
-  double sx = 0.0, sy = 0.0, rm = 1e300;
-  for (int q = l; q < k; q += GRP) {
+  const mdq_smooth_shared::ExactSums g = mdq_smooth_shared::exact_gather(p, k, l, [&](int q, d2& pa, d2& pc) {
     const uint32_t w = inc[q0 + q];
     const int a = w & 0x3FF, c = (w >> 10) & 0x3FF;
-    const d2 pa = *reinterpret_cast<const lds_d2*>(recb + a * REC);
-    const d2 pc = *reinterpret_cast<const lds_d2*>(recb + c * REC);
-    sx += pa.x + pc.x;
-    sy += pa.y + pc.y;
-    const double tx = pc.x - pa.x, ty = pc.y - pa.y;
-    const double cr = ty * (p.x - pa.x) - tx * (p.y - pa.y);
-    rm = fmin(rm, cr * cr * rcp_nr(tx * tx + ty * ty));   // SQUARED distance to the line through the opposite edge
-  }
-  sx = grp_sum(sx);
-  sy = grp_sum(sy);
-  rm = grp_min(rm);
+    pa = *reinterpret_cast<const lds_d2*>(recb + a * REC);
+    pc = *reinterpret_cast<const lds_d2*>(recb + c * REC);
+  });
+  const double sx = g.sx, sy = g.sy, rm = g.rm;
   const double r2k = 1.0 / (2.0 * k);
   const double pc_ = l == 0 ? p.x : p.y;
   const double dc_ = (l == 0 ? sx : sy) * r2k - pc_;    // lane 0: dx, lane 1: dy
-  const double dother = dpp8<0xB1>(dc_);
+  const double dother = dpp_f64<0xB1>(dc_);
   const double q2 = dc_ * dc_ + dother * dother;
   pn = pc_;
   if (!(q2 >= EPS * EPS && q2 > 0.0)) return false;     // |c - p| < DOLFIN_EPS: the vertex stays
@@ -189,7 +120,7 @@ __device__ __forceinline__ bool exact_update(const lds_u8* recb, const lds_i32* 
 // flow around the barriers is uniform - and the threads behind the first SWG do nothing in between (their `tid` is beyond
 // every loop bound and every `tid <` test).  `lds`: LDS_BYTES, 16-byte aligned.
 __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int NV, int NT, double* coords, const int32_t* cells,
-                                           const int32_t* nv_, const int32_t* nt_, const int iters, long long* trace) {
+                                           const int32_t* nv_, const int32_t* nt_, const int iters) {
   unsigned char* recb = lds + OFF_REC;
   unsigned char* rows = lds + OFF_ROW;
   uint16_t* passtab = reinterpret_cast<uint16_t*>(lds + OFF_PT);
@@ -206,13 +137,6 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
   int* part = reinterpret_cast<int*>(lds + OFF_PART);
   const int tid = threadIdx.x < SWG ? (int)threadIdx.x : 1 << 24;
   if (iters <= 0) return;
-#ifdef MDQ_SMOOTH_TRACE
-  int phase_ = 0;   // setup phase stamps of environment 0 in the slots of sweep 63
-#define MDQ_SMOOTH_PHASE() if (trace && b == 0 && tid == 0) trace[2 * (63 * SNV + phase_++)] = clock64();
-#else
-#define MDQ_SMOOTH_PHASE()
-#endif
-  MDQ_SMOOTH_PHASE()
   const int nv = nv_[b], nt = nt_[b];
   double2* x = reinterpret_cast<double2*>(coords) + (int64_t)b * NV;
   const int32_t* tri = cells + (int64_t)b * NT * 3;
@@ -221,8 +145,7 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
   for (int t = tid; t < nt; t += SWG)
     for (int k = 0; k < 3; ++k) atomicAdd(&cnt[tri[3 * t + k]], 1);
   __syncthreads();
-  MDQ_SMOOTH_PHASE()   /* 1: counted */
-  scan_inclusive(cnt, part);
+  mdq_smooth_shared::scan_inclusive<SWG, SNV>(cnt, part);
   for (int v = tid; v < SNV; v += SWG) ptr[v + 1] = cnt[v];
   if (tid == 0) ptr[0] = 0;
   __syncthreads();
@@ -242,7 +165,6 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
     }
   }
   __syncthreads();
-  MDQ_SMOOTH_PHASE()   /* 2: cell lists filled */
   for (int v = tid; v < SNV; v += SWG) cnt[v] = 0;   // now: 1 = a neighbour of the vertex is not seen exactly twice
   __syncthreads();
   // one thread per (vertex, incident cell): rank of the cell among the vertex's cells (ascending cell id: the fixed
@@ -282,8 +204,7 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
     cnt[v] = interior ? 1 : 0;
   }
   __syncthreads();
-  MDQ_SMOOTH_PHASE()   /* 3: sorted, interior test, records */
-  scan_inclusive(cnt, part);
+  mdq_smooth_shared::scan_inclusive<SWG, SNV>(cnt, part);
   const int n_int = cnt[SNV - 1];
   __syncthreads();
   for (int v = tid; v < SNV + 8; v += SWG) {
@@ -295,7 +216,6 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
   if (tid < 32) r2ktab[tid] = tid ? 1.0 / (2.0 * tid) : 0.0;
   if (tid < SNV / 64) rb[tid] = bigdeg[tid] = 0ull;
   __syncthreads();
-  MDQ_SMOOTH_PHASE()   /* 4: interior ranks */
   // metadata rows.  Row n_int is the empty pass slot: vertex and cells on the zero record except lane 0, whose cell
   // is the far-away edge (a finite altitude keeps the slot on the fast path; it stores zeros into the zero record)
   for (int r = tid; r <= n_int; r += SWG) {
@@ -339,7 +259,6 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
     for (int l = 0; l < GRP; l += 4) *reinterpret_cast<u4*>(rows + r * ROW + 4 * l) = u4{w[l], w[l + 1], w[l + 2], w[l + 3]};
     *reinterpret_cast<u4*>(rows + r * ROW + 32) = u4{(uint32_t)__double2loint(r2k), (uint32_t)__double2hiint(r2k), wv, __float_as_uint(thr)};
   }
-  MDQ_SMOOTH_PHASE()   /* 5: rows */
   __syncthreads();
   // passes of one sweep by LIST SCHEDULING (wave 0): a vertex is ready when its lower-numbered interior neighbours are
   // scheduled; every pass takes the (up to) 8 ready vertices with the smallest indices, then releases their
@@ -441,7 +360,6 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
     *reinterpret_cast<d2*>(recb + v * REC + 16) = d2{p.y, p.x};
   }
   __syncthreads();
-  MDQ_SMOOTH_PHASE()   /* 7: pass table */
   // ---------------- the sweeps: wave 0 walks the passes
   if (tid < 64 && npass > 0) {
     const int lane = tid, l = lane & 7;
@@ -470,7 +388,6 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
         : "=&v"(pa), "=&v"(pc), "=&v"(pv), "=&v"(W1), "=&v"(M1), "=&v"(RK2)                                             \
         : "v"((W) & 0xFFFF), "v"((W) >> 16), "v"(vrec | par16), "v"((RKN) + lrow), "v"(RKN), "v"(PT), "n"(OFF_ROW + 32) \
         : "memory");                                                                                                    \
-    MDQ_SMOOTH_STAMP(t_ready)                                                                                           \
     /* component 0 of a lane is the one it keeps (even lanes x, odd lanes y), component 1 the one it hands over */      \
     double S = pa.x + pc.x;                                                                                             \
     const double T = pa.y + pc.y;                                                                                       \
@@ -483,9 +400,9 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
     uint32_t ab = __float_as_uint((float)(cr * cr) * __builtin_amdgcn_rcpf((float)len2));                               \
     /* centroid sums: stage 1 exchanges the other component with the neighbour lane, stages 2 and 3 add like */         \
     /* components (lanes 0..3 of the group end with the totals: lane 0 x, lane 1 y) */                                  \
-    S += dpp8<0xB1>(T);                                                                                                 \
+    S += dpp_f64<0xB1>(T);                                                                                                 \
     asm("s_nop 1\n\tv_min_u32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "+v"(ab));               \
-    S += dpp8<0x4E>(S);                                                                                                 \
+    S += dpp_f64<0x4E>(S);                                                                                                 \
     asm("s_nop 1\n\tv_min_u32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "+v"(ab));               \
     {                                                                                                                   \
       const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(S), 0x104, 0xF, 0x5, true); /* row_shl:4 */          \
@@ -509,7 +426,6 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
     /* the prefetched metadata has long arrived */                                                                      \
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(W1), "+v"(M1), "+v"(RK2)::"memory");                                     \
     if (l < 2) asm volatile("ds_write_b64 %0, %2\n\tds_write_b64 %1, %2" ::"v"(vrec + st1), "v"(vrec + st2), "v"(pn) : "memory"); \
-    MDQ_SMOOTH_TRACE_OUT(vrec)                                                                                          \
   }
 #ifdef MDQ_SMOOTH_DIAGNOSE   /* debug builds: the last undecided update of a speculative sweep in slots 40.. */
 #define MDQ_SMOOTH_DIAG(fast, vrec, q2f, ab, thr)                                                     \
@@ -520,28 +436,16 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
 #else
 #define MDQ_SMOOTH_DIAG(fast, vrec, q2f, ab, thr)
 #endif
-#ifdef MDQ_SMOOTH_TRACE
-#define MDQ_SMOOTH_STAMP(t) const long long t = clock64();
-#define MDQ_SMOOTH_TRACE_OUT(vrec)                                     \
-  if (trace && b == 0 && l == 0 && (vrec) != (uint32_t)ZREC) {         \
-    trace[2 * ((int64_t)sweep * SNV + (vrec) / REC)] = t_ready;        \
-    trace[2 * ((int64_t)sweep * SNV + (vrec) / REC) + 1] = clock64();  \
-  }
-#else
-#define MDQ_SMOOTH_STAMP(t)
-#define MDQ_SMOOTH_TRACE_OUT(vrec)
-#endif
     // ---- speculative walk: the new position is stored BEFORE the step-limit test of the update has been evaluated;
     // the test (same fp32 decision, from the registers the update was computed from) runs behind the position loads of
     // the next pass, i.e. in their LDS latency.  An update that is not clearly a full step (none on the reference
     // meshes) abandons the walk: the records are reloaded and the sweeps run again with the test in front of the store.
 #define MDQ_SMOOTH_SPEC(PA, PC, PV, M, PA1, PC1, PV1, W1, M1, RKIN, RKOUT, PT)                                          \
   {                                                                                                                     \
-    MDQ_SMOOTH_STAMP(t_ready)                                                                                           \
     double S = PA.x + PC.x;                                                                                             \
     const double T = PA.y + PC.y;                                                                                       \
-    S += dpp8<0xB1>(T);                                                                                                 \
-    S += dpp8<0x4E>(S);                                                                                                 \
+    S += dpp_f64<0xB1>(T);                                                                                                 \
+    S += dpp_f64<0x4E>(S);                                                                                                 \
     {                                                                                                                   \
       const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(S), 0x104, 0xF, 0x5, true); /* row_shl:4 */          \
       const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(S), 0x104, 0xF, 0x5, true);                          \
@@ -554,7 +458,6 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
       *reinterpret_cast<lds_f64*>(RW + vrec + st1) = pn;                                                                \
       *reinterpret_cast<lds_f64*>(RW + vrec + st2) = pn;                                                                \
     }                                                                                                                   \
-    MDQ_SMOOTH_TRACE_OUT(vrec)                                                                                          \
     asm volatile("" ::: "memory");                                                                                      \
     /* positions of the next pass, metadata of the one behind it, vertex list of the third */                           \
     PA1 = *reinterpret_cast<const lds_d2*>(R + ((W1) & 0xFFFF));                                                        \
@@ -716,18 +619,13 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
     }
 #undef MDQ_SMOOTH_SPEC
 #undef MDQ_SMOOTH_PASS
-#undef MDQ_SMOOTH_STAMP
-#undef MDQ_SMOOTH_TRACE_OUT
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
   __syncthreads();
-  MDQ_SMOOTH_PHASE()   /* 8: sweeps */
   for (int v = tid; v < nv; v += SWG) {
     const d2 p = *reinterpret_cast<const d2*>(recb + v * REC);
     x[v] = double2{p.x, p.y};
   }
-  MDQ_SMOOTH_PHASE()   /* 9: written back */
-#undef MDQ_SMOOTH_PHASE
 }
 
 // B environments over the workgroups of the grid (mdq_smooth: one workgroup per environment; the hand-back launch of
@@ -735,7 +633,7 @@ __device__ __forceinline__ void smooth_env(unsigned char* lds, const int b, int 
 // workgroup of 141 KB LDS finds a compute unit at once, 128 of them wait for the kernels of other streams to drain)
 __global__ __launch_bounds__(SWG) void smooth_kernel(int B, int NV, int NT, double* coords, const int32_t* cells,
                                                      const int32_t* nv_, const int32_t* nt_, const int32_t* iters_,
-                                                     int cap, long long* trace) {
+                                                     int cap, long long* /* unused: the argument block, and with it the machine code, stays as it was */) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
   if (gridDim.x < (unsigned)B) {
     // the walk-over form: is there anything to do at all?  Every wave looks at all the counts (two loads per lane for 128
@@ -745,25 +643,12 @@ __global__ __launch_bounds__(SWG) void smooth_kernel(int B, int NV, int NT, doub
     if (__builtin_amdgcn_ballot_w64(any) == 0ull) return;
   }
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    smooth_env(lds, b, NV, NT, coords, cells, nv_, nt_, cap > 0 ? min(iters_[b], cap) : iters_[b], trace);   // (cap: only the first sweeps)
+    smooth_env(lds, b, NV, NT, coords, cells, nv_, nt_, cap > 0 ? min(iters_[b], cap) : iters_[b]);   // (cap: only the first sweeps)
     __syncthreads();
   }
 }
 
 }  // namespace mdq_smoothing
-
-#ifdef MDQ_SMOOTH_TRACE
-// debug builds only: [64 sweeps][SNV][2] shader-clock timestamps (ready, done) of every update of environment 0,
-// in page-locked host memory the kernel writes directly
-extern "C" long long* mdq_smooth_trace_host() {
-  static long long* g_trace = nullptr;
-  if (!g_trace) {
-    hipHostMalloc(reinterpret_cast<void**>(&g_trace), sizeof(long long) * 2 * 64 * mdq_smoothing::SNV, hipHostMallocDefault);
-    memset(g_trace, 0, sizeof(long long) * 2 * 64 * mdq_smoothing::SNV);
-  }
-  return g_trace;
-}
-#endif
 
 extern "C" int mdq_smooth_stats(int64_t* out64, int32_t reset) {
   if (out64 && hipMemcpyFromSymbol(out64, HIP_SYMBOL(mdq_smoothing::g_abandoned), 64 * sizeof(int64_t)) != hipSuccess)
@@ -787,12 +672,8 @@ extern "C" int mdq_smooth(int32_t B, int32_t NV, int32_t NT, double* coords, con
   if (B <= 0 || !coords || !cells || !nv || !nt || !iterations) return mdq_set_error("mdq_smooth: bad arguments");
   if (NV > mdq_smoothing::SNV || NT > mdq_smoothing::SNT)     // a mesh beyond the 1024-vertex kernels: level-scheduled kernel
     return smooth_big_launch(B, NV, NT, coords, cells, nv, nt, iterations, nullptr, nullptr, 0, workspace, workspace_bytes, stream);
-  long long* trace = nullptr;
-#ifdef MDQ_SMOOTH_TRACE
-  trace = mdq_smooth_trace_host();
-#endif
   hipLaunchKernelGGL(mdq_smoothing::smooth_kernel, dim3(B), dim3(mdq_smoothing::SWG), 0, (hipStream_t)stream, B, NV, NT, coords,
-                     cells, nv, nt, iterations, 0, trace);
+                     cells, nv, nt, iterations, 0, (long long*)nullptr);
   if (hipGetLastError() != hipSuccess) return mdq_set_error("smooth_kernel launch failed");
   return 0;
 }

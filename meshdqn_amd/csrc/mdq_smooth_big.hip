@@ -15,8 +15,12 @@
 
 #include "../../include/meshdqn_hip.h"
 #include "mdq_internal.h"
+#include "mdq_smooth_shared.hip"
 
 namespace mdq_smooth_big {
+using mdq_smooth_shared::d2;
+using mdq_smooth_shared::dpp_f64;
+using mdq_smooth_shared::rcp_nr;
 constexpr int BNV = 4096, BNT = 8192, BWG = 1024;
 constexpr int MAXK = 16;           // incident cells per vertex in the level-ordered work records (more: the general loop)
 constexpr int MAXLEV = 1024;       // levels whose starts are kept in LDS (more: the general loop)
@@ -33,8 +37,9 @@ struct BCap {
   static constexpr size_t SLAB = TABLES + (KV > 1 ? 16 * (size_t)NV + sizeof(int) * NV + 64 : 0);     // + positions + levels
 };
 static_assert(BCap<1>::SLAB == SLAB_BYTES, "the 4096-vertex instance keeps its slab layout");
-
-typedef double d2 __attribute__((ext_vector_type(2)));
+// bytes from one mesh's slab to the next
+template <int KV>
+__host__ __device__ constexpr size_t slab_stride() { return (BCap<KV>::SLAB + 255) & ~(size_t)255; }
 
 #ifdef MDQ_SB_TRACE
 // debug build only: s_memtime cycles of the sections of a level (wave 0 of mesh 0), summed over the launch
@@ -44,46 +49,13 @@ static __device__ long long mdq_sb_trace_buf[8];
 #define SB_STAMP(k)
 #endif
 
-template <int CTRL>
-__device__ __forceinline__ double dppd(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double grp8_sum(double v) {
-  v += dppd<0xB1>(v);
-  v += dppd<0x4E>(v);
-  v += dppd<0x141>(v);
-  return v;
-}
-__device__ __forceinline__ double grp8_min(double v) {
-  v = fmin(v, dppd<0xB1>(v));
-  v = fmin(v, dppd<0x4E>(v));
-  v = fmin(v, dppd<0x141>(v));
-  return v;
-}
-__device__ __forceinline__ double rsqrt_d(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  const double hx = 0.5 * x;
-  y = y * (1.5 - hx * y * y);
-  y = y * (1.5 - hx * y * y);
-  return y;
-}
-__device__ __forceinline__ double rcp_d(double x) {
-  double y = __builtin_amdgcn_rcp(x);
-  y = y * (2.0 - x * y);
-  y = y * (2.0 - x * y);
-  return y;
-}
-
 // the same update by a group of FOUR lanes from a work record whose entries are already in registers: lane l plays the lanes
 // l and l + 4 of the 8-lane form (entries l, l + 8 and l + 4, l + 12 of the vertex's ascending-cell list), and the two partial
 // sums go through the 8-lane tree - (xor 1, xor 2) inside each virtual quad, then quad 0 + quad 1 - so that every sum is
-// associated exactly as in exact_vertex: identical bits, half the lanes (the level loop is bound by instruction issue: the
+// associated exactly as in exact_gather (mdq_smooth_shared.hip): identical bits, half the lanes (the level loop is bound by instruction issue: the
 // scalar tail - divisions, comparisons - ran in eight lanes per vertex)
 __device__ __forceinline__ d2 exact_vertex_rec(const d2* X, const double* r2k_tab, int v, int k, int l, const uint32_t (&w)[4]) {
 #pragma clang fp contract(off)
-  const double EPS = 3.0e-16;
   // every LDS read of the update is issued up front (the addresses are in registers: one round trip, not a chain of them);
   // entries beyond k read position 0 and contribute +0.0 / no minimum (x + 0.0 == x: the sums keep their bits)
   const d2 p = X[v];
@@ -111,7 +83,7 @@ __device__ __forceinline__ d2 exact_vertex_rec(const d2* X, const double* r2k_ta
     const double tx = pc[e].x - pa[e].x, ty = pc[e].y - pa[e].y;
     const double cr = ty * (p.x - pa[e].x) - tx * (p.y - pa[e].y);
     const double t2 = tx * tx + ty * ty;
-    const double r_ = cr * cr * rcp_d(on ? t2 : 1.0);
+    const double r_ = cr * cr * rcp_nr(on ? t2 : 1.0);
     rm = on ? fmin(rm, r_) : rm;
   };
   entry(0, 0, l < k);                 // virtual lane l:     entry l
@@ -120,53 +92,43 @@ __device__ __forceinline__ d2 exact_vertex_rec(const d2* X, const double* r2k_ta
   if (wide) entry(1, 3, l + 12 < k);  //                     entry l + 12
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    sx[h] += dppd<0xB1>(sx[h]);
-    sx[h] += dppd<0x4E>(sx[h]);
-    sy[h] += dppd<0xB1>(sy[h]);
-    sy[h] += dppd<0x4E>(sy[h]);
+    sx[h] += dpp_f64<0xB1>(sx[h]);
+    sx[h] += dpp_f64<0x4E>(sx[h]);
+    sy[h] += dpp_f64<0xB1>(sy[h]);
+    sy[h] += dpp_f64<0x4E>(sy[h]);
   }
-  rm = fmin(rm, dppd<0xB1>(rm));
-  rm = fmin(rm, dppd<0x4E>(rm));
-  const double sxt = sx[0] + sx[1], syt = sy[0] + sy[1];
-  const double dx = sxt * r2k - p.x, dy = syt * r2k - p.y;
-  const double q2 = dx * dx + dy * dy;
-  if (!(q2 >= EPS * EPS && q2 > 0.0)) return p;
-  if (0.25 * rm < q2) {
-    const double f = 0.5 * (rm * rsqrt_d(rm)) * rsqrt_d(q2);
-    return d2{p.x + f * dx, p.y + f * dy};
-  }
-  return d2{p.x + dx, p.y + dy};
+  rm = fmin(rm, dpp_f64<0xB1>(rm));
+  rm = fmin(rm, dpp_f64<0x4E>(rm));
+  return mdq_smooth_shared::exact_step(p, sx[0] + sx[1], sy[0] + sy[1], rm, r2k);
 }
 
-// DOLFIN's update of vertex v by a group of 8 lanes (lane l of the group takes incident cells l, l + 8, ...): the same
-// arithmetic, in the same order, as exact_vertex of mdq_smooth_linear.hip / exact_update of mdq_smooth.hip
+// DOLFIN's update of vertex v by a group of 8 lanes (lane l of the group takes incident cells l, l + 8, ...): the general
+// loop, for any number of cells at a vertex
 __device__ __forceinline__ d2 exact_vertex(const d2* X, const int* ptr, const uint32_t* inc, int v, int l) {
 #pragma clang fp contract(off)
-  const double EPS = 3.0e-16;
   const int q0 = ptr[v], k = ptr[v + 1] - q0;
   const d2 p = X[v];
-  double sx = 0.0, sy = 0.0, rm = 1e300;
-  for (int q = l; q < k; q += 8) {
+  const mdq_smooth_shared::ExactSums g = mdq_smooth_shared::exact_gather(p, k, l, [&](int q, d2& pa, d2& pc) {
     const uint32_t w = inc[q0 + q];
-    const d2 pa = X[w & 0xFFFF], pc = X[w >> 16];
-    sx += pa.x + pc.x;
-    sy += pa.y + pc.y;
-    const double tx = pc.x - pa.x, ty = pc.y - pa.y;
-    const double cr = ty * (p.x - pa.x) - tx * (p.y - pa.y);
-    rm = fmin(rm, cr * cr * rcp_d(tx * tx + ty * ty));   // SQUARED distance to the line through the opposite edge
+    pa = X[w & 0xFFFF], pc = X[w >> 16];
+  });
+  return mdq_smooth_shared::exact_step(p, g.sx, g.sy, g.rm, 1.0 / (2.0 * k));
+}
+
+// A level-ordered work record as lane l4 of a group of four holds it: meta[i] = v | k << 16 and the entries l4, l4 + 4, l4 + 8,
+// l4 + 12 of inc2[i][MAXK]; all zero behind the end i1 of the level
+struct Rec { uint32_t m, w[4]; };
+__device__ __forceinline__ void fetch_rec(const uint32_t* meta, const uint32_t* inc2, int l4, int i, int i1, Rec& r) {
+  r.m = 0u;
+  r.w[0] = r.w[1] = r.w[2] = r.w[3] = 0u;
+  if (i < i1) {
+    r.m = meta[i];
+    const uint32_t* e = inc2 + i * MAXK + l4;
+    r.w[0] = e[0];
+    r.w[1] = e[4];
+    r.w[2] = e[8];
+    r.w[3] = e[12];
   }
-  sx = grp8_sum(sx);
-  sy = grp8_sum(sy);
-  rm = grp8_min(rm);
-  const double r2k = 1.0 / (2.0 * k);
-  const double dx = sx * r2k - p.x, dy = sy * r2k - p.y;
-  const double q2 = dx * dx + dy * dy;
-  if (!(q2 >= EPS * EPS && q2 > 0.0)) return p;          // |c - p| < DOLFIN_EPS: the vertex stays
-  if (0.25 * rm < q2) {                                  // limited step: needs the lengths
-    const double f = 0.5 * (rm * rsqrt_d(rm)) * rsqrt_d(q2);
-    return d2{p.x + f * dx, p.y + f * dy};
-  }
-  return d2{p.x + dx, p.y + dy};                         // |c - p| <= r_min / 2: to the centroid itself
 }
 
 // The sweeps of the level schedule (shared by the two kernels below): positions X and level starts `lstart` in LDS, the
@@ -179,25 +141,12 @@ __device__ __forceinline__ void level_sweeps(d2* X, const double* r2k_tab, const
     // behind the update + the barrier (they do not depend on the positions)
     constexpr int G = BWG / 4;
     const int g4 = tid >> 2, l4 = tid & 3;
-    struct Rec { uint32_t m, w[4]; };
-    auto fetch = [&](int i, int i1, Rec& r) {
-      r.m = 0u;
-      r.w[0] = r.w[1] = r.w[2] = r.w[3] = 0u;
-      if (i < i1) {
-        r.m = meta[i];
-        const uint32_t* e = inc2 + i * MAXK + l4;
-        r.w[0] = e[0];      // entry l
-        r.w[1] = e[4];      // entry l + 4
-        r.w[2] = e[8];      // entry l + 8
-        r.w[3] = e[12];     // entry l + 12
-      }
-    };
     // two record sets used alternately (a register copy `cur = nxt` would wait for the loads it copies - in front of the
     // barrier, i.e. the L2 round trip back on every level)
     Rec ra, rb;
     int i0 = lstart[1], i1 = lstart[2];                       // this level
     int j0 = lmax > 1 ? lstart[2] : i0, j1 = lmax > 1 ? lstart[3] : i1;   // the next one (level 1 again behind the last)
-    fetch(i0 + g4, i1, ra);
+    fetch_rec(meta, inc2, l4, i0 + g4, i1, ra);
     auto level = [&](int l, Rec& mine, Rec& next) {
       // the level starts two levels ahead are read now and used by the NEXT call's record request: no LDS round trip in
       // front of the global one
@@ -206,19 +155,12 @@ __device__ __forceinline__ void level_sweeps(d2* X, const double* r2k_tab, const
       long long tq_ = __builtin_amdgcn_s_memtime();
 #endif
       const int k0 = lstart[l2], k1 = lstart[l2 + 1];
-#ifndef MDQ_SB_NOFETCH
-      fetch(j0 + g4, j1, next);
-#endif
+      fetch_rec(meta, inc2, l4, j0 + g4, j1, next);
       SB_STAMP(0)
       for (int i = i0 + g4; i < i1; i += G) {
-        if (i != i0 + g4) fetch(i, i1, mine);                 // (further passes of a wide level)
+        if (i != i0 + g4) fetch_rec(meta, inc2, l4, i, i1, mine);                 // (further passes of a wide level)
         const int v = mine.m & 0xFFFF, k = mine.m >> 16;
-#ifdef MDQ_SB_NOCOMP
-        const d2 xn = X[v] + X[mine.w[0] & 0xFFFF] * 1e-300;
-        (void)k;
-#else
         const d2 xn = exact_vertex_rec(X, r2k_tab, v, k, l4, mine.w);
-#endif
         if (l4 == 0) X[v] = xn;
       }
       SB_STAMP(1)
@@ -226,10 +168,8 @@ __device__ __forceinline__ void level_sweeps(d2* X, const double* r2k_tab, const
       SB_STAMP(2)
       // LDS-only barrier: the positions of this level are in LDS (lgkmcnt), the records requested for the next level are
       // still on their way (vmcnt) and stay in flight - __syncthreads() drains the vector-memory counter as well
-#ifndef MDQ_SB_NOBAR
       if (GX) __syncthreads();
       else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
       SB_STAMP(3)
     };
     const int total = S * lmax;
@@ -260,19 +200,6 @@ __device__ __forceinline__ void skew_sweeps(d2* X, const double* r2k_tab, const 
                                             int P, int J, int S, int tid) {
   constexpr int G = BWG / 4;
   const int g4 = tid >> 2, l4 = tid & 3;
-  struct Rec { uint32_t m, w[4]; };
-  auto fetch = [&](int i, int i1, Rec& r) {
-    r.m = 0u;
-    r.w[0] = r.w[1] = r.w[2] = r.w[3] = 0u;
-    if (i < i1) {
-      r.m = meta[i];
-      const uint32_t* e = inc2 + i * MAXK + l4;
-      r.w[0] = e[0];
-      r.w[1] = e[4];
-      r.w[2] = e[8];
-      r.w[3] = e[12];
-    }
-  };
   const int T = (S - 1 + J) * P;                             // time steps
   // the record range of time step (q P + r)
   auto range = [&](int r, int q, int& a, int& b) {
@@ -288,15 +215,15 @@ __device__ __forceinline__ void skew_sweeps(d2* X, const double* r2k_tab, const 
   range(0, 0, i0, i1);
   int r2 = P > 1 ? 1 : 0, q2 = P > 1 ? 0 : 1;                // (residue, sweep block) of the step after the current one ...
   range(r2, q2, j0, j1);
-  fetch(i0 + g4, i1, ra);
+  fetch_rec(meta, inc2, l4, i0 + g4, i1, ra);
   auto step = [&](Rec& mine, Rec& next) {
     // ... and of the one after that: its range is read now and used by the NEXT call's record request
     if (++r2 == P) { r2 = 0; ++q2; }
     int k0, k1;
     range(r2, q2, k0, k1);
-    fetch(j0 + g4, j1, next);
+    fetch_rec(meta, inc2, l4, j0 + g4, j1, next);
     for (int i = i0 + g4; i < i1; i += G) {
-      if (i != i0 + g4) fetch(i, i1, mine);                 // (further passes of a wide step)
+      if (i != i0 + g4) fetch_rec(meta, inc2, l4, i, i1, mine);                 // (further passes of a wide step)
       const int v = mine.m & 0xFFFF, k = mine.m >> 16;
       const d2 xn = exact_vertex_rec(X, r2k_tab, v, k, l4, mine.w);
       if (l4 == 0) X[v] = xn;
@@ -319,7 +246,7 @@ __global__ __launch_bounds__(BWG) void smooth_big_kernel(int NV, int NT, double*
   constexpr int BNV = BCap<KV>::NV, BNT = BCap<KV>::NT;       // (shadow the 4096-vertex constants of the namespace)
   constexpr size_t SLAB_BYTES = BCap<KV>::SLAB;
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_[];
-  unsigned char* xbase = KV == 1 ? dyn_ : slab + (size_t)blockIdx.x * ((SLAB_BYTES + 255) & ~(size_t)255) + ((BCap<KV>::TABLES + 15) & ~(size_t)15);
+  unsigned char* xbase = KV == 1 ? dyn_ : slab + (size_t)blockIdx.x * slab_stride<KV>() + ((BCap<KV>::TABLES + 15) & ~(size_t)15);
   d2* X = reinterpret_cast<d2*>(xbase);                      // [BNV] 64 KB of LDS (KV = 1) / on the slab behind the tables
   int* cnt = reinterpret_cast<int*>(xbase + sizeof(d2) * BNV);  // [BNV] 16 KB: counts / cursors, then levels
   __shared__ int part[BWG];
@@ -327,13 +254,13 @@ __global__ __launch_bounds__(BWG) void smooth_big_kernel(int NV, int NT, double*
   __shared__ double r2k_tab[MAXK + 1];
   __shared__ int lstart[MAXLEV + 2];                          // level starts (a copy of lptr: the sweeps never leave the CU for them)
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int S = iters_ ? iters_[b] : ((rem[b] >= 0 && rstat[b] == 0) ? iters_env : 0);
+  const int S = mdq_smooth_shared::sweeps_of(b, iters_, rem, rstat, iters_env);
   if (status && tid == 0) status[b] = 0;
   if (S <= 0) return;
   const int nv = nv_[b], nt = nt_[b];
   double2* xg = reinterpret_cast<double2*>(coords) + (int64_t)b * NV;
   const int32_t* tri = cells + (int64_t)b * NT * 3;
-  unsigned char* sb = slab + (size_t)b * ((SLAB_BYTES + 255) & ~(size_t)255);
+  unsigned char* sb = slab + (size_t)b * slab_stride<KV>();
   int* ptr = reinterpret_cast<int*>(sb);                                   // [BNV + 1] vertex -> cells
   uint32_t* inc = reinterpret_cast<uint32_t*>(ptr + BNV + 8);              // [3 BNT] a | c << 16, sorted by cell per vertex
   uint32_t* cel = inc + 3 * BNT;                                           // [3 BNT] cell id of the entry
@@ -557,7 +484,7 @@ __global__ __launch_bounds__(FWG) void smooth_flow_kernel(int NV, int NT, double
   __shared__ double r2k_tab[MAXK + 1];
   __shared__ int misc[4];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int S = iters_ ? iters_[b] : ((rem[b] >= 0 && rstat[b] == 0) ? iters_env : 0);
+  const int S = mdq_smooth_shared::sweeps_of(b, iters_, rem, rstat, iters_env);
   // redo[b]: sweeps handed back to the level kernel (launched behind this one; it returns at once for 0) - a mesh with more
   // than MAXK cells at a vertex or a sweep count that does not fit the byte counters
   if (tid == 0) redo[b] = (S >= 255) ? S : 0;
@@ -700,7 +627,7 @@ __global__ __launch_bounds__(FWG) void smooth_flow_kernel(int NV, int NT, double
   // solution of the left inequalities; raising tau(v) to tau(w) - (P - 1) where the right one fails and re-establishing the
   // left ones converges to the least solution above them when one exists - in place: a monotone iteration from below reaches
   // the same fixed point in any order).  P = half the levels (rounded up), then 5/8 and 3/4 of them; no P: tau = level, P =
-  // levels (the plain level schedule).  MDQ_NO_SMOOTH_SKEW (compile time): never.
+  // levels (the plain level schedule).
   int lmax = 0;
   for (int v = tid; v < nv; v += FWG) lmax = max(lmax, done[v] == 0 ? lev[v] : 0);
   part[tid] = lmax;
@@ -712,7 +639,6 @@ __global__ __launch_bounds__(FWG) void smooth_flow_kernel(int NV, int NT, double
   lmax = part[0];
   __syncthreads();
   int P = lmax > 0 ? lmax : 1, J = 1;
-#ifndef MDQ_NO_SMOOTH_SKEW
   if (lmax >= 8 && lmax <= 1000) {
     int* tau = indeg;                                        // (the in-degrees are all zero now)
     const int cand[3] = {(lmax + 1) / 2, (5 * lmax + 7) / 8, (3 * lmax + 3) / 4};
@@ -768,7 +694,6 @@ __global__ __launch_bounds__(FWG) void smooth_flow_kernel(int NV, int NT, double
       __syncthreads();
     }
   }
-#endif
   for (int l_ = tid; l_ < MAXLEV + 2; l_ += FWG) lvl[l_] = 0;
   __syncthreads();
   for (int v = tid; v < nv; v += FWG)
@@ -801,7 +726,7 @@ __global__ __launch_bounds__(FWG) void smooth_flow_kernel(int NV, int NT, double
     return;
   }
   // ---- the level-ordered work records of the sweeps, to the workspace (the sweeps read them one level ahead); level starts
-  uint32_t* meta = reinterpret_cast<uint32_t*>(slab + (size_t)b * ((SLAB_BYTES + 255) & ~(size_t)255));
+  uint32_t* meta = reinterpret_cast<uint32_t*>(slab + (size_t)b * slab_stride<1>());
   uint32_t* inc2 = meta + BNV;
   for (int i = tid; i < n_int; i += FWG) {
     const uint32_t tr = trec[i];
@@ -841,8 +766,8 @@ extern "C" MDQ_API int mdq_sb_trace_host(long long* out, int reset) {
 static int64_t smooth_big_workspace_bytes(int32_t B, int32_t NV, int32_t NT) {
   using namespace mdq_smooth_big;
   if (NV > BCap<4>::NV || NT > BCap<4>::NT) return -1;
-  if (NV > BNV || NT > BNT) return (int64_t)((BCap<4>::SLAB + 255) & ~(size_t)255) * B;                // (no hand-back launch there)
-  return (int64_t)((SLAB_BYTES + 255) & ~(size_t)255) * B + (((int64_t)B * 4 + 255) & ~(int64_t)255);   // tables + the hand-back counts
+  if (NV > BNV || NT > BNT) return (int64_t)slab_stride<4>() * B;                // (no hand-back launch there)
+  return (int64_t)slab_stride<1>() * B + (((int64_t)B * 4 + 255) & ~(int64_t)255);   // tables + the hand-back counts
 }
 
 // mdq_smooth / mdq_smooth_fast / mdq_smooth_fast_env for NV > 1024 (called by those entry points)
@@ -872,7 +797,7 @@ static int smooth_big_launch(int32_t B, int32_t NV, int32_t NT, double* coords, 
     static const hipError_t attr2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&smooth_flow_kernel),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8832);
     if (attr2 != hipSuccess) return mdq_set_error("hipFuncSetAttribute(smooth_flow_kernel) failed");
-    int32_t* redo = reinterpret_cast<int32_t*>(slab + ((SLAB_BYTES + 255) & ~(size_t)255) * (size_t)B);
+    int32_t* redo = reinterpret_cast<int32_t*>(slab + slab_stride<1>() * (size_t)B);
     hipLaunchKernelGGL(smooth_flow_kernel, dim3(B), dim3(FWG), flow_lds, (hipStream_t)stream, NV, NT, coords, cells, nv, nt,
                        iterations, rem, rstat, iters_env, slab, redo);
     hipLaunchKernelGGL(smooth_big_kernel<1>, dim3(B), dim3(BWG), lds, (hipStream_t)stream, NV, NT, coords, cells, nv, nt, redo,

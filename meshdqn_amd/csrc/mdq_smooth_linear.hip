@@ -40,17 +40,16 @@
 
 #include "../../include/meshdqn_hip.h"
 #include "mdq_internal.h"
+#include "mdq_smooth_shared.hip"
 
 namespace mdq_smooth_lin {
+using mdq_smooth_shared::d2;
+using mdq_smooth_shared::u4;
 constexpr int LNV = 1024;          // vertex capacity
 constexpr int LNT = 2048;          // triangle capacity
-#ifndef MDQ_SMOOTH_LWG
-#define MDQ_SMOOTH_LWG 768
-#endif
-constexpr int LWG = MDQ_SMOOTH_LWG;   // threads per workgroup (512 or 768): waves 0 / 1 solve x / y, the waves on the other two SIMDs validate
+constexpr int LWG = 768;          // threads per workgroup: waves 0 / 1 solve x / y, the waves on the other two SIMDs validate
 constexpr int SCT = 512;           // threads that take part in the block scans (two entries each)
 constexpr int TRW = LWG / 64 < 11 ? LWG / 64 : 11;   // waves that build block inverses (their packed triangles share 3 position buffers)
-static_assert(LWG == 512 || LWG == 768, "workgroup shape");
 constexpr int BS = 32;             // rows per block
 constexpr int NSLOT = 14;          // gather slots per row (7 per lane half)
 constexpr int NNARROW = 4;         // slots per lane half a NARROW block step reads: no row of the block has more than 8
@@ -89,22 +88,7 @@ static_assert(LNV / BS <= 32, "one bit per block");
 static_assert(OFF_SROW % 16 == 0 && OFF_PTR % 16 == 0 && OFF_INC % 16 == 0 && OFF_G % 16 == 0 && OFF_R2K % 8 == 0 && OFF_M01 % 16 == 0, "LDS alignment");
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-
-template <int CTRL>
-__device__ __forceinline__ double dppd(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-// sum over groups of 8 consecutive lanes (all lanes get the total): xor 1, xor 2 (quad_perm), other quad (row_half_mirror)
-__device__ __forceinline__ double grp8_sum(double v) {
-  v += dppd<0xB1>(v);
-  v += dppd<0x4E>(v);
-  v += dppd<0x141>(v);
-  return v;
-}
+// minimum over groups of 8 consecutive lanes (all lanes get it): xor 1, xor 2 (quad_perm), other quad (row_half_mirror)
 __device__ __forceinline__ float grp8_min(float v) {
   v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)));
   v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)));
@@ -117,34 +101,6 @@ __device__ __forceinline__ double halves_sum(double v) {
   const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
   const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
   return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-
-__device__ __forceinline__ void scan_inclusive(int* data, int* part) {   // data[0..LNV): the first SCT threads, 2 entries each
-  const int tid = threadIdx.x;
-  constexpr int PER = LNV / SCT;
-  const bool sc = tid < SCT;
-  int loc[PER], run = 0;
-  if (sc) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      run += data[tid * PER + i];
-      loc[i] = run;
-    }
-    part[tid] = run;
-  }
-  __syncthreads();
-  for (int off = 1; off < SCT; off <<= 1) {
-    const int add = (sc && tid >= off) ? part[tid - off] : 0;
-    __syncthreads();
-    if (sc) part[tid] += add;
-    __syncthreads();
-  }
-  if (sc) {
-    const int base = part[tid] - run;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) data[tid * PER + i] = base + loc[i];
-  }
-  __syncthreads();
 }
 
 // one validation pass: lane = one (vertex, incident cell) entry of the flat list.  Did the update its vertex took in the
@@ -257,14 +213,9 @@ __device__ __forceinline__ void solve_block(unsigned char* lds, const u4 meta, c
 }
 
 __device__ __forceinline__ void load_m(d2 (&M)[8], const d2* mg, int b, int i, int h) {
-#ifdef LIN_NOMLOAD   /* experiment: no workspace traffic (wrong results) */
-#pragma unroll
-  for (int t = 0; t < 8; ++t) M[t] = d2{0.01 * (b + t), 0.02 * i};
-#else
   const d2* p = mg + ((size_t)(b * 2 + h) * 8) * 32 + i;
 #pragma unroll
   for (int t = 0; t < 8; ++t) M[t] = p[t * 32];
-#endif
 }
 
 // the same rows from the copy of blocks 0 and 1 in LDS (OFF_M01: same layout as the workspace)
@@ -307,33 +258,12 @@ __device__ __forceinline__ void solve_sweep(unsigned char* lds, const d2* mg, in
   }
 }
 
-__device__ __forceinline__ double grp8_mind(double v) {
-  v = fmin(v, dppd<0xB1>(v));
-  v = fmin(v, dppd<0x4E>(v));
-  v = fmin(v, dppd<0x141>(v));
-  return v;
-}
-// 1/sqrt(x) and 1/x to double precision (~1 ulp): hardware estimate + two Newton steps
-__device__ __forceinline__ double lin_rsqrt(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  const double hx = 0.5 * x;
-  y = y * (1.5 - hx * y * y);
-  y = y * (1.5 - hx * y * y);
-  return y;
-}
-__device__ __forceinline__ double lin_rcp(double x) {
-  double y = __builtin_amdgcn_rcp(x);
-  y = y * (2.0 - x * y);
-  y = y * (2.0 - x * y);
-  return y;
-}
-
 // DOLFIN's update of vertex v in exact fp64 (any degree, limited step, "stays" rule), by every group of 8 lanes of the
 // wave redundantly: the vertex's old position from OLD, its neighbours' positions as the update sees them (the new ones
-// of lower-numbered interior neighbours = cur, the old ones otherwise).  Same arithmetic as exact_update of mdq_smooth.hip.
+// of lower-numbered interior neighbours = cur, the old ones otherwise).  The loop is exact_gather of mdq_smooth_shared.hip
+// written out (through the shared function this kernel's machine code moved), the tail is the shared exact_step.
 __device__ __forceinline__ d2 exact_vertex(const unsigned char* lds, int v, int l, const unsigned char* OLD) {
 #pragma clang fp contract(off)
-  const double EPS = 3.0e-16;
   const int* ptr = reinterpret_cast<const int*>(lds + OFF_PTR);
   const uint32_t* inc = reinterpret_cast<const uint32_t*>(lds + OFF_INC);
   const unsigned char* CUR = lds + OFF_CUR;
@@ -349,20 +279,12 @@ __device__ __forceinline__ d2 exact_vertex(const unsigned char* lds, int v, int 
     sy += pa.y + pc.y;
     const double tx = pc.x - pa.x, ty = pc.y - pa.y;
     const double cr = ty * (p.x - pa.x) - tx * (p.y - pa.y);
-    rm = fmin(rm, cr * cr * lin_rcp(tx * tx + ty * ty));   // SQUARED distance to the line through the opposite edge
+    rm = fmin(rm, cr * cr * mdq_smooth_shared::rcp_nr(tx * tx + ty * ty));   // SQUARED distance to the line through the opposite edge
   }
-  sx = grp8_sum(sx);
-  sy = grp8_sum(sy);
-  rm = grp8_mind(rm);
-  const double r2k = 1.0 / (2.0 * k);
-  const double dx = sx * r2k - p.x, dy = sy * r2k - p.y;
-  const double q2 = dx * dx + dy * dy;
-  if (!(q2 >= EPS * EPS && q2 > 0.0)) return p;          // |c - p| < DOLFIN_EPS: the vertex stays
-  if (0.25 * rm < q2) {                                  // limited step: needs the lengths
-    const double f = 0.5 * (rm * lin_rsqrt(rm)) * lin_rsqrt(q2);
-    return d2{p.x + f * dx, p.y + f * dy};
-  }
-  return d2{p.x + dx, p.y + dy};                         // |c - p| <= r_min / 2: to the centroid itself
+  sx = mdq_smooth_shared::grp8_sum(sx);
+  sy = mdq_smooth_shared::grp8_sum(sy);
+  rm = mdq_smooth_shared::grp8_min(rm);
+  return mdq_smooth_shared::exact_step(p, sx, sy, rm, 1.0 / (2.0 * k));
 }
 
 // a sweep with vertices that do NOT take the full step (flags in OFF_FIXV), by ONE wave for both components: per block the
@@ -464,8 +386,7 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
   // the A / B switches of the launch (smooth_fast_impl): bit 0 every block at full gather width, bit 1 the per-vertex
   // neighbour lists by the look-up loop, bit 2 every row of a block inverse through the serial row loop
   const bool gather_all = flags & 1, nb_loop = flags & 2, inv_all = flags & 4;
-  // sweeps: given per environment, or - inside an env step - `iters_env` where a vertex was removed successfully
-  // (Env2DAirfoil._check_mesh -> flow_solver.remesh -> smooth(50), flow_solver.py:236-237; nothing otherwise)
+  // (sweeps_of of mdq_smooth_shared.hip, written out: through the function this kernel's machine code moved)
   const int S = iters_ ? iters_[b] : ((rem[b] >= 0 && rstat[b] == 0) ? iters_env : 0);
   if (S <= 0) {
     if (tid == 0) redo[b] = stats[3 * b] = stats[3 * b + 1] = stats[3 * b + 2] = 0;
@@ -498,7 +419,7 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
   for (int t = tid; t < nt; t += LWG)
     for (int k = 0; k < 3; ++k) atomicAdd(&cnt[tri[3 * t + k]], 1);
   __syncthreads();
-  scan_inclusive(cnt, part);
+  mdq_smooth_shared::scan_inclusive<SCT, LNV>(cnt, part);
   for (int v = tid; v < LNV; v += LWG) ptr[v + 1] = cnt[v];
   if (tid == 0) ptr[0] = 0;
   __syncthreads();
@@ -599,7 +520,7 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
   }
   __syncthreads();
   LT_STAMP(1)
-  scan_inclusive(cnt, part);
+  mdq_smooth_shared::scan_inclusive<SCT, LNV>(cnt, part);
   const int n_int = cnt[LNV - 1];
   const int nb = (n_int + BS - 1) / BS;
   __syncthreads();
@@ -668,7 +589,7 @@ __global__ __launch_bounds__(LWG) void smooth_linear_kernel(int NV, int NT, doub
     // call for - normally - nothing.)  The walk is written for 256 threads: the others only reach its barriers.
     static_assert(mdq_smoothing::LDS_BYTES <= LDS_BYTES && mdq_smoothing::SNV == LNV && mdq_smoothing::SNT == LNT, "hand-back in place");
     __syncthreads();
-    mdq_smoothing::smooth_env(lds, b, NV, NT, coords, cells, nv_, nt_, S, nullptr);
+    mdq_smoothing::smooth_env(lds, b, NV, NT, coords, cells, nv_, nt_, S);
     if (tid == 0) {
       redo[b] = S;                               // (diagnostics: handed back, with all its sweeps)
       stats[3 * b] = stats[3 * b + 1] = stats[3 * b + 2] = 0;
@@ -926,7 +847,7 @@ extern "C" int64_t mdq_smooth_fast_workspace_bytes(int32_t B, int32_t NV) {
   return (int64_t)B * blocks * mdq_smooth_lin::MBLK * 8 + (int64_t)B * 16 + 256;   // block inverses, [B] redo, [B][3] diagnostics
 }
 
-static int smooth_fast_impl(const char* who, int32_t B, int32_t NV, int32_t NT, double* coords, const int32_t* cells,
+static int smooth_fast_impl(int32_t B, int32_t NV, int32_t NT, double* coords, const int32_t* cells,
                             const int32_t* nv, const int32_t* nt, const int32_t* iterations, const int32_t* rem,
                             const int32_t* rstat, int32_t iters_env, void* workspace, int64_t workspace_bytes, void* stream) {
   if (B <= 0 || !coords || !cells || !nv || !nt || (!iterations && (!rem || !rstat)) || !workspace)
@@ -935,7 +856,6 @@ static int smooth_fast_impl(const char* who, int32_t B, int32_t NV, int32_t NT, 
     return smooth_big_launch(B, NV, NT, coords, cells, nv, nt, iterations, rem, rstat, iters_env, workspace, workspace_bytes, stream);
   if (workspace_bytes < mdq_smooth_fast_workspace_bytes(B, NV) || (reinterpret_cast<uintptr_t>(workspace) & 15))
     return mdq_set_error("mdq_smooth_fast: workspace too small or not 16-byte aligned (mdq_smooth_fast_workspace_bytes)");
-  (void)who;
   const int64_t blocks = (NV + mdq_smooth_lin::BS - 1) / mdq_smooth_lin::BS + 2;
   const int64_t mstride = blocks * mdq_smooth_lin::MBLK;
   double* mws = reinterpret_cast<double*>(workspace);
@@ -967,7 +887,7 @@ extern "C" int mdq_smooth_fast(int32_t B, int32_t NV, int32_t NT, double* coords
                                const int32_t* nt, const int32_t* iterations, void* workspace, int64_t workspace_bytes,
                                void* stream) {
   if (!iterations) return mdq_set_error("mdq_smooth_fast: bad arguments");
-  return smooth_fast_impl("mdq_smooth_fast", B, NV, NT, coords, cells, nv, nt, iterations, nullptr, nullptr, 0, workspace,
+  return smooth_fast_impl(B, NV, NT, coords, cells, nv, nt, iterations, nullptr, nullptr, 0, workspace,
                           workspace_bytes, stream);
 }
 
@@ -975,6 +895,6 @@ extern "C" int mdq_smooth_fast_env(int32_t B, int32_t NV, int32_t NT, double* co
                                    const int32_t* nt, const int32_t* rem, const int32_t* rstat, int32_t iterations,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
   if (!rem || !rstat) return mdq_set_error("mdq_smooth_fast_env: bad arguments");
-  return smooth_fast_impl("mdq_smooth_fast_env", B, NV, NT, coords, cells, nv, nt, nullptr, rem, rstat, iterations, workspace,
+  return smooth_fast_impl(B, NV, NT, coords, cells, nv, nt, nullptr, rem, rstat, iterations, workspace,
                           workspace_bytes, stream);
 }
