@@ -870,6 +870,54 @@ MDQ_API int mdq_env_result_forces(int32_t B, int32_t N, int32_t S, const double*
                    const double* new_lifts /* [B][S] */, const double* gt_lift /* [S] */, double lift_weight,
                    double lift_threshold, double lift_floor, int32_t* reason /* [B] or NULL */, void* stream);
 
+/*
+ * Shape quality of the cells of B meshes (appended within ABI 8; not in the reference, which never measures its meshes): one
+ * launch, one 256-thread workgroup per environment, no atomics, no scratch, LDS independent of the mesh size.  For a cell with
+ * the vertices i0, i1, i2 and the points P0, P1, P2, everything in fp64 and every product, sum and quotient rounded on its own
+ * (uncontracted; no sqrt, no transcendental):
+ *     ax = x1-x0, ay = y1-y0;  bx = x2-x0, by = y2-y0;  cx = x2-x1, cy = y2-y1
+ *     A2 = fabs((ax*by) - (ay*bx))                                      twice the area
+ *     s  = ((ax*ax + ay*ay) + (bx*bx + by*by)) + (cx*cx + cy*cy)
+ *     q  = s > 0 ? (K * A2) / s : 0       K = 2 sqrt(3) = 3.4641016151377544: 1 equilateral, 0 degenerate
+ *     d0 = ax*bx + ay*by;  d1 = -(ax*cx + ay*cy);  d2 = bx*cx + by*cy   dots at the three corners
+ *     cot = A2 > 0 ? fmax(d0, fmax(d1, d2)) / A2 : +inf                 cotangent of the cell's smallest angle
+ * A cell whose q or cot is not finite, or one of whose vertex ids lies outside [0, nv[b]) (its coordinates are then never
+ * loaded), counts as the worst: q = 0, cot = +inf.  Per environment b over the cells [0, nt[b]) (nv[b] / nt[b] are capped at
+ * NV / NT): qual[b] = {q_min, cot_max}, the smallest q and the largest cot; qinfo[b] = {cell_q, cell_cot, n_low, 0}, the
+ * lowest cell index that attains q_min, the lowest that attains cot_max, and the number of cells with q < q_floor.
+ * nt[b] <= 0: {0, +inf} and {-1, -1, 0, 0}.  The results do not depend on the order in which the cells are visited.
+ * coords, qual and qinfo must be 16-byte aligned.  Refused before the launch: B, NV or NT <= 0, a NULL pointer, an array not
+ * aligned, q_floor not finite or outside [0, 1].
+ */
+MDQ_API int mdq_mesh_quality(int32_t B, int32_t NV, int32_t NT, const double* coords /* [B][NV][2] */,
+                   const int32_t* cells /* [B][NT][3] */, const int32_t* nv, const int32_t* nt, double q_floor,
+                   double* qual /* [B][2]: q_min, cot_max */, int32_t* qinfo /* [B][4]: cell_q, cell_cot, n_low, 0 */,
+                   void* stream);
+
+/*
+ * mdq_env_result_forces with the MESH QUALITY in the reward and as a stop (appended within ABI 8).  With q_min =
+ * quality[b][0], cot_max = quality[b][1] (as mdq_mesh_quality writes them), q_ref = quality_ref[0] (device: the q_min of the
+ * initial mesh), wq = quality_weight, Qm = min_quality, and max_cot = 1 / tan(min angle), a code-0 step becomes, in fp64, in
+ * this order, uncontracted:
+ *     quality_reward = 2 fmin(q_min / q_ref, 1) - 1
+ *     accq           = (q_min < Qm) || (cot_max > max_cot)
+ *     num = drag_reward;  den = 1
+ *     lifts set:    num = num + w  * lift_reward;     den = den + w
+ *     quality set:  num = num + wq * quality_reward;  den = den + wq
+ *     reward = num / den + time_reward,    done = acc || accl || accq || vert,    reason |= 32 where accq
+ * quality [B][2] and quality_ref [1] are both set or both NULL; NULL: the three numbers are not read and every output has the
+ * bits of mdq_env_result_forces (which IS this call with NULL quality); wq = 0, Qm = 0, max_cot = +inf with a finite quality
+ * gives those bits too.  Refused before the launch: one of the two arrays alone; with quality, wq negative / not finite, Qm
+ * outside [0, 1), max_cot NaN or <= 0 (+inf, no angle stop, is allowed).
+ */
+MDQ_API int mdq_env_result_quality(int32_t B, int32_t N, int32_t S, const double* new_drags, const double* gt_drag,
+                   const int32_t* nv, int32_t nv0, const int32_t* rstat, const int32_t* topo_status, const int32_t* nsel,
+                   int32_t* code, int32_t* steps, double threshold, double time_reward, double goal_vertices, int32_t timesteps,
+                   double negative_reward, int32_t auto_reset, double* reward, uint8_t* done, int32_t* err_flag, int32_t* nv_out,
+                   const double* new_lifts, const double* gt_lift, double lift_weight, double lift_threshold, double lift_floor,
+                   int32_t* reason, const double* quality /* [B][2] */, const double* quality_ref /* [1] */,
+                   double quality_weight, double min_quality, double max_cot, void* stream);
+
 /* mdq_restore_rows for the environments with mask[b] != 0 (device array): the in-place reset without a host-side list. */
 MDQ_API int mdq_restore_rows_masked(int32_t n, void* const* dst, const void* const* src, const int64_t* row_bytes, int32_t B,
                             const uint8_t* mask, void* stream);
@@ -946,6 +994,13 @@ typedef struct {
   const double* gt_lift;
   double lift_weight, lift_threshold, lift_floor;
   int32_t* reason;
+  /* optional (appended within ABI 8), the mesh quality in the reward and as a stop, exactly as mdq_env_result_quality:
+   * quality [B][2] (q_min, cot_max as mdq_mesh_quality writes them) and quality_ref ([1]; with src_of_env [A], the value of
+   * the environment's airfoil) are both set or both NULL (then the three numbers are not read: a zero-initialised tail is
+   * the step without the quality part); a stop on the quality alone resets the environment in place like any other. */
+  const double* quality;
+  const double* quality_ref;
+  double quality_weight, min_quality, max_cot;
 } mdq_env_finish_desc;
 MDQ_API int mdq_env_finish(const mdq_env_finish_desc* d, void* stream);
 

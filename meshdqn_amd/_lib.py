@@ -130,7 +130,9 @@ class EnvFinishDesc(C.Structure):
         (n, C.c_void_p) for n in ("coords", "u", "p", "n_closest", "x_init", "x", "arrive")] + [
         (n, C.c_void_p) for n in ("src_of_env", "nv0_of")] + [("src_stride", C.c_int64 * FINISH_MAX_ROWS)] + [
         ("new_lifts", C.c_void_p), ("gt_lift", C.c_void_p)] + [                    # optional, appended within ABI 8
-        (n, C.c_double) for n in ("lift_weight", "lift_threshold", "lift_floor")] + [("reason", C.c_void_p)]
+        (n, C.c_double) for n in ("lift_weight", "lift_threshold", "lift_floor")] + [("reason", C.c_void_p)] + [
+        ("quality", C.c_void_p), ("quality_ref", C.c_void_p)] + [                  # optional, appended within ABI 8
+        (n, C.c_double) for n in ("quality_weight", "min_quality", "max_cot")]
 
 
 PACK_MAX = 32      # MDQ_GCN_PACK_MAX
@@ -215,6 +217,13 @@ SYMBOLS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                         C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "mdq_env_result_quality": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                         C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "mdq_mesh_quality": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "mdq_restore_rows_masked": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mdq_restore_rows_src": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),

@@ -3,6 +3,7 @@
 // `v_func.interpolate(original_u)`, `p_func.interpolate(original_p)` and the vertex evaluations).
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <string>
 
@@ -511,7 +512,8 @@ __global__ void env_result_kernel(int B, int N, int S, const double* new_drags, 
                                   int32_t timesteps, double negative_reward, int32_t auto_reset, double* reward,
                                   uint8_t* done, int32_t* err_flag, int32_t* nv_out, const double* new_lifts,
                                   const double* gt_lift, double lift_weight, double lift_threshold, double lift_floor,
-                                  int32_t* reason) {
+                                  int32_t* reason, const double* quality, const double* quality_ref, double quality_weight,
+                                  double min_quality, double max_cot) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
@@ -534,8 +536,8 @@ __global__ void env_result_kernel(int B, int N, int S, const double* new_drags, 
   const double tr = (double)(nv0 - nv[b]) * time_reward;
   const bool vert = (double)nv[b] < goal_vertices * (double)nv0;
   const bool ok = c == 0;
-  double r_ok = drag_reward + tr;
-  bool accl = false;
+  double r_ok = drag_reward + tr, num = drag_reward, den = 1.0;
+  bool accl = false, accq = false;
   if (new_lifts) {
     const double lift_factor = -2.0 * log(0.5) / lift_threshold;
     double sl = 0.0;
@@ -546,17 +548,28 @@ __global__ void env_result_kernel(int B, int N, int S, const double* new_drags, 
       accl = accl || el > lift_threshold;
     }
     const double lift_reward = 2.0 * exp(-lift_factor * sqrt(sl)) - 1.0;
-    r_ok = (drag_reward + lift_weight * lift_reward) / (1.0 + lift_weight) + tr;
+    num = drag_reward + lift_weight * lift_reward;
+    den = 1.0 + lift_weight;
+    r_ok = num / den + tr;
+  }
+  if (quality) {        // (header: mdq_env_result_quality)
+    const double q_min = quality[2 * (int64_t)b], cot_max = quality[2 * (int64_t)b + 1];
+    const double quality_reward = 2.0 * fmin(q_min / quality_ref[0], 1.0) - 1.0;
+    accq = q_min < min_quality || cot_max > max_cot;
+    num = num + quality_weight * quality_reward;
+    den = den + quality_weight;
+    r_ok = num / den + tr;
   }
   double r = ok ? r_ok : negative_reward;
-  bool dn = ok ? (acc || accl || vert) : (c != 1);
+  bool dn = ok ? (acc || accl || accq || vert) : (c != 1);
   const int st = steps[b] + 1;
   dn = dn || st >= timesteps;
   reward[b] = r;
   if (nv_out) nv_out[b] = nv[b];      // (the vertex count of the step, before an in-place reset rewrites nv)
   done[b] = dn ? 1 : 0;
   if (reason)
-    reason[b] = (ok ? (acc ? 1 : 0) | (accl ? 2 : 0) | (vert ? 4 : 0) : (c != 1 ? 8 : 0)) | (st >= timesteps ? 16 : 0);
+    reason[b] = (ok ? (acc ? 1 : 0) | (accl ? 2 : 0) | (vert ? 4 : 0) | (accq ? 32 : 0) : (c != 1 ? 8 : 0)) |
+                (st >= timesteps ? 16 : 0);
   code[b] = c;
   steps[b] = (dn && auto_reset) ? 0 : st;
 }
@@ -634,6 +647,39 @@ static const char* lift_args_error(const double* new_lifts, const double* gt_lif
   return nullptr;
 }
 
+// the quality arguments of mdq_env_result_quality / mdq_env_finish_desc: NULL when they are acceptable (both arrays absent,
+// or both present with wq >= 0 finite, Qm in [0, 1), max_cot > 0 (+inf allowed)), else what is wrong with them
+static const char* quality_args_error(const double* quality, const double* quality_ref, double wq, double Qm, double max_cot) {
+  if ((quality == nullptr) != (quality_ref == nullptr)) return "quality and quality_ref go together (both or neither)";
+  if (!quality) return nullptr;
+  if (!(wq >= 0.0) || std::isinf(wq)) return "quality_weight must be finite and >= 0";
+  if (!(Qm >= 0.0 && Qm < 1.0)) return "min_quality must lie in [0, 1) (0: no stop)";
+  if (!(max_cot > 0.0)) return "max_cot must be > 0 (+inf: no angle stop)";
+  return nullptr;
+}
+
+extern "C" int mdq_env_result_quality(int32_t B, int32_t N, int32_t S, const double* new_drags, const double* gt_drag,
+                                      const int32_t* nv, int32_t nv0, const int32_t* rstat, const int32_t* topo_status,
+                                      const int32_t* nsel, int32_t* code, int32_t* steps, double threshold, double time_reward,
+                                      double goal_vertices, int32_t timesteps, double negative_reward, int32_t auto_reset,
+                                      double* reward, uint8_t* done, int32_t* err_flag, int32_t* nv_out, const double* new_lifts,
+                                      const double* gt_lift, double lift_weight, double lift_threshold, double lift_floor,
+                                      int32_t* reason, const double* quality, const double* quality_ref, double quality_weight,
+                                      double min_quality, double max_cot, void* stream) {
+  if (B <= 0 || S <= 0 || !new_drags || !gt_drag || !nv || !rstat || !nsel || !code || !steps || !reward || !done || !err_flag)
+    return mdq_set_error("mdq_env_result: bad arguments");
+  if (const char* why = lift_args_error(new_lifts, gt_lift, lift_weight, lift_threshold, lift_floor))
+    return mdq_set_error((std::string("mdq_env_result_forces: ") + why).c_str());
+  if (const char* why = quality_args_error(quality, quality_ref, quality_weight, min_quality, max_cot))
+    return mdq_set_error((std::string("mdq_env_result_quality: ") + why).c_str());
+  hipLaunchKernelGGL(mdq_mesh::env_result_kernel, dim3((B + 127) / 128), dim3(128), 0, (hipStream_t)stream, B, N, S, new_drags,
+                     gt_drag, nv, nv0, rstat, topo_status, nsel, code, steps, threshold, time_reward, goal_vertices, timesteps,
+                     negative_reward, auto_reset, reward, done, err_flag, nv_out, new_lifts, gt_lift, lift_weight, lift_threshold,
+                     lift_floor, reason, quality, quality_ref, quality_weight, min_quality, max_cot);
+  if (hipGetLastError() != hipSuccess) return mdq_set_error("env_result_kernel launch failed");
+  return 0;
+}
+
 extern "C" int mdq_env_result_forces(int32_t B, int32_t N, int32_t S, const double* new_drags, const double* gt_drag,
                                      const int32_t* nv, int32_t nv0, const int32_t* rstat, const int32_t* topo_status,
                                      const int32_t* nsel, int32_t* code, int32_t* steps, double threshold, double time_reward,
@@ -641,16 +687,9 @@ extern "C" int mdq_env_result_forces(int32_t B, int32_t N, int32_t S, const doub
                                      double* reward, uint8_t* done, int32_t* err_flag, int32_t* nv_out, const double* new_lifts,
                                      const double* gt_lift, double lift_weight, double lift_threshold, double lift_floor,
                                      int32_t* reason, void* stream) {
-  if (B <= 0 || S <= 0 || !new_drags || !gt_drag || !nv || !rstat || !nsel || !code || !steps || !reward || !done || !err_flag)
-    return mdq_set_error("mdq_env_result: bad arguments");
-  if (const char* why = lift_args_error(new_lifts, gt_lift, lift_weight, lift_threshold, lift_floor))
-    return mdq_set_error((std::string("mdq_env_result_forces: ") + why).c_str());
-  hipLaunchKernelGGL(mdq_mesh::env_result_kernel, dim3((B + 127) / 128), dim3(128), 0, (hipStream_t)stream, B, N, S, new_drags,
-                     gt_drag, nv, nv0, rstat, topo_status, nsel, code, steps, threshold, time_reward, goal_vertices, timesteps,
-                     negative_reward, auto_reset, reward, done, err_flag, nv_out, new_lifts, gt_lift, lift_weight, lift_threshold,
-                     lift_floor, reason);
-  if (hipGetLastError() != hipSuccess) return mdq_set_error("env_result_kernel launch failed");
-  return 0;
+  return mdq_env_result_quality(B, N, S, new_drags, gt_drag, nv, nv0, rstat, topo_status, nsel, code, steps, threshold, time_reward,
+                                goal_vertices, timesteps, negative_reward, auto_reset, reward, done, err_flag, nv_out, new_lifts,
+                                gt_lift, lift_weight, lift_threshold, lift_floor, reason, nullptr, nullptr, 0.0, 0.0, 0.0, stream);
 }
 
 extern "C" int mdq_env_result(int32_t B, int32_t N, int32_t S, const double* new_drags, const double* gt_drag, const int32_t* nv,
@@ -723,8 +762,8 @@ __global__ __launch_bounds__(256) void env_finish_kernel(mdq_env_finish_desc d) 
     const double tr = (double)(nv0 - nvb) * d.time_reward;
     const bool vert = (double)nvb < d.goal_vertices * (double)nv0;
     const bool ok = c == 0;
-    double r_ok = drag_reward + tr;
-    bool accl = false;
+    double r_ok = drag_reward + tr, num = drag_reward, den = 1.0;
+    bool accl = false, accq = false;
     if (d.new_lifts) {       // (workgroup-uniform: a kernel argument)
       const double* gt_lift = d.gt_lift + (int64_t)a * d.S;
       const double lift_factor = -2.0 * log(0.5) / d.lift_threshold;
@@ -736,10 +775,20 @@ __global__ __launch_bounds__(256) void env_finish_kernel(mdq_env_finish_desc d) 
         accl = accl || el > d.lift_threshold;
       }
       const double lift_reward = 2.0 * exp(-lift_factor * sqrt(sl)) - 1.0;
-      r_ok = (drag_reward + d.lift_weight * lift_reward) / (1.0 + d.lift_weight) + tr;
+      num = drag_reward + d.lift_weight * lift_reward;
+      den = 1.0 + d.lift_weight;
+      r_ok = num / den + tr;
+    }
+    if (d.quality) {         // (workgroup-uniform: a kernel argument; header: mdq_env_result_quality)
+      const double q_min = d.quality[2 * (int64_t)b], cot_max = d.quality[2 * (int64_t)b + 1];
+      const double quality_reward = 2.0 * fmin(q_min / d.quality_ref[a], 1.0) - 1.0;
+      accq = q_min < d.min_quality || cot_max > d.max_cot;
+      num = num + d.quality_weight * quality_reward;
+      den = den + d.quality_weight;
+      r_ok = num / den + tr;
     }
     const double r = ok ? r_ok : d.negative_reward;
-    bool dn = ok ? (acc || accl || vert) : (c != 1);
+    bool dn = ok ? (acc || accl || accq || vert) : (c != 1);
     const int st = d.steps_in[b] + 1;
     dn = dn || st >= d.timesteps;
     if (y == 0) {
@@ -747,7 +796,8 @@ __global__ __launch_bounds__(256) void env_finish_kernel(mdq_env_finish_desc d) 
       if (d.nv_out) d.nv_out[b] = nvb;
       d.done[b] = dn ? 1 : 0;
       if (d.reason)
-        d.reason[b] = (ok ? (acc ? 1 : 0) | (accl ? 2 : 0) | (vert ? 4 : 0) : (c != 1 ? 8 : 0)) | (st >= d.timesteps ? 16 : 0);
+        d.reason[b] = (ok ? (acc ? 1 : 0) | (accl ? 2 : 0) | (vert ? 4 : 0) | (accq ? 32 : 0) : (c != 1 ? 8 : 0)) |
+                      (st >= d.timesteps ? 16 : 0);
       d.code_out[b] = c;
       d.steps_out[b] = (dn && d.auto_reset) ? 0 : st;
     }
@@ -862,6 +912,8 @@ extern "C" int mdq_env_finish(const mdq_env_finish_desc* d, void* stream) {
   if (d->src_of_env && !d->nv0_of) return mdq_set_error("mdq_env_finish: src_of_env needs nv0_of");
   if (const char* why = lift_args_error(d->new_lifts, d->gt_lift, d->lift_weight, d->lift_threshold, d->lift_floor))
     return mdq_set_error((std::string("mdq_env_finish: ") + why).c_str());
+  if (const char* why = quality_args_error(d->quality, d->quality_ref, d->quality_weight, d->min_quality, d->max_cot))
+    return mdq_set_error((std::string("mdq_env_finish: ") + why).c_str());
   // workgroups per environment: enough lanes for the hand-over copies AND the in-place reset of a terminated environment
   // (16 bytes per lane and pass, ~4 passes; the workgroups of the other environments find nothing to restore and leave);
   // without cached initial features the reset path needs the whole environment in one workgroup
@@ -877,6 +929,108 @@ extern "C" int mdq_env_finish(const mdq_env_finish_desc* d, void* stream) {
   }
   hipLaunchKernelGGL(mdq_mesh::env_finish_kernel, dim3(d->B, Y), dim3(256), 0, (hipStream_t)stream, *d);
   if (hipGetLastError() != hipSuccess) return mdq_set_error("env_finish_kernel launch failed");
+  return 0;
+}
+
+namespace mdq_mesh {
+// ---- shape quality of the cells (header: mdq_mesh_quality; not in the reference)
+// (value, index) pairs: `(v2, i2)` replaces `(v, i)` when its value is better (LESS: smaller, else larger) or equal with the
+// lower index - an order-independent choice, so the lanes and waves may be combined in any order.  No NaN enters: a cell
+// whose numbers are not finite has been turned into the worst cell before.
+template <bool LESS>
+__device__ __forceinline__ void qpair_take(double& v, int& i, double v2, int i2) {
+  const bool better = LESS ? v2 < v : v2 > v;
+  if (better || (v2 == v && i2 < i)) {
+    v = v2;
+    i = i2;
+  }
+}
+
+// One 256-thread workgroup per environment, thread t walks the cells t, t + 256, ...; the mesh size appears in the trip
+// count only (no LDS table, no atomics), so the one instance serves every mesh class.
+__global__ __launch_bounds__(256) void mesh_quality_kernel(int NV, int NT, const double* __restrict__ coords,
+                                                           const int32_t* __restrict__ cells, const int32_t* __restrict__ nv,
+                                                           const int32_t* __restrict__ nt, double q_floor,
+                                                           double* __restrict__ qual, int32_t* __restrict__ qinfo) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int nvb = max(min(__builtin_amdgcn_readfirstlane(nv[b]), NV), 0);
+  const int ntb = min(__builtin_amdgcn_readfirstlane(nt[b]), NT);
+  const double INF = __builtin_inf();
+  if (ntb <= 0) {        // (workgroup-uniform)
+    if (tid == 0) {
+      *reinterpret_cast<double2*>(qual + 2 * (int64_t)b) = make_double2(0.0, INF);
+      *reinterpret_cast<int4*>(qinfo + 4 * (int64_t)b) = make_int4(-1, -1, 0, 0);
+    }
+    return;
+  }
+  const double2* P = reinterpret_cast<const double2*>(coords) + (int64_t)b * NV;      // (one 16-byte load per vertex)
+  const int32_t* C = cells + (int64_t)b * NT * 3;
+  const double K = 3.4641016151377544;       // 2 sqrt(3)
+  double bq = INF, bc = -INF;
+  int iq = INT_MAX, ic = INT_MAX, cnt = 0;
+  for (int t = tid; t < ntb; t += 256) {
+    const int i0 = C[3 * t], i1 = C[3 * t + 1], i2 = C[3 * t + 2];
+    double q = 0.0, cot = INF;
+    if ((unsigned)i0 < (unsigned)nvb && (unsigned)i1 < (unsigned)nvb && (unsigned)i2 < (unsigned)nvb) {
+      const double2 p0 = P[i0], p1 = P[i1], p2 = P[i2];
+      const double ax = p1.x - p0.x, ay = p1.y - p0.y, bx = p2.x - p0.x, by = p2.y - p0.y, cx = p2.x - p1.x, cy = p2.y - p1.y;
+      const double A2 = fabs((ax * by) - (ay * bx));
+      const double s = ((ax * ax + ay * ay) + (bx * bx + by * by)) + (cx * cx + cy * cy);
+      const double qc = s > 0.0 ? (K * A2) / s : 0.0;
+      const double d0 = ax * bx + ay * by, d1 = -(ax * cx + ay * cy), d2 = bx * cx + by * cy;
+      const double cc = A2 > 0.0 ? fmax(d0, fmax(d1, d2)) / A2 : INF;
+      if (fabs(qc) < INF && fabs(cc) < INF) {       // (both finite; else the worst cell)
+        q = qc;
+        cot = cc;
+      }
+    }
+    if (q < bq) {         // (t ascends: the first cell to attain a value keeps it)
+      bq = q;
+      iq = t;
+    }
+    if (cot > bc) {
+      bc = cot;
+      ic = t;
+    }
+    cnt += q < q_floor ? 1 : 0;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    qpair_take<true>(bq, iq, __shfl_xor(bq, o, 64), __shfl_xor(iq, o, 64));
+    qpair_take<false>(bc, ic, __shfl_xor(bc, o, 64), __shfl_xor(ic, o, 64));
+    cnt += __shfl_xor(cnt, o, 64);
+  }
+  __shared__ double s_q[4], s_c[4];
+  __shared__ int s_iq[4], s_ic[4], s_cnt[4];
+  const int w = tid >> 6;
+  if ((tid & 63) == 0) {
+    s_q[w] = bq, s_iq[w] = iq;
+    s_c[w] = bc, s_ic[w] = ic;
+    s_cnt[w] = cnt;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < 4; ++k) {
+      qpair_take<true>(bq, iq, s_q[k], s_iq[k]);
+      qpair_take<false>(bc, ic, s_c[k], s_ic[k]);
+      cnt += s_cnt[k];
+    }
+    *reinterpret_cast<double2*>(qual + 2 * (int64_t)b) = make_double2(bq, bc);
+    *reinterpret_cast<int4*>(qinfo + 4 * (int64_t)b) = make_int4(iq, ic, cnt, 0);
+  }
+}
+}  // namespace mdq_mesh
+
+extern "C" int mdq_mesh_quality(int32_t B, int32_t NV, int32_t NT, const double* coords, const int32_t* cells, const int32_t* nv,
+                                const int32_t* nt, double q_floor, double* qual, int32_t* qinfo, void* stream) {
+  if (B <= 0 || NV <= 0 || NT <= 0) return mdq_set_error("mdq_mesh_quality: B, NV and NT must be positive");
+  if (!coords || !cells || !nv || !nt || !qual || !qinfo) return mdq_set_error("mdq_mesh_quality: NULL pointer");
+  if (((uintptr_t)coords | (uintptr_t)qual | (uintptr_t)qinfo) & 15)
+    return mdq_set_error("mdq_mesh_quality: coords, qual and qinfo must be 16-byte aligned");
+  if (!(q_floor >= 0.0 && q_floor <= 1.0)) return mdq_set_error("mdq_mesh_quality: q_floor must be finite and lie in [0, 1]");
+  hipLaunchKernelGGL(mdq_mesh::mesh_quality_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, NV, NT, coords, cells, nv, nt,
+                     q_floor, qual, qinfo);
+  if (hipGetLastError() != hipSuccess) return mdq_set_error("mesh_quality_kernel launch failed");
   return 0;
 }
 

@@ -89,12 +89,20 @@ def select_action(net, state, device):
     return int(q.argmax().item())
 
 
+def _quality_row(env):
+    """[q_min, smallest angle in degrees] of the environment's current mesh (mdq_mesh_quality, B = 1)."""
+    q_min, cot_max = env._mesh_batch().quality()[0][0].cpu().tolist()
+    return [q_min, float(np.degrees(np.arctan2(1.0, cot_max)))]
+
+
 def deploy(env, net=None, actions=None, complete_traj: bool = True, max_steps: Optional[int] = None,
            save_dir: Optional[str] = None, prefix: str = "", stop_on_done: bool = True, batched: bool = True,
            final_sim: bool = True):
     """Roll the policy (or a recorded action list) until the environment terminates; returns a dict of trajectories and
     writes the reference's `.npy` files into `save_dir` (names `{prefix}interpolate_drag_trajectory.npy`,
-    `{prefix}drag_trajectory.npy`, `{prefix}complete_drags.npy`, `{prefix}complete_lifts.npy`, `{prefix}actions.npy`)."""
+    `{prefix}drag_trajectory.npy`, `{prefix}complete_drags.npy`, `{prefix}complete_lifts.npy`, `{prefix}actions.npy`).
+    `est_quality` of the dict (not in the reference; no file, the files keep their reference layout): rows [q_min, smallest
+    angle in degrees] of the cells of the initial mesh and of the mesh after every step."""
     from .flow_solver import Mesh
     dev = env.compute_device
     fs = env.flow_solver
@@ -106,6 +114,7 @@ def deploy(env, net=None, actions=None, complete_traj: bool = True, max_steps: O
     gt_drag, gt_lift = np.array(env.gt_drag, np.float64), np.array(env.gt_lift, np.float64)
     est_v, est_d, est_l = [nv0], [np.array(env.new_drags)], [np.array(env.new_lifts)]           # :304-313
     traj_v, traj_d, traj_l = [nv0], [gt_drag], [gt_lift]                                          # :303
+    est_q = [_quality_row(env)]
     complete_d, complete_l = [gt_drag], [gt_lift]                                                 # :315-316
     taken, selected_ids, pending = [], [], []
     best_mesh = Mesh(fs.mesh)
@@ -126,6 +135,7 @@ def deploy(env, net=None, actions=None, complete_traj: bool = True, max_steps: O
         est_v.append(nv_after)
         est_d.append(np.array(env.new_drags))
         est_l.append(np.array(env.new_lifts))
+        est_q.append(_quality_row(env))
         if complete_traj and selected is not None:   # :376-387
             traj_v.append(nv_after)
             if batched:
@@ -167,6 +177,7 @@ def deploy(env, net=None, actions=None, complete_traj: bool = True, max_steps: O
         fs.mesh = Mesh(best_mesh)
     out = dict(actions=np.array(taken), selected=np.array(selected_ids, dtype=np.float64),
                est_vertices=np.array(est_v), est_drag=np.array(est_d), est_lift=np.array(est_l),
+               est_quality=np.array(est_q, dtype=np.float64),
                traj_vertices=np.array(traj_v), traj_drag=np.array(traj_d), traj_lift=np.array(traj_l),
                complete_drags=np.array(complete_d), complete_lifts=np.array(complete_l),
                gt_drag=gt_drag, gt_lift=gt_lift, done=bool(done), rollout_seconds=t_roll, resimulation_seconds=t_sim,

@@ -58,6 +58,10 @@ class Env2DAirfoil(object):
         # opt-in (not in the reference): the lift in the reward and in the accuracy stop (reward.py); `end_reason` is the
         # bitmask (reward.REASON_*) of what ended the last step, 0 while the episode goes on
         self.lift = _reward.LiftSpec.from_config(ap)
+        # opt-in as well: the mesh quality (mdq_mesh_quality with B = 1 on the light mesh descriptor) in the reward and as a
+        # stop; `q_ref` is the q_min of the initial (smoothed) mesh, `mesh_quality` / `quality_cell` describe the last step's
+        self.quality = _reward.QualitySpec.from_config(ap)
+        self.q_ref, self.mesh_quality, self.quality_cell = None, None, -1
         self.end_reason = 0
         self._mesh_name = str(config["flow_config"]["geometry_params"]["mesh"])
         self.removed_coordinates = []
@@ -128,6 +132,10 @@ class Env2DAirfoil(object):
             torch.stack([p.data for p in self.original_p]), device=self.compute_device)
         self._light = None
         self.lift.check_gt_lift(self.gt_lift, len(self.gt_drag), names=[self._mesh_name])
+        if self.quality.on:
+            self._measure_quality()
+            self.q_ref = float(self.mesh_quality[0])
+            self.quality.check_q_ref([self.q_ref], names=[self._mesh_name])
         self._calculate_velocities()
         self._calculate_pressures()
         self.steps = 0
@@ -289,6 +297,12 @@ class Env2DAirfoil(object):
             self._light = LightMeshBatch([topo], [topo.coords], self.flow_solver.mu, device=self.compute_device)
         return self._light
 
+    def _measure_quality(self):
+        """(q_min, cot_max) and the worst cell of the current mesh: one launch with B = 1."""
+        qual, qinfo = self._mesh_batch().quality()
+        self.mesh_quality = qual[0].cpu().numpy()
+        self.quality_cell = int(qinfo[0, 0])
+
     def calculate_reward(self):
         try:
             lb = self._mesh_batch()
@@ -302,18 +316,22 @@ class Env2DAirfoil(object):
             drag, lift = lb.probe_forces(ub, pb)  # 2S surface integrals in one launch
             self.new_drags = drag[0].cpu().numpy()
             self.new_lifts = lift[0].cpu().numpy()
+            if self.quality.on:
+                self._measure_quality()
         except Exception:
             print("\n\nSAMPLING BROKE\n\n")
             return self.NEGATIVE_REWARD, True, True
-        value, acc_thresh, lift_thresh = _reward.accuracy_terms(self.lift, self.gt_drag, self.new_drags, self.threshold,
-                                                                self.gt_lift, self.new_lifts)
+        terms = _reward.accuracy_terms(self.lift, self.gt_drag, self.new_drags, self.threshold, self.gt_lift, self.new_lifts,
+                                       qspec=self.quality, quality=self.mesh_quality, q_ref=self.q_ref)
+        value, acc_thresh, lift_thresh = terms[:3]
+        quality_thresh = bool(terms[3]) if self.quality.on else False
         time_reward = (self.initial_num_node - len(self.coordinate_list)) * self.TIME_REWARD
         vert_thresh = len(self.flow_solver.mesh.coordinates()) < self.goal_vertices * self.initial_num_node
         if vert_thresh:
             print("\nMAXIMUM REMOVALS REACHED\n")
         self.end_reason = int(bool(acc_thresh) * _reward.REASON_DRAG | bool(lift_thresh) * _reward.REASON_LIFT |
-                              bool(vert_thresh) * _reward.REASON_VERTICES)
-        return float(value + time_reward), False, bool(acc_thresh or lift_thresh or vert_thresh)
+                              bool(vert_thresh) * _reward.REASON_VERTICES | quality_thresh * _reward.REASON_QUALITY)
+        return float(value + time_reward), False, bool(acc_thresh or lift_thresh or vert_thresh or quality_thresh)
 
     def set_plot_dir(self, plot_dir):
         self.plot_dir = plot_dir

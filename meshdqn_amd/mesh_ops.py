@@ -81,6 +81,16 @@ class LightMeshBatch:
         _lib.check(rc, "mdq_probe_forces")
         return drag, lift
 
+    def quality(self, q_floor: float = 0.0):
+        """Shape quality of the cells of the B meshes (`mesh_quality_gpu`): qual (B,2) f8, qinfo (B,4) i4 device tensors.  The
+        cell lists ([B][NT][3]: the descriptor holds them dof-major) are uploaded at the first call."""
+        if getattr(self, "_cells_dev", None) is None:
+            h = np.zeros((self.B, self.cap["NT"], 3), np.int32)
+            for b, t in enumerate(self.topos):
+                h[b, :t.nt] = t.cells
+            self._cells_dev = torch.from_numpy(h).to(self.device)
+        return mesh_quality_gpu(self.t["coords"], self._cells_dev, self.t["nv"], self.t["nt"], q_floor)
+
 
 class SnapshotInterpolator:
     """Source = the original (smoothed) mesh with S stored snapshots; targets = coarsened meshes."""
@@ -386,6 +396,28 @@ def smooth_batch_gpu(coords: torch.Tensor, cells: torch.Tensor, nv: torch.Tensor
         ws = _SMOOTH_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=coords.device)
     _lib.check(lib.mdq_smooth_fast(B, NV, NT, coords.data_ptr(), cells.data_ptr(), nv.data_ptr(), nt.data_ptr(),
                                    iterations.data_ptr(), ws.data_ptr(), ws.numel(), sp), "mdq_smooth_fast")
+
+
+def mesh_quality_gpu(coords: torch.Tensor, cells: torch.Tensor, nv: torch.Tensor, nt: torch.Tensor, q_floor: float = 0.0,
+                     out=None):
+    """Shape quality of the cells of B meshes in one launch (`mdq_mesh_quality`, formulas in the header): coords (B,NV,2) f8,
+    cells (B,NT,3) i4, nv / nt (B,) i4 device tensors.  Returns the device tensors (qual (B,2) f8: q_min, cot_max; qinfo
+    (B,4) i4: cell_q, cell_cot, the number of cells with q < `q_floor`, 0); `out` = (qual, qinfo) to write into."""
+    lib = _lib.load()
+    B, NV, NT = coords.shape[0], coords.shape[1], cells.shape[1]
+    assert coords.dtype == torch.float64 and cells.dtype == torch.int32 and coords.is_contiguous() and cells.is_contiguous()
+    assert nv.dtype == torch.int32 and nt.dtype == torch.int32 and nv.numel() == B and nt.numel() == B
+    assert tuple(coords.shape) == (B, NV, 2) and tuple(cells.shape) == (B, NT, 3)
+    if out is None:
+        qual = torch.empty((B, 2), dtype=torch.float64, device=coords.device)
+        qinfo = torch.empty((B, 4), dtype=torch.int32, device=coords.device)
+    else:
+        qual, qinfo = out
+        assert qual.dtype == torch.float64 and qinfo.dtype == torch.int32 and qual.is_contiguous() and qinfo.is_contiguous()
+        assert tuple(qual.shape) == (B, 2) and tuple(qinfo.shape) == (B, 4)
+    _lib.check(lib.mdq_mesh_quality(B, NV, NT, coords.data_ptr(), cells.data_ptr(), nv.data_ptr(), nt.data_ptr(), float(q_floor),
+                                    qual.data_ptr(), qinfo.data_ptr(), _lib.stream_ptr()), "mdq_mesh_quality")
+    return qual, qinfo
 
 
 def smooth_env_gpu(coords: torch.Tensor, cells: torch.Tensor, nv: torch.Tensor, nt: torch.Tensor, rem: torch.Tensor,

@@ -358,7 +358,7 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
     ev_opt = rep = None
     trace = dict(u=[], idx=[], weight=[], td=[], beta=[])
     ntrace = dict(idx=[], reward=[], nonfinal=[], steps=[], head=[])
-    rewards, dones_hist, actions_hist = [], [], []
+    rewards, dones_hist, actions_hist, reasons_hist = [], [], [], []
     episodes = _EpisodeLog(log, venv)
     step_no, prev = 0, None      # prev: (record base, act, rew, done) of the step whose records await their next state
     while step_no < num_steps:
@@ -476,6 +476,7 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
             rewards.append(rew.copy())
             dones_hist.append(done.copy())
             actions_hist.append(out["actions"][k].copy())
+            reasons_hist.append(out["reasons"][k].copy())
             episodes.add_step(eps_mean[k], out["actions"][k], rew, done)
         if log is not None:
             for l_ in new_losses:
@@ -484,7 +485,7 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
         if every and on_every is not None and (step_no // every) > ((step_no - K) // every):
             on_every(step_no, steps_done)
     out = dict(rewards=np.array(rewards), dones=np.array(dones_hist), losses=list(trainer.losses), steps_done=steps_done,
-               actions=np.array(actions_hist))
+               actions=np.array(actions_hist), reasons=np.array(reasons_hist))     # (reasons: reward.REASON_* per step)
     if per_trace:
         out["per"] = {key: np.concatenate(v) if v else np.zeros(0) for key, v in trace.items()}
     if nstep_trace:

@@ -32,8 +32,8 @@ from .env import Env2DAirfoil
 from .flow_leg import FlowLeg, check_flow_forces
 from .inflow import canonical_inlet, inflow_factors, leg_profile_table, spec_table
 from .ipcs_batch import flow_table
-from .mesh_ops import (DeviceTopologyBatch, HostTopologyBatch, remesh_batch, remesh_batch_gpu, remesh_workspace, smooth_batch_gpu,
-                       smooth_env_gpu)
+from .mesh_ops import (DeviceTopologyBatch, HostTopologyBatch, mesh_quality_gpu, remesh_batch, remesh_batch_gpu, remesh_workspace,
+                       smooth_batch_gpu, smooth_env_gpu)
 
 
 def _host_cores() -> int:
@@ -191,6 +191,8 @@ class VecEnv2DAirfoil:
         self.NEGATIVE_REWARD = -1.0
         # opt-in (not in the reference): the lift in the reward and in the accuracy stop - batch-wide numbers, like `threshold`
         self.lift = _reward.LiftSpec.from_config(ap)
+        # opt-in as well: the mesh quality (one mdq_mesh_quality launch per step) in the reward and as a stop - batch-wide too
+        self.quality = _reward.QualitySpec.from_config(ap)
         self.S = len(base.original_u)
         if any(len(bb.original_u) != self.S or np.asarray(bb.gt_drag).shape != (self.S,) for bb in bases):
             raise ValueError("snapshots: every airfoil needs the same S = solver_steps // save_steps snapshots and gt_drag values")
@@ -347,6 +349,18 @@ class VecEnv2DAirfoil:
             self._gt_lift_env = np.asarray(self.gt_lift, dtype=np.float64).reshape(A, self.S)[self.airfoil]
         self.new_drags = np.zeros((B, self.S))
         self.new_lifts = np.zeros((B, self.S))
+        # mesh quality: q_ref per airfoil from ONE launch on the cached initial meshes; per step the kernel writes
+        # `_dev_quality` (B, 2) = (q_min, cot_max) and `_dev_qinfo` (B, 4), mirrored in `mesh_quality` / `quality_cell`
+        self.q_ref = self._q_ref_env = self._q_ref_dev = self._dev_quality = self._dev_qinfo = None
+        self.mesh_quality, self.quality_cell = np.zeros((B, 2)), np.full(B, -1, np.int32)
+        if self.quality.on:
+            qual0, _ = mesh_quality_gpu(self._x0_dev, self._cells0_dev, self._nv0_dev, self._nt0_dev)
+            self.q_ref = qual0[:, 0].cpu().numpy().copy()                           # (A,)
+            self.quality.check_q_ref(self.q_ref, names=[bb._mesh_name for bb in bases])
+            self._q_ref_env = self.q_ref[self.airfoil]                              # (B,)
+            self._q_ref_dev = qual0[:, 0].contiguous()
+            self._dev_quality = torch.empty((B, 2), dtype=torch.float64, device=self.device)
+            self._dev_qinfo = torch.empty((B, 4), dtype=torch.int32, device=self.device)
         self.reset_all()
 
     @property
@@ -382,7 +396,8 @@ class VecEnv2DAirfoil:
         if self.A == 1:
             # every environment restarts from the same mesh: cache its derived data (row 0) for in-place resets
             self._init_cache = dict(h={k: a[0].copy() for k, a in self.h.items()}, u=self.u[0].clone(), p=self.p[0].clone(),
-                                    drags=self.new_drags[0].copy(), lifts=self.new_lifts[0].copy())
+                                    drags=self.new_drags[0].copy(), lifts=self.new_lifts[0].copy(),
+                                    quality=self.mesh_quality[0].copy(), quality_cell=self.quality_cell[0].copy())
             if self.gpu_topology:
                 self._init_cache["dev"] = {k: self.dtopo.t[k][0].clone() for k in self._STATE_KEYS}
         else:
@@ -391,7 +406,8 @@ class VecEnv2DAirfoil:
             rows = [int(np.flatnonzero(self.airfoil == a)[0]) if (self.airfoil == a).any() else 0 for a in range(self.A)]
             ri = torch.tensor(rows, dtype=torch.long, device=self.device)
             self._init_cache = dict(h={k: a[rows].copy() for k, a in self.h.items()}, u=self.u[ri].contiguous(),
-                                    p=self.p[ri].contiguous(), drags=self.new_drags[rows].copy(), lifts=self.new_lifts[rows].copy())
+                                    p=self.p[ri].contiguous(), drags=self.new_drags[rows].copy(), lifts=self.new_lifts[rows].copy(),
+                                    quality=self.mesh_quality[rows].copy(), quality_cell=self.quality_cell[rows].copy())
             if self.gpu_topology:
                 self._init_cache["dev"] = {k: self.dtopo.t[k][ri].contiguous() for k in self._STATE_KEYS}
         return self.get_state()
@@ -426,6 +442,8 @@ class VecEnv2DAirfoil:
             self.h[k][idx] = self._cached(c["h"][k], idx)
         self.new_drags[idx] = self._cached(c["drags"], idx)
         self.new_lifts[idx] = self._cached(c["lifts"], idx)
+        self.mesh_quality[idx] = self._cached(c["quality"], idx)
+        self.quality_cell[idx] = self._cached(c["quality_cell"], idx)
         # device side: ONE launch restores the rows of every tensor (a dozen index_put launches otherwise).  The
         # argument arrays are built once; only the two per-step buffers (u, p) change their addresses.
         ra = self._restore_arg_arrays()
@@ -548,6 +566,9 @@ class VecEnv2DAirfoil:
                                              lift.data_ptr(), _lib.stream_ptr()), "mdq_probe_forces")
         self.u, self.p, self._coords_dev = out_u, out_p, t_coords
         self._dev_drag, self._dev_lift = drag, lift
+        if self.quality.on:     # ONE launch on the smoothed meshes of this step, either topology engine (off: no launch)
+            t_cells = dt.cells if self.gpu_topology else up("cells", dev)
+            mesh_quality_gpu(t_coords, t_cells, keep["nv"], keep["nt"], out=(self._dev_quality, self._dev_qinfo))
         fd = fl = None
         if self.flow_overlap:
             if not defer_flow:                  # (deferred: the device-resident step hands over through mdq_env_finish)
@@ -568,8 +589,12 @@ class VecEnv2DAirfoil:
                 parts += [fd.reshape(-1).view(torch.int32), fl.reshape(-1).view(torch.int32)]
                 nflow = fd.numel()
             nf = 2 * B * self.S + 2 * nflow
+            if self.quality.on:     # (q_min, cot_max) per environment ride behind the forces, their cells behind the integers
+                parts.append(self._dev_quality.reshape(-1).view(torch.int32))
+                nf += 2 * B
+            tail = [self._dev_qinfo[:, 0].contiguous()] if self.quality.on else []
             packed = torch.cat(parts + [dt.status, dt.t["nsel"], dt.t["nedges"], dt.t["ne"], dt.t["coord_map"].reshape(-1),
-                                        dt.t["n_closest"].reshape(-1)])
+                                        dt.t["n_closest"].reshape(-1)] + tail)
             if self._packed_host is None or self._packed_host.numel() != packed.numel():
                 self._packed_host = torch.empty(packed.numel(), dtype=torch.int32, pin_memory=True)
             self._packed_host.copy_(packed, non_blocking=True)      # page-locked: the copy is queued behind the kernels
@@ -589,7 +614,7 @@ class VecEnv2DAirfoil:
             ints = packed[2 * nf:]
             if fshape is not None:
                 self.flow_drag = fl64[2 * B * self.S:2 * B * self.S + nflow].reshape(fshape).copy()
-                self.flow_lift = fl64[2 * B * self.S + nflow:].reshape(fshape).copy()
+                self.flow_lift = fl64[2 * B * self.S + nflow:2 * B * self.S + 2 * nflow].reshape(fshape).copy()
             self.new_drags = fl64[:B * self.S].reshape(B, self.S).copy()
             self.new_lifts = fl64[B * self.S:2 * B * self.S].reshape(B, self.S).copy()
             st = ints[:B]
@@ -599,11 +624,17 @@ class VecEnv2DAirfoil:
             h["nedges"][...] = ints[2 * B:3 * B]
             h["ne"][...] = ints[3 * B:4 * B]
             h["coord_map"][...] = ints[4 * B:4 * B + B * N].reshape(B, N)
-            h["n_closest"][...] = ints[4 * B + B * N:].reshape(B, N)
+            h["n_closest"][...] = ints[4 * B + B * N:4 * B + 2 * B * N].reshape(B, N)
+            if self.quality.on:
+                self.mesh_quality = fl64[nf - 2 * B:nf].reshape(B, 2).copy()
+                self.quality_cell = ints[4 * B + 2 * B * N:5 * B + 2 * B * N].copy()
         else:
             drag, lift = self._pending
             self.new_drags = drag.cpu().numpy().copy()
             self.new_lifts = lift.cpu().numpy().copy()
+            if self.quality.on:
+                self.mesh_quality = self._dev_quality.cpu().numpy().copy()
+                self.quality_cell = self._dev_qinfo[:, 0].cpu().numpy().copy()
         self._pending = None
 
     # ------------------------------------------------------------------
@@ -715,9 +746,13 @@ class VecEnv2DAirfoil:
         # (B, S) ground truth: every environment's own airfoil; the formula lives in reward.py
         rewards, dones, reasons = _reward.rewards(self.lift, self._gt_drag_env, self.new_drags, self.nv, self.initial_num_node, code,
                                                   self.steps, self.threshold, self.TIME_REWARD, self.goal_vertices, self.timesteps,
-                                                  self.NEGATIVE_REWARD, self._gt_lift_env, self.new_lifts)
+                                                  self.NEGATIVE_REWARD, self._gt_lift_env, self.new_lifts, qspec=self.quality,
+                                                  quality=self.mesh_quality, q_ref=self._q_ref_env)
         infos = dict(code=code, nv=self.nv.copy(), new_drags=self.new_drags.copy(), new_lifts=self.new_lifts.copy(),
                      reason=reasons)
+        if self.quality.on:      # the quality of the step's meshes (before any auto-reset), as the kernel measured it
+            infos.update(q_min=self.mesh_quality[:, 0].copy(), min_angle=_reward.min_angle_degrees(self.mesh_quality[:, 1]),
+                         quality_cell=self.quality_cell.copy())
         if self.flow_overlap:    # drag / lift of the re-solved flow of the PREVIOUS step's meshes (None at the first step)
             infos.update(flow_lag=1, flow_drag=None if prev_flow is None else prev_flow[0],
                          flow_lift=None if prev_flow is None else prev_flow[1])
@@ -764,7 +799,8 @@ class VecEnv2DAirfoil:
         terminal logic and the in-place resets are all kernels on the current stream (`mdq_env_act`, `mdq_remesh`,
         `mdq_smooth_fast_env`, `mdq_env_topology`, ..., `mdq_env_result`, `mdq_restore_rows_masked`).
         Same semantics as `steps` calls of `step()` (tested against it).  Returns dict(rewards (steps,B), dones,
-        actions, codes, nv, reasons - the bitmask of what ended a step, reward.REASON_*) - read back ONCE at the end, when the
+        actions, codes, nv, reasons - the bitmask of what ended a step, reward.REASON_*; with the mesh quality on also quality
+        (steps,B,2): q_min, cot_max) - read back ONCE at the end, when the
         host mirrors of the environments are refreshed too."""
         cur = torch.cuda.current_stream(self.device)
         if cur == torch.cuda.default_stream(self.device):
@@ -873,6 +909,9 @@ class VecEnv2DAirfoil:
                   # step counters: read by every workgroup of mdq_env_finish, written to the other array (si: the current one)
                   d_steps=[torch.from_numpy(self.steps.astype(np.int32)).to(dev), torch.empty(B, dtype=i32, device=dev)], si=0,
                   err=torch.zeros(1, dtype=i32, device=dev), reason=torch.empty((K, B), dtype=i32, device=dev))
+        if self.quality.on:     # (q_min, cot_max) of every step: the quality launch of step k writes row k
+            ro["quality"] = torch.empty((K, B, 2), dtype=torch.float64, device=dev)
+            ro["qinfo"] = torch.empty((K, B, 4), dtype=i32, device=dev)
         if self._gt_drag_dev is None:       # (A, S): row a = airfoil a
             self._gt_drag_dev = torch.from_numpy(np.ascontiguousarray(self.gt_drags, dtype=np.float64)).to(dev)
         if self.lift.on and self._gt_lift_dev is None:
@@ -890,7 +929,8 @@ class VecEnv2DAirfoil:
         Launches of a step (8 - the smoothing hands back inside its own launch; 14 in round 3): Q-forward (embedding, MLP head),
         `mdq_remesh_act` (action decoding + vertex removal), `mdq_smooth_fast_env`, `mdq_env_topology`,
         `mdq_interpolate_snapshots`, `mdq_probe_forces`, `mdq_env_finish` (reward / terminal logic, hand-over of the meshes
-        to the flow stream, in-place resets, node features of the next state)."""
+        to the flow stream, in-place resets, node features of the next state).  With the mesh-quality keys set a ninth,
+        `mdq_mesh_quality`, sits between `mdq_probe_forces` and `mdq_env_finish`; without them none is added."""
         dt, lib, B, N, S, k = self.dtopo, self.lib, self.B, self.N, self.S, ro["k"]
         if k >= ro["K"]:
             raise IndexError("rollout_step beyond the steps of rollout_begin")
@@ -921,6 +961,8 @@ class VecEnv2DAirfoil:
         # start; the leg starts on its stream behind both
         flow = self.flow if self.flow_overlap else None
         sparse = 0 if os.environ.get("MDQ_FULL_INTERP", "") == "1" else (1 if self.flow_steps > 0 else 2)
+        if self.quality.on:         # the quality launch inside `_refresh_launch` writes this step's row of the rollout's record
+            self._dev_quality, self._dev_qinfo = ro["quality"][k], ro["qinfo"][k]
         self._refresh_launch(readback=False, defer_flow=True, sparse=sparse, before_topology=flow.arm_handover if flow else None,
                              after_topology=flow.mesh_ready if flow else None)
         # ---- the end of the step in one launch
@@ -955,6 +997,9 @@ class VecEnv2DAirfoil:
             if self.lift.on:        # the lift part of the reward / accuracy stop (off: the tail stays zero, the drag-only step)
                 d.gt_lift = self._gt_lift_dev.data_ptr()
                 d.lift_weight, d.lift_threshold, d.lift_floor = self.lift.weight, self.lift.threshold, self.lift.floor
+            if self.quality.on:     # the quality part (off: the tail stays zero); q_ref [A], the row of the environment's airfoil
+                d.quality_ref = self._q_ref_dev.data_ptr()
+                d.quality_weight, d.min_quality, d.max_cot = self.quality.weight, self.quality.min_quality, self.quality.max_cot
         c = self._init_cache
         if c.get("x") is None:      # node features of the initial states (what an environment shows right after its reset)
             xi = torch.empty((self.A, N, 2 + 3 * S), dtype=torch.float32, device=self.device)
@@ -984,6 +1029,8 @@ class VecEnv2DAirfoil:
         d.new_drags = self._dev_drag.data_ptr()
         if self.lift.on:            # (the array the probe launch of this step wrote beside the drags)
             d.new_lifts = self._dev_lift.data_ptr()
+        if self.quality.on:         # (what the quality launch of this step wrote)
+            d.quality = self._dev_quality.data_ptr()
         d.reason = ro["reason"][k].data_ptr()
         d.code_in, d.code_out = ro["code_act"].data_ptr(), ro["code"][k].data_ptr()
         d.steps_in, d.steps_out = ro["d_steps"][ro["si"]].data_ptr(), ro["d_steps"][ro["si"] ^ 1].data_ptr()
@@ -1045,6 +1092,8 @@ class VecEnv2DAirfoil:
                  ("nv_steps", ro["nv"][:K]), ("reasons", ro["reason"][:K]), ("err", ro["err"]), ("nv", dt.nv), ("nt", dt.nt),
                  ("offset", dt.offset), ("steps", ro["d_steps"][ro["si"]]), ("drag", self._dev_drag), ("lift", self._dev_lift)]
         parts += [(k, dt.t[k]) for k in ("nsel", "nedges", "ne", "coord_map", "n_closest")]
+        if self.quality.on:
+            parts += [("quality", ro["quality"][:K]), ("qinfo", ro["qinfo"][:K])]
         if self.flow_steps > 0:
             parts.append(("flow_status", self.flow_status))        # (legs up to the previous step: the last one may still run)
             if self.flow.map_status is not None:
@@ -1065,6 +1114,10 @@ class VecEnv2DAirfoil:
             off += f.numel() + p_
         out = dict(rewards=got["rewards"], dones=got["dones"].astype(bool), actions=got["actions"], codes=got["codes"],
                    nv=got["nv_steps"], reasons=got["reasons"])
+        if self.quality.on:     # (K, B, 2): q_min, cot_max of every step's meshes, before any reset
+            out["quality"] = got["quality"]
+            if K:
+                self.mesh_quality, self.quality_cell = got["quality"][-1].copy(), got["qinfo"][-1][:, 0].copy()
         if int(got["err"][0]) != 0:
             raise _lib.MeshDQNHipError("topology kernel failed inside rollout_device")
         if K:               # a failed flow leg is an ERROR here, not a NaN in what the caller reads later
@@ -1077,6 +1130,8 @@ class VecEnv2DAirfoil:
         if last_done is not None and last_done.any():      # (restarted environments: the cached initial forces, like step())
             self.new_drags[last_done] = self._cached(self._init_cache["drags"], last_done)
             self.new_lifts[last_done] = self._cached(self._init_cache["lifts"], last_done)
+            self.mesh_quality[last_done] = self._cached(self._init_cache["quality"], last_done)
+            self.quality_cell[last_done] = self._cached(self._init_cache["quality_cell"], last_done)
             # ... and their interpolated snapshots: `mdq_env_finish` leaves them alone inside a rollout (every step
             # interpolates again before anything reads them); whoever reads the state after the LAST step - get_state(), a
             # host-driven step() - must find the initial fields in the rows of the environments that step reset

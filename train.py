@@ -93,7 +93,26 @@ def parser():
     ap.add_argument("--lift-threshold", type=float, default=None, metavar="T",
                     help="relative lift error that ends an episode (agent_params.lift_threshold); alone, a pure stop criterion "
                          "(W = 0)")
+    ap.add_argument("--quality-weight", type=float, default=None, metavar="WQ",
+                    help="weight of the mesh quality in the reward, (drag_reward [+ W lift_reward] + WQ quality_reward) / "
+                         "(1 [+ W] + WQ) with quality_reward = 2 min(q_min / q_min of the initial mesh, 1) - 1: the yaml key "
+                         "agent_params.quality_weight (not a reference key: its reward never looks at the cells)")
+    ap.add_argument("--min-quality", type=float, default=None, metavar="Q",
+                    help="smallest shape quality q in [0, 1) below which an episode ends (agent_params.min_quality; 0: no stop)")
+    ap.add_argument("--min-angle", type=float, default=None, metavar="DEG",
+                    help="smallest cell angle in degrees, in [0, 60), below which an episode ends (agent_params.min_angle; 0: no "
+                         "stop); any of the three switches the per-step quality launch on")
     return ap
+
+
+def quality_options(args, cfgs):
+    """--quality-weight / --min-quality / --min-angle written into agent_params of every config (the flags win over the
+    yaml keys) before the environments are built; meshdqn_amd/reward.py reads and validates them."""
+    for c in cfgs:
+        for key in ("quality_weight", "min_quality", "min_angle"):
+            v = getattr(args, key)
+            if v is not None:
+                c["agent_params"][key] = float(v)
 
 
 def lift_options(args, cfgs):
@@ -131,6 +150,7 @@ def main():
     torch.set_num_threads(1)   # (many-core hosts under a CPU quota: the CPU-side tensor ops are tiny, no intra-op pool)
     cfgs = [yaml.safe_load(open(path)) for path in args.config]
     lift_options(args, cfgs)
+    quality_options(args, cfgs)
     check_airfoil_configs(cfgs, mixed_flow=args.mixed_flow, mixed_inflow=args.mixed_inflow)     # (before any device work: a typo in a yaml ends the run here)
     cfg = cfgs[0]
     ctx = DistContext()
@@ -224,6 +244,10 @@ def main():
         for a, c in enumerate(cfgs[1:], 1):      # (several airfoils: config.yaml is airfoil 0's, config_<a>.yaml the others')
             yaml.safe_dump(c, open(os.path.join(args.save_dir, f"config_{a}.yaml"), "w"))
         print(f"ranks {ctx.world}: {args.steps} batched steps x {args.envs} envs/rank, mean reward {out['rewards'].mean():.4f}")
+        if "reasons" in out and out["reasons"].size:     # (device loop) what ended the episodes of this rank, by reason bit
+            names = {1: "drag", 2: "lift", 4: "vertex goal", 8: "failed step", 16: "step limit", 32: "mesh quality"}
+            ends = ", ".join(f"{n} {int((out['reasons'] & b != 0).sum())}" for b, n in names.items())
+            print(f"episode ends: {int((out['reasons'] != 0).sum())} ({ends})")
         if ctx.backend:
             print(f"process group: backend {ctx.backend}, {ctx.world} rank(s)")
     ctx.close()
