@@ -673,6 +673,45 @@ typedef struct mdq_adam_desc {
 } mdq_adam_desc;
 MDQ_API int mdq_adam_step(const mdq_adam_desc* d, void* stream);
 
+/*
+ * Target network and Double-DQN targets (Mnih et al. 2015, van Hasselt et al. 2016; no reference counterpart: its two
+ * networks swap roles every `target_update` steps and never exchange weights).  Appended within ABI 8.  Two launches of the
+ * optimiser chain around the unchanged learning step; all pointers device; no atomics, no device random numbers: results
+ * are run-to-run identical.
+ *
+ * mdq_double_q_select: q_online, q_target and q_sel are float [B][OUT], sel is int32 [B] and may be NULL.  Per row b, with
+ * best = -inf and j* = 0, for j = 0 .. OUT - 1 in this order: q_online[b][j] replaces the pair only if it is > best - the
+ * first maximum wins (torch.argmax; -0 and +0 are equal), a NaN is never selected, a row with nothing above -inf gives
+ * j* = 0.  Then
+ *     v = q_target[b][j*];   q_sel[b][c] = v for every c < OUT;   sel[b] = j*
+ * - the row is broadcast, so `max_j q_other[b][j]` of mdq_gcn_train_step in mode 0 with q_other = q_sel is exactly v: the
+ * target r + gamma nonfinal Q_target(s', argmax_a Q_online(s', a)) without a change to the learning step.  One launch, one
+ * wave per row, MDQ_DOUBLE_Q_ROWS rows per workgroup, any OUT >= 1.  q_online and q_target may be the same array (v is then
+ * the row's maximum).  B <= 0, OUT <= 0, a NULL among the three arrays and a q_sel that overlaps q_online or q_target are
+ * refused before any launch.
+ */
+#define MDQ_DOUBLE_Q_ROWS 4
+MDQ_API int mdq_double_q_select(int32_t B, int32_t OUT, const float* q_online, const float* q_target, float* q_sel,
+                        int32_t* sel, void* stream);
+
+/*
+ * mdq_target_update: the target network's parameters follow the online ones, up to 32 parameter tensors in one launch
+ * (tensor s: len[s] floats; the grid of mdq_adam_step).  tau == 1: dst[s][i] = src[s][i], the bits (NaN payloads and the
+ * sign of zero included).  Otherwise, with tf = (float) tau,
+ *     dst[s][i] = dst[s][i] + tf * (src[s][i] - dst[s][i])
+ * in three float operations, each rounded on its own (no fused multiply-add): a float32 restatement gives the same bits.
+ * n outside 1 .. 32, a NULL pointer or a negative len among the first n, a tau that is not finite or outside (0, 1] and
+ * dst[s] == src[s] are refused before any launch.
+ */
+typedef struct mdq_target_update_desc {
+  int32_t n, _pad;
+  float* dst[MDQ_GCN_PACK_MAX];
+  const float* src[MDQ_GCN_PACK_MAX];
+  int32_t len[MDQ_GCN_PACK_MAX];
+  double tau;                 /* in (0, 1] */
+} mdq_target_update_desc;
+MDQ_API int mdq_target_update(const mdq_target_update_desc* d, void* stream);
+
 /* Up to 8 buffer copies in one launch (no reference counterpart; the env step hands its meshes and the warm-start fields
  * to the flow engine with it): buffer t = rows[t] rows of row_bytes[t] bytes, consecutive rows src_stride_bytes[t] /
  * dst_stride_bytes[t] apart (all multiples of 4, pointers 4-byte aligned; device pointers, host arrays of them). */

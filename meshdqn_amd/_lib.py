@@ -164,6 +164,15 @@ class ReplayNstepDesc(C.Structure):
                 ("steps", C.c_void_p)]
 
 
+DOUBLE_Q_ROWS = 4  # MDQ_DOUBLE_Q_ROWS: rows per workgroup of mdq_double_q_select
+
+
+class TargetUpdateDesc(C.Structure):
+    """Mirror of `mdq_target_update_desc` (appended within ABI 8)."""
+    _fields_ = [("n", C.c_int32), ("_pad", C.c_int32), ("dst", C.c_void_p * PACK_MAX), ("src", C.c_void_p * PACK_MAX),
+                ("len", C.c_int32 * PACK_MAX), ("tau", C.c_double)]
+
+
 # every symbol include/meshdqn_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mdq_abi_version": (C.c_int, []),
@@ -257,6 +266,8 @@ SYMBOLS = {
     "mdq_replay_prio_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p]),
     "mdq_adam_step": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mdq_double_q_select": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mdq_target_update": (C.c_int, [C.POINTER(TargetUpdateDesc), C.c_void_p]),
     "mdq_spin": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
     "mdq_stream_create_cu_mask": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "mdq_stream_destroy": (C.c_int, [C.c_void_p]),

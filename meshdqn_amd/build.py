@@ -42,6 +42,7 @@ UNITS = {
     "tilemaps": ("mdq_tilemaps.hip", [], []),
     "gcn": ("mdq_tu_gcn.hip", [], ["mdq_gcn.hip", "mdq_gcn_train.hip"]),
     "replay": ("mdq_replay.hip", [], []),
+    "target": ("mdq_target.hip", [], []),
     "mesh": ("mdq_mesh.hip", [], []),
     "smooth": ("mdq_tu_smooth.hip", [], ["mdq_smooth_shared.hip", "mdq_smooth_big.hip", "mdq_smooth.hip", "mdq_smooth_linear.hip"]),
     "topology": ("mdq_topology.hip", [], []),

@@ -88,6 +88,14 @@ def _refuse_n_step(trainer, loop: str):
                          "(DQNTrainer(n_step=...)) needs train_loop_device")
 
 
+def _refuse_target_net(trainer, what: str):
+    """The target network's selection and refresh are launches of the device loop's optimiser chain; the host paths restate
+    the reference's toggle, in which policy_net_2 is a second learner and not a copy."""
+    if trainer.target_net is not None:
+        raise ValueError(f"{what} restates the reference's toggle between two learners: a trainer with a target network "
+                         "(DQNTrainer(target_net=...)) needs train_loop_device")
+
+
 def _draw_epsilon(steps_done, n_actions: int, eps_start, eps_end, eps_decay):
     """Host random numbers of one batched step (both batched loops): epsilon per env, who explores, the random actions."""
     eps = eps_end + (eps_start - eps_end) * np.exp(-1.0 * steps_done / eps_decay)
@@ -125,6 +133,7 @@ def train_loop_per_worker(trainer: DQNTrainer, env_factory, num_episodes: int, m
     seeds), hence the loop must be bounded by `max_steps` (episodes are then cut at that common step count)."""
     _refuse_prioritized(trainer, "train_loop_per_worker")
     _refuse_n_step(trainer, "train_loop_per_worker")
+    _refuse_target_net(trainer, "train_loop_per_worker")
     ctx = trainer.ctx
     if ctx.world > 1 and max_steps is None:
         raise ValueError("train_loop_per_worker with more than one rank needs max_steps (a step count common to all "
@@ -185,6 +194,7 @@ def train_loop_vec(trainer: DQNTrainer, venv, num_steps: int, optim_per_step: in
     Returns dict(rewards (num_steps,B), dones, losses, steps_done)."""
     _refuse_prioritized(trainer, "train_loop_vec")
     _refuse_n_step(trainer, "train_loop_vec")
+    _refuse_target_net(trainer, "train_loop_vec")
     ctx = trainer.ctx
     B, N = venv.B, venv.N
     fused = FusedGcn(trainer.policy_net_1)
@@ -281,7 +291,7 @@ def train_loop_vec(trainer: DQNTrainer, venv, num_steps: int, optim_per_step: in
 def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step: int = 1, eps_decay=10000, eps_start=1.0,
                       eps_end=0.01, share_replay=False, log: Optional["TrainingLog"] = None, steps_done0=None, every: int = 0,
                       on_every=None, chunk: int = 64, optimiser_stream: str = "auto", per_trace: bool = False,
-                      nstep_trace: bool = False):
+                      nstep_trace: bool = False, target_trace: bool = False):
     """`train_loop_vec` WITHOUT a host round trip inside a batched step (one rank of configs[3]): the environment step is
     `VecEnv2DAirfoil.rollout_step` (Q-forward, epsilon-greedy choice, vertex removal ... reward / reset logic as kernels),
     the B transitions go into the record ring with one launch (`mdq_replay_step`; with `share_replay` the ranks
@@ -310,12 +320,22 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
     writer of the ring on it; with `share_replay` the all-gather of group t - 1 precedes the minibatches on the optimiser
     stream itself.  So every record a walk can reach (the groups of steps t - G + 1 .. t - 1) is finished and stable while
     the walk reads it.  `nstep_trace=True` (refused for n_step = 1) adds out["nstep"]: `idx`, `reward`, `nonfinal`, `steps`
-    (minibatches, batch) and `head` (minibatches,), the first record of the head group, read back like the `per` trace."""
+    (minibatches, batch) and `head` (minibatches,), the first record of the head group, read back like the `per` trace.
+
+    With `DQNTrainer(target_net=...)` policy_net_1 is the one online network and policy_net_2 its target (see
+    `optimize_device`): one more forward and the select launch (kind "double") in front of the learning step, and every
+    `period` gradient steps the target update behind `mdq_adam_step`, all on the optimiser stream.  No new stream or event:
+    the train-role copies of both networks are repacked on that stream, in order with the kernels that write the
+    parameters; the acting copy belongs to policy_net_1 and follows it as before.  `target_trace=True` (kind "double" only)
+    adds out["target"]: `sel` (int32) and `value` (float32), (minibatches, batch): the action the online network chose in
+    every next state and the target network's value of it, read back like the `per` trace."""
     ctx = trainer.ctx
     dev = ctx.device
     per = trainer.prioritized
     if per_trace and per is None:
         raise ValueError("per_trace needs a trainer with prioritized replay")
+    if target_trace and (trainer.target_net is None or trainer.target_net["kind"] != "double"):
+        raise ValueError("target_trace needs a trainer with target_net kind 'double'")
     n_step = trainer.n_step
     if nstep_trace and n_step == 1:
         raise ValueError("nstep_trace needs a trainer with n_step > 1")
@@ -335,7 +355,8 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
             out = train_loop_device(trainer, venv, num_steps, optim_per_step=optim_per_step, eps_decay=eps_decay,
                                     eps_start=eps_start, eps_end=eps_end, share_replay=share_replay, log=log,
                                     steps_done0=steps_done0, every=every, on_every=on_every, chunk=chunk,
-                                    optimiser_stream=optimiser_stream, per_trace=per_trace, nstep_trace=nstep_trace)
+                                    optimiser_stream=optimiser_stream, per_trace=per_trace, nstep_trace=nstep_trace,
+                                    target_trace=target_trace)
         main.wait_stream(trainer._main_stream)
         return out
     if venv.flow_overlap and not same_stream(venv._calibrated_for, main):
@@ -358,6 +379,7 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
     ev_opt = rep = None
     trace = dict(u=[], idx=[], weight=[], td=[], beta=[])
     ntrace = dict(idx=[], reward=[], nonfinal=[], steps=[], head=[])
+    ttrace = dict(sel=[], value=[])
     rewards, dones_hist, actions_hist, reasons_hist = [], [], [], []
     episodes = _EpisodeLog(log, venv)
     step_no, prev = 0, None      # prev: (record base, act, rew, done) of the step whose records await their next state
@@ -385,6 +407,9 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
                 shape = (loss_ring.numel(), trainer.batch_size)
                 ns_steps = torch.zeros(shape, dtype=torch.int32, device=dev)
                 ns_rew, ns_nf = torch.zeros(shape, device=dev), torch.zeros(shape, device=dev)
+            if target_trace:        # what the select launch chose, a row per minibatch of a chunk
+                shape = (loss_ring.numel(), trainer.batch_size)
+                tg_sel, tg_val = torch.zeros(shape, dtype=torch.int32, device=dev), torch.zeros(shape, device=dev)
         # minibatches of the chunk: the number of finished records at every step is known in advance; one upload
         if per is None:
             mbs = [rep.draw(t, trainer.batch_size) for t in range(t0 + step_no, t0 + step_no + K)
@@ -422,6 +447,8 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
                         allgather_records_into(ctx, rep.R, prev[0], B, W)
                     for _k in range(optim_per_step if do_opt else 0):
                         nkw = dict(head_step=t, steps_out=ns_steps[n_loss] if nstep_trace else None) if n_step > 1 else {}
+                        if target_trace:
+                            nkw.update(sel_out=tg_sel[n_loss], value_out=tg_val[n_loss])
                         if per is None:
                             trainer.optimize_device(rep, mb_dev[n_loss], loss_out=loss_ring[n_loss:n_loss + 1], **nkw)
                         else:
@@ -471,6 +498,9 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
             for key, ring in (("reward", ns_rew), ("nonfinal", ns_nf), ("steps", ns_steps)):
                 ntrace[key].append(ring[:n_loss].cpu().numpy())
             ntrace["head"].append(np.asarray(heads, np.int64))
+        if target_trace:
+            ttrace["sel"].append(tg_sel[:n_loss].cpu().numpy())
+            ttrace["value"].append(tg_val[:n_loss].cpu().numpy())
         for k in range(K):
             rew, done = out["rewards"][k], out["dones"][k]
             rewards.append(rew.copy())
@@ -490,4 +520,6 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
         out["per"] = {key: np.concatenate(v) if v else np.zeros(0) for key, v in trace.items()}
     if nstep_trace:
         out["nstep"] = {key: np.concatenate(v) if v else np.zeros(0) for key, v in ntrace.items()}
+    if target_trace:
+        out["target"] = {key: np.concatenate(v) if v else np.zeros(0) for key, v in ttrace.items()}
     return out

@@ -34,15 +34,18 @@ from .gcn_fused import fused_of
 from .replay import (DeviceBatch, DeviceReplay, ReplayMemory, SharedDeviceReplay, StateRef, Transition,  # noqa: F401
                      gather_state_refs, pack_transitions, pack_transitions_device, state_refs, state_to_data_list,
                      unpack_transitions)
-from .train_loops import TrainingLog, epsilon_threshold, train_loop_device, train_loop_per_worker, train_loop_vec  # noqa: F401
+from .train_loops import (TrainingLog, _refuse_target_net, epsilon_threshold, train_loop_device,  # noqa: F401
+                          train_loop_per_worker, train_loop_vec)
 
 
 class DQNTrainer:
     def __init__(self, n_actions: int, num_inputs: int, ctx: Optional[DistContext] = None, lr=1e-5, weight_decay=1e-6,
                  batch_size=32, gamma=1.0, target_update=50, replay_capacity=10000, conv_width=128, topk=0.1,
-                 seed=1370, dense: bool = True, e_max: int = 1536, prioritized: Optional[dict] = None, n_step: int = 1):
+                 seed=1370, dense: bool = True, e_max: int = 1536, prioritized: Optional[dict] = None, n_step: int = 1,
+                 target_net: Optional[dict] = None):
         self.prioritized = self._check_prioritized(prioritized, batch_size)
         self.n_step = self._check_n_step(n_step)           # a constructor option like `prioritized`: not checkpointed
+        self.target_net = self._check_target_net(target_net, target_update)     # ... and so is this one
         self.ctx = ctx or DistContext()
         self.dense, self.e_max = bool(dense), int(e_max)   # static-shape autograd path for equal-sized graphs
         dev = self.ctx.device
@@ -55,6 +58,10 @@ class DQNTrainer:
         self.policy_net_2.set_num_nodes(num_inputs)
         self.policy_net_1.to(dev)
         self.policy_net_2.to(dev)
+        if self.target_net is not None:
+            # both networks were constructed in the default trainer's order (policy_net_1 has its bits from the same seed);
+            # the target starts as a copy of the online network.  A later `load()` keeps whatever the checkpoint holds.
+            self.policy_net_2.load_state_dict(self.policy_net_1.state_dict())
         self.n_actions, self.batch_size, self.gamma, self.target_update = n_actions, batch_size, gamma, target_update
         # (torch's fused=True Adam measured 4x slower than the foreach implementation on this ROCm build)
         self.opts = [torch.optim.Adam(n.parameters(), lr=lr, weight_decay=weight_decay)
@@ -71,6 +78,7 @@ class DQNTrainer:
         # the device learner's lazily built state: streams of the loops (`train_loop_vec` / `train_loop_device`) and what
         # the optimiser stream was calibrated against, flat Adam moments per network, minibatch buffers of `optimize_device`
         self._opt_stream = self._main_stream = self._opt_calibrated_for = self._adam = self._mb_bufs = None
+        self._target_desc = None    # descriptor of `mdq_target_update` (policy_net_2 <- policy_net_1), built on first use
         self.opt_calibration_ms: List[float] = []
         random.seed(seed + self.ctx.rank)
         np.random.seed(seed + self.ctx.rank)
@@ -116,6 +124,36 @@ class DQNTrainer:
         if not 1 <= int(n_step) <= cls.N_STEP_MAX:
             raise ValueError(f"n_step: {n_step} outside 1 .. {cls.N_STEP_MAX} (the walk of mdq_replay_sample_nstep)")
         return int(n_step)
+
+    # --- target network and Double-DQN targets (`train_loop_device` only: two launches of the optimiser chain) ------
+    TARGET_NET_KINDS = ("double", "max")
+
+    @classmethod
+    def _check_target_net(cls, target_net, target_update) -> Optional[dict]:
+        """None (the reference's toggle: the two networks swap roles every `target_update` steps and never exchange
+        weights), or the complete option dict: policy_net_1 is the one online network, trained on every step, and
+        policy_net_2 a copy of it that follows every `period` gradient steps, by a copy (tau 1) or Polyak averaging
+        (target += tau (online - target)).  kind "double": r + gamma^m Q_target(s', argmax_a Q_online(s', a)) (van Hasselt
+        et al. 2016); "max": r + gamma^m max_a Q_target(s', a) (Mnih et al. 2015)."""
+        if target_net is None:
+            return None
+        known = ("kind", "period", "tau")
+        if not isinstance(target_net, dict):
+            raise ValueError("target_net: None or a dict with any of " + ", ".join(known))
+        unknown = sorted(set(target_net) - set(known), key=repr)
+        if unknown:
+            raise ValueError(f"target_net: unknown option(s) {unknown}; known: " + ", ".join(known))
+        kind = target_net.get("kind", "double")
+        if not isinstance(kind, str) or kind not in cls.TARGET_NET_KINDS:
+            raise ValueError(f"target_net: kind {kind!r} is none of " + ", ".join(cls.TARGET_NET_KINDS))
+        period = target_net.get("period", target_update)
+        if isinstance(period, bool) or not isinstance(period, (int, np.integer)) or int(period) < 1:
+            raise ValueError(f"target_net: period must be an integer >= 1, not {period!r}")
+        tau = target_net.get("tau", 1.0)
+        if isinstance(tau, bool) or not isinstance(tau, (int, float, np.integer, np.floating)) or \
+                not (np.isfinite(tau) and 0.0 < float(tau) <= 1.0):
+            raise ValueError(f"target_net: tau must lie in (0, 1], not {tau!r}")
+        return dict(kind=kind, period=int(period), tau=float(tau))
 
     def beta(self, g: Optional[int] = None) -> float:
         """Importance-weight exponent after g gradient applications (`num_grads`, which is checkpointed: a restart
@@ -289,6 +327,7 @@ class DQNTrainer:
     def optimize(self, transitions: Optional[List[Transition]] = None):
         """One optimiser step (airfoil_dqn.py:315-340 + :184-200 + :286-310): local loss/backward, ONE flat
         all-reduce of the gradient over all ranks, identical Adam step on every rank."""
+        _refuse_target_net(self, "optimize")
         if transitions is None:
             mem = self.device_memory if self.device_memory is not None else self.memory
             if mem.size() < self.batch_size:
@@ -396,7 +435,8 @@ class DQNTrainer:
         = the current one, and its flow stream): like `VecEnv2DAirfoil.calibrate_streams` - HIP's stream -> hardware queue
         mapping leaves pairs that overlap only partly, and the learning loop then runs at 2.6 instead of 1.95 ms per
         batched step.  Every candidate carries a stand-in chain (fused forward of one network + `mdq_gcn_train_step` of
-        the other on a fixed random minibatch: the kernels of `optimize_device`, no parameter is changed) through a few
+        the other on a fixed random minibatch, with `target_net` kind "double" also the second forward and the select
+        launch: the kernels of `optimize_device`, no parameter is changed) through a few
         real env steps with the loop's own synchronisation; the fastest stays.  The environments are reset afterwards."""
         dev = self.ctx.device
         main = torch.cuda.current_stream(dev)
@@ -426,6 +466,8 @@ class DQNTrainer:
         f1, f2 = self._fused_of(self.policy_net_1, "train"), self._fused_of(self.policy_net_2, "train")
         f1._pack()
         f2._pack()
+        double = self.target_net is not None and self.target_net["kind"] == "double"
+        q_sel = torch.zeros((mb, self.n_actions + 1), dtype=torch.float32, device=dev) if double else None
         rng = np.random.default_rng(977)
 
         def timed(cand, k):
@@ -439,6 +481,12 @@ class DQNTrainer:
                 with torch.cuda.stream(cand):
                     cand.wait_event(ev)
                     qo = f2.forward_arrays(x, node_ptr, esrc, edst, edge_ptr, N, EM)
+                    if double:      # the chain that will run: the online network's forward and the select launch as well
+                        q_on = f1.forward_arrays(x, node_ptr, esrc, edst, edge_ptr, N, EM)
+                        _lib.check(_lib.load().mdq_double_q_select(mb, q_sel.shape[1], q_on.data_ptr(), qo.data_ptr(),
+                                                                   q_sel.data_ptr(), None, _lib.stream_ptr()),
+                                   "mdq_double_q_select")
+                        qo = q_sel
                     f1.train_step(x, node_ptr, esrc, edst, edge_ptr, N, EM, 0, qo, action, reward, nonfinal, self.gamma)
                 venv.rollout_step(ro, fused_act)
             main.wait_stream(cand)
@@ -462,7 +510,8 @@ class DQNTrainer:
 
     def optimize_device(self, rep: "SharedDeviceReplay", idx, loss_out: Optional[torch.Tensor] = None,
                         weight: Optional[torch.Tensor] = None, td_out: Optional[torch.Tensor] = None,
-                        head_step: Optional[int] = None, steps_out: Optional[torch.Tensor] = None):
+                        head_step: Optional[int] = None, steps_out: Optional[torch.Tensor] = None,
+                        sel_out: Optional[torch.Tensor] = None, value_out: Optional[torch.Tensor] = None):
         """One optimiser step on a minibatch of the record ring WITHOUT host synchronisation and without autograd:
         `mdq_replay_sample` (records `idx` -> graph arrays), fused forward of the network without gradient,
         `mdq_gcn_train_step` of the other one (forward + double-DQN Huber loss + backward), ONE flat all-reduce over the
@@ -474,13 +523,24 @@ class DQNTrainer:
         A trainer with `n_step` > 1 samples with `mdq_replay_sample_nstep` instead: the reward becomes the discounted sum over
         the walk from every drawn record, s' the state the walk ends in, and `nonfinal` carries gamma^(m-1), which the
         unchanged learning step multiplies by gamma.  `head_step` (required then): the batched step t whose group is being
-        written, which no walk enters (`rep.group_base(t)`); `steps_out`: (batch,) int32 device tensor for the lengths m."""
+        written, which no walk enters (`rep.group_base(t)`); `steps_out`: (batch,) int32 device tensor for the lengths m.
+
+        A trainer with `target_net` never toggles: policy_net_1 is trained on every step (mode 0) against policy_net_2, the
+        target.  The chain becomes: the sampling launch, the fused forward of the target on the next states (q_t), for kind
+        "double" the fused forward of the online network on the same graphs (q_o) and `mdq_double_q_select` (q_o, q_t) ->
+        a row per graph whose maximum is Q_target(s', argmax_a Q_online(s', a)), the unchanged learning step with that as
+        `q_other`, the all-reduce, `mdq_adam_step`, and every `period` gradient steps `mdq_target_update` (target <- online,
+        `tau`) on the same stream.  Every rank runs the same update on identical replicas: no collective.  `sel_out` /
+        `value_out` (kind "double"): (batch,) int32 / float32 device tensors that receive the chosen action and that value."""
         dev = self.ctx.device
         if self.n_step > 1 and head_step is None:
             raise ValueError("optimize_device: a trainer with n_step > 1 needs head_step (the batched step being written)")
-        if (self.num_grads % self.target_update) == 0:
+        tn = self.target_net
+        if (sel_out is not None or value_out is not None) and (tn is None or tn["kind"] != "double"):
+            raise ValueError("optimize_device: sel_out / value_out need a trainer with target_net kind 'double'")
+        if tn is None and (self.num_grads % self.target_update) == 0:
             self.select = not self.select
-        sel = self.select
+        sel = True if tn is not None else self.select
         k = 0 if sel else 1
         net, other = ((self.policy_net_1, self.policy_net_2) if sel else (self.policy_net_2, self.policy_net_1))
         mb, N, F, EM = len(idx), rep.N, rep.F, rep.e_max
@@ -515,6 +575,8 @@ class DQNTrainer:
         gn = dict(x=b["x_n"], esrc=b["esrc_n"], edst=b["edst_n"], edge_ptr=b["edge_ptr_n"])
         go, gd = (gn, gs) if sel else (gs, gn)
         qo = self._fused_of(other, "train").forward_arrays(go["x"], b["node_ptr"], go["esrc"], go["edst"], go["edge_ptr"], N, EM)
+        if tn is not None and tn["kind"] == "double":
+            qo = self._double_q_select(net, go, b, qo, N, EM, sel_out, value_out)
         loss, flat = self._fused_of(net, "train").train_step(gd["x"], b["node_ptr"], gd["esrc"], gd["edst"], gd["edge_ptr"], N, EM,
                                                     0 if sel else 1, qo, b["action"], b["reward"], b["nonfinal"], self.gamma,
                                                     loss_out=loss_out, weight=weight, td_out=td_out)
@@ -522,7 +584,48 @@ class DQNTrainer:
             self.ctx.allreduce_mean_(flat)
         self._adam_step_device(k, flat)
         self.num_grads += 1
+        if tn is not None and self.num_grads % tn["period"] == 0:
+            self._target_update_device(tn["tau"])
         return loss
+
+    def _double_q_select(self, online, gn, b, q_t, N, EM, sel_out, value_out):
+        """The Double-DQN half of `optimize_device`: the online network's train-role forward on the next-state graphs `gn`,
+        then `mdq_double_q_select` -> the (batch, out) array whose row b holds q_t[b][argmax_j q_o[b][j]] in every column."""
+        q_o = self._fused_of(online, "train").forward_arrays(gn["x"], b["node_ptr"], gn["esrc"], gn["edst"], gn["edge_ptr"], N, EM)
+        q_sel = b.get("q_sel")
+        if q_sel is None or q_sel.shape != q_t.shape:
+            q_sel = b["q_sel"] = torch.zeros_like(q_t)
+        mb, out_dim = q_t.shape
+        for t, dt in ((sel_out, torch.int32), (value_out, torch.float32)):
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != q_t.device or t.numel() != mb):
+                raise ValueError(f"optimize_device: sel_out / value_out must be contiguous int32 / float32 tensors of {mb} "
+                                 f"entries on {q_t.device}")
+        _lib.check(_lib.load().mdq_double_q_select(mb, out_dim, q_o.data_ptr(), q_t.data_ptr(), q_sel.data_ptr(),
+                                                   None if sel_out is None else sel_out.data_ptr(), _lib.stream_ptr()),
+                   "mdq_double_q_select")
+        if value_out is not None:
+            value_out.copy_(q_sel[:, 0])
+        return q_sel
+
+    def _target_update_device(self, tau: float):
+        """policy_net_2 <- policy_net_1 with ONE launch (`mdq_target_update`) on the current stream - the optimiser stream,
+        in order behind the `mdq_adam_step` that wrote the online parameters and in front of the target's next forward."""
+        src, dst = list(self.policy_net_1.parameters()), list(self.policy_net_2.parameters())
+        d = self._target_desc
+        if d is None or any(d.src[i] != p.data_ptr() or d.dst[i] != q.data_ptr() for i, (p, q) in enumerate(zip(src, dst))):
+            if len(src) > _lib.PACK_MAX:
+                raise ValueError("too many parameter tensors for mdq_target_update")
+            d = self._target_desc = _lib.TargetUpdateDesc()
+            d.n = len(src)
+            for i, (p, q) in enumerate(zip(src, dst)):
+                if p.shape != q.shape or p.dtype != torch.float32 or q.dtype != torch.float32 or \
+                        not (p.is_contiguous() and q.is_contiguous()):
+                    raise ValueError("mdq_target_update needs contiguous float32 parameters of equal shapes")
+                d.src[i], d.dst[i], d.len[i] = p.data_ptr(), q.data_ptr(), p.numel()
+        d.tau = float(tau)
+        _lib.check(_lib.load().mdq_target_update(C.byref(d), _lib.stream_ptr()), "mdq_target_update")
+        # the kernel wrote the parameters behind torch's back: the packed copies of the target repack before their next forward
+        self.policy_net_2._mdq_version = getattr(self.policy_net_2, "_mdq_version", 0) + 1
 
     def save(self, save_dir, prefix="", extra: Optional[dict] = None):
         """`ParameterServer.write` (airfoil_dqn.py:214-218): PyG-keyed state dicts `{prefix}policy_net_{1,2}.pt`, plus

@@ -46,6 +46,28 @@ def n_step_option(flag, cfg: dict) -> int:
     return n
 
 
+def target_options(args, cfg: dict):
+    """The `target_net` argument of `DQNTrainer` from --target-net / --target-tau / --target-period and the optional
+    top-level yaml block `target_net: {kind: double, tau: 1.0, period: 50}` (not a reference section: its two networks swap
+    roles and never exchange weights).  None: the reference's toggle.  The block alone switches the option on; every flag
+    wins over the block's key; --target-tau / --target-period without a kind from either side: an error."""
+    block = cfg.get("target_net")
+    if block is not None and not isinstance(block, dict):
+        raise SystemExit(f"target_net: a block with any of kind, tau, period, not {block!r}")
+    opt = dict(block or {})
+    unknown = sorted(set(opt) - {"kind", "tau", "period"}, key=repr)
+    if unknown:
+        raise SystemExit(f"target_net: unknown key(s) {unknown} (known: kind, tau, period)")
+    for key, flag in (("kind", args.target_net), ("tau", args.target_tau), ("period", args.target_period)):
+        if flag is not None:
+            opt[key] = flag
+    if block is None and args.target_net is None:
+        if opt:
+            raise SystemExit("--target-tau / --target-period need --target-net {max,double} or a yaml block target_net:")
+        return None
+    return opt
+
+
 def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True, action="append",
@@ -86,6 +108,15 @@ def parser():
                     help="n-step returns in the device-resident loop, 1 .. 64 (the n-step transition of every drawn record is "
                          "composed from the record ring inside the sampling launch); also the yaml key replay: {n_step: N}; "
                          "default 1")
+    ap.add_argument("--target-net", choices=("max", "double"), default=None,
+                    help="a target network in the device-resident loop: policy_net_1 is trained on every step, policy_net_2 is "
+                         "its copy, refreshed every --target-period gradient steps; double: Double-DQN targets "
+                         "Q_target(s', argmax_a Q_online(s', a)), max: max_a Q_target(s', a); also the yaml block "
+                         "target_net: {kind: double, tau: 1.0, period: 50}; default: the reference's toggle")
+    ap.add_argument("--target-tau", type=float, default=None, metavar="T",
+                    help="Polyak factor of the target refresh in (0, 1], target += T (online - target); default 1: a copy")
+    ap.add_argument("--target-period", type=int, default=None, metavar="P",
+                    help="gradient steps between two refreshes of the target network; default: agent_params.target_update")
     ap.add_argument("--lift-weight", type=float, default=None, metavar="W",
                     help="weight of the lift in the reward, (drag_reward + W lift_reward) / (1 + W): the yaml key "
                          "agent_params.lift_weight (not a reference key: its reward reads the drag only); alone, the lift also "
@@ -161,7 +192,8 @@ def main():
                          ctx=ctx, lr=float(opt.get("lr", 1e-5)), weight_decay=float(opt.get("weight_decay", 1e-6)),
                          batch_size=int(opt.get("batch_size", 32)), gamma=float(eps.get("gamma", 1.0)),
                          target_update=int(ap_.get("target_update", 50)),
-                         prioritized=prioritized_options(args.prioritized_replay, cfg), n_step=n_step_option(args.n_step, cfg))
+                         prioritized=prioritized_options(args.prioritized_replay, cfg), n_step=n_step_option(args.n_step, cfg),
+                         target_net=target_options(args, cfg))
     # restart chain: restart n reads the checkpoint with n - 1 "restart_" prefixes and writes with n (every rank loads the
     # same files, so the replicas stay identical)
     restart_num, steps_done0 = 0, None
@@ -198,6 +230,8 @@ def main():
         raise SystemExit("prioritized replay needs the device-resident loop (a GPU, the device mesh engine, no --host-loop)")
     if trainer.n_step > 1 and not device_loop:
         raise SystemExit("n-step returns need the device-resident loop (a GPU, the device mesh engine, no --host-loop)")
+    if trainer.target_net is not None and not device_loop:
+        raise SystemExit("a target network needs the device-resident loop (a GPU, the device mesh engine, no --host-loop)")
     loop = train_loop_device if device_loop else train_loop_vec
     kw, every, on_every = {}, args.save_every, checkpoint
     if args.digest:
