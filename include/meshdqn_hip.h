@@ -660,7 +660,17 @@ MDQ_API int mdq_replay_prio_update(float* prio, int32_t capacity, int32_t n, con
 /*
  * torch.optim.Adam.step (amsgrad False; weight decay added to the gradient) for up to 32 parameter tensors in one
  * launch: segment s updates param[s][0..len[s]) from grad / exp_avg / exp_avg_sq [offset[s] ..] (flat buffers laid out
- * like the flat gradient).  bias_correction{1,2} = 1 - beta{1,2}^step, computed by the caller.
+ * like the flat gradient).  bias_correction{1,2} = 1 - beta{1,2}^step, computed by the caller.  Per element, in float:
+ *     g' = g + wd p  (only if wd != 0);   m' = m + w1 (g' - m);   v' = b2 v + w2 (g' g');
+ *     p' = p - lr_c (m' / (sqrt(v') / bc2s + eps))
+ * with w1 = 1 - beta1, w2 = 1 - beta2, lr_c = lr / bias_correction1 and bc2s = sqrt(bias_correction2) formed in double and
+ * rounded once to float (as torch forms them), and b2, eps, wd the doubles rounded once.  The operations are the ones above
+ * in that order; a product and the sum that takes it may be contracted into one fused multiply-add, sqrt and the divisions
+ * are correctly rounded.  grad is only read; nothing outside the n segments is written.  A segment with len 0 is skipped
+ * whatever its pointer.  Refused before any launch (nonzero return, mdq_last_error names mdq_adam_step and the field): n
+ * outside 1 .. 32; grad, exp_avg or exp_avg_sq NULL; among the first n segments a negative len, a negative offset, offset +
+ * len beyond int32, or param NULL where len > 0; lr, eps or weight_decay negative or not finite; beta1 or beta2 outside
+ * [0, 1); bias_correction1 or bias_correction2 outside (0, 1].
  */
 typedef struct mdq_adam_desc {
   int32_t n, _pad;

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 
 #include "../../include/meshdqn_hip.h"
 #include "mdq_internal.h"
@@ -210,13 +211,15 @@ __global__ __launch_bounds__(256) void adam_kernel(mdq_adam_desc D) {
   float* p = D.param[s];
   const int len = D.len[s], off = D.offset[s];
   const float lr_c = (float)(D.lr / D.bias_correction1), bc2s = (float)sqrt(D.bias_correction2);
-  const float b1 = (float)D.beta1, b2 = (float)D.beta2, eps = (float)D.eps, wd = (float)D.weight_decay;
+  const float b2 = (float)D.beta2, eps = (float)D.eps, wd = (float)D.weight_decay;
+  // the weights as torch forms them: 1 - beta in double, rounded once (1.f - (float)beta2 is off by 1.3e-5 of itself)
+  const float w1 = (float)(1.0 - D.beta1), w2 = (float)(1.0 - D.beta2);
   for (int i = blockIdx.x * 256 + threadIdx.x; i < len; i += gridDim.x * 256) {
     float g = D.grad[off + i];
     const float w = p[i];
     if (wd != 0.f) g = fmaf(wd, w, g);
-    const float m = D.exp_avg[off + i] + (1.f - b1) * (g - D.exp_avg[off + i]);      // lerp, as torch does
-    const float v = b2 * D.exp_avg_sq[off + i] + (1.f - b2) * (g * g);
+    const float m = D.exp_avg[off + i] + w1 * (g - D.exp_avg[off + i]);      // lerp, as torch does
+    const float v = b2 * D.exp_avg_sq[off + i] + w2 * (g * g);
     D.exp_avg[off + i] = m;
     D.exp_avg_sq[off + i] = v;
     p[i] = w - lr_c * (m / (sqrtf(v) / bc2s + eps));
@@ -263,8 +266,27 @@ extern "C" int mdq_replay_sample_nstep(const mdq_replay_sample_desc* d, const md
 extern "C" int mdq_replay_sample(const mdq_replay_sample_desc* d, void* stream) { return mdq_replay_sample_nstep(d, nullptr, stream); }
 
 extern "C" int mdq_adam_step(const mdq_adam_desc* d, void* stream) {
-  if (!d || d->n <= 0 || d->n > MDQ_GCN_PACK_MAX || !d->grad || !d->exp_avg || !d->exp_avg_sq)
-    return mdq_set_error("mdq_adam_step: bad arguments");
+  if (!d) return mdq_set_error("mdq_adam_step: NULL descriptor");
+  if (d->n < 1 || d->n > MDQ_GCN_PACK_MAX) return mdq_set_error("mdq_adam_step: n outside 1 .. 32");
+  if (!d->grad) return mdq_set_error("mdq_adam_step: grad is NULL");
+  if (!d->exp_avg) return mdq_set_error("mdq_adam_step: exp_avg is NULL");
+  if (!d->exp_avg_sq) return mdq_set_error("mdq_adam_step: exp_avg_sq is NULL");
+  for (int s = 0; s < d->n; ++s) {
+    if (d->len[s] < 0) return mdq_set_error("mdq_adam_step: negative len");
+    if (d->offset[s] < 0) return mdq_set_error("mdq_adam_step: negative offset");
+    if ((long long)d->offset[s] + d->len[s] > INT32_MAX) return mdq_set_error("mdq_adam_step: offset + len beyond int32");
+    if (d->len[s] > 0 && !d->param[s]) return mdq_set_error("mdq_adam_step: param is NULL where len > 0");
+  }
+  if (!std::isfinite(d->lr) || d->lr < 0.0) return mdq_set_error("mdq_adam_step: lr must be finite and not negative");
+  if (!std::isfinite(d->eps) || d->eps < 0.0) return mdq_set_error("mdq_adam_step: eps must be finite and not negative");
+  if (!std::isfinite(d->weight_decay) || d->weight_decay < 0.0)
+    return mdq_set_error("mdq_adam_step: weight_decay must be finite and not negative");
+  if (!(d->beta1 >= 0.0 && d->beta1 < 1.0)) return mdq_set_error("mdq_adam_step: beta1 outside [0, 1)");
+  if (!(d->beta2 >= 0.0 && d->beta2 < 1.0)) return mdq_set_error("mdq_adam_step: beta2 outside [0, 1)");
+  if (!(d->bias_correction1 > 0.0 && d->bias_correction1 <= 1.0))
+    return mdq_set_error("mdq_adam_step: bias_correction1 outside (0, 1]");
+  if (!(d->bias_correction2 > 0.0 && d->bias_correction2 <= 1.0))
+    return mdq_set_error("mdq_adam_step: bias_correction2 outside (0, 1]");
   hipLaunchKernelGGL(mdq_replay::adam_kernel, dim3(32, d->n), dim3(256), 0, (hipStream_t)stream, *d);
   if (hipGetLastError() != hipSuccess) return mdq_set_error("adam_kernel launch failed");
   return 0;

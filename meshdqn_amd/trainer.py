@@ -417,7 +417,7 @@ class DQNTrainer:
             opt.state[p_]["step"] += 1
         step = float(opt.state[a["params"][0]]["step"])
         d = a["desc"]
-        if any(d.param[i] != p_.data_ptr() for i, p_ in enumerate(a["params"][:1])):
+        if any(d.param[i] != p_.data_ptr() for i, p_ in enumerate(a["params"])):     # (any may be re-seated)
             for i, p_ in enumerate(a["params"]):
                 d.param[i] = p_.data_ptr()
         d.grad = flat.data_ptr()
