@@ -425,8 +425,9 @@ typedef struct mdq_gcn_level {
 typedef struct mdq_gcn_net {
   int32_t nlevels, C, fin0, out_dim;  /* conv/pool levels, conv width, input features, head outputs */
   double ratio;                       /* TopKPooling ratio */
-  int32_t softmax;                    /* 1: softmax over the head outputs (NodeRemovalNet) */
-  int32_t _pad;
+  int32_t softmax;                    /* 1: softmax over the head outputs (NodeRemovalNet, head "softmax") */
+  int32_t dueling;                    /* 1: dueling aggregation of the head outputs (see lin_v_w below); excludes softmax.
+                                         Both 0: the raw lin3 outputs (AirfoilGCNN; NodeRemovalNet, head "linear") */
   mdq_gcn_level levels[6];
   const float* lin1_w;   /* device [2C][128]  lin1.weight^T */
   const float* lin1_b;
@@ -434,6 +435,15 @@ typedef struct mdq_gcn_net {
   const float* lin2_b;
   const float* lin3_w;   /* device [64][out_dim] */
   const float* lin3_b;
+  /* optional, appended within ABI 8 (read only when dueling != 0): the value stream of the dueling head (Wang et al.
+     2016; not a reference feature).  With a2 = relu(lin2(relu(lin1(emb)))), A = lin3(a2) and v = lin_v_b + a2 . lin_v_w the
+     outputs of a graph are q_c = v + (A_c - mean_j A_j).  `dueling` takes the place of the padding word behind `softmax`
+     and the two pointers are the struct's last fields, so MDQ_ABI_VERSION stays 8: zero-initialised they mean what ABI 8
+     meant, and a caller that zero-initialises the descriptor (every ABI 8 caller must) and is rebuilt against this header
+     behaves as before; no entry point or exported symbol is added.  mdq_gcn_forward* and mdq_gcn_train_step* refuse, before
+     any launch, dueling together with softmax and dueling with either pointer NULL. */
+  const float* lin_v_w;  /* device [64]  lin_v.weight */
+  const float* lin_v_b;  /* device [1] */
 } mdq_gcn_net;
 
 /*
@@ -445,7 +455,7 @@ typedef struct mdq_gcn_net {
  *   esrc/edst device int32 [sum_edges]          edge end points, LOCAL node ids (0..n_g-1), j -> i
  *   edge_ptr device int32 [B+1]
  *   emb      device float [B][2C]  (out)        graph embeddings (x1+x2+...)
- *   out      device float [B][out_dim] (out)    head outputs (softmax probabilities if net.softmax)
+ *   out      device float [B][out_dim] (out)    head outputs (softmax probabilities if net.softmax, dueling q if net.dueling)
  *   NMAX / EMAX: upper bounds of nodes / edges per graph (sizes the LDS carve-up)
  */
 MDQ_API int mdq_gcn_forward(const mdq_gcn_net* net, int32_t B, int32_t NMAX, int32_t EMAX, const float* x,
@@ -478,7 +488,8 @@ typedef struct mdq_gcn_grad_layout {
   int32_t w_l[6], b[6], w_r[6], pool_w[6]; /* per level: lin_l.weight | lin.weight, lin_l.bias | bias, lin_r.weight (SAGE), pool weight */
   int32_t lin1_w, lin1_b, lin2_w, lin2_b, lin3_w, lin3_b;
   int32_t total;                           /* floats of the flat gradient (ALL parameters of the module) */
-  int32_t _pad;
+  int32_t lin_v;                           /* dueling head only (read when net.dueling != 0; took the place of the padding
+                                              word): offset of lin_v.weight [64], its bias sits at lin_v + 64 */
 } mdq_gcn_grad_layout;
 
 typedef struct mdq_gcn_train_desc {
@@ -513,6 +524,9 @@ MDQ_API int64_t mdq_gcn_train_workspace(const mdq_gcn_net* net, int32_t NMAX, in
  * `loss.backward()` in DataWorker.compute_gradients (airfoil_dqn.py:286-310) and the PyG backward passes of SAGEConv /
  * GCNConv / TopKPooling / global max + mean pool behind it.  One workgroup per graph (forward out of LDS, backward over
  * the rows TopKPooling kept), then a reduction of the per-graph gradients in graph order: bitwise reproducible.
+ * `out` of the formulas above is what the head puts out: probabilities (net.softmax), the raw lin3 outputs, or the dueling
+ * q = v + (A - mean A) (net.dueling).  Dueling backward, g = d loss / d q[j]: d A[c] = g ((c == j) - 1 / out_dim), d v = g;
+ * lin_v's gradient goes to layout.lin_v (weight, 64 floats) and layout.lin_v + 64 (bias), which must lie inside `total`.
  */
 MDQ_API int mdq_gcn_train_step(const mdq_gcn_net* net, const mdq_gcn_train_desc* d, void* stream);
 

@@ -216,9 +216,23 @@ class _WeightAccessors:
             off += n
 
 
+HEADS = ("softmax", "linear", "dueling")
+
+
+def check_head(head):
+    if head not in HEADS:
+        raise ValueError(f"head must be one of 'softmax', 'linear', 'dueling', not {head!r}")
+    return head
+
+
 class NodeRemovalNet(nn.Module, _WeightAccessors):
-    def __init__(self, output_dim, conv_width=64, topk=0.5, initial_num_nodes=None):
+    """`head` (not a reference feature) picks what the outputs of a graph are, with a2 = relu(lin2(relu(lin1(emb)))):
+    "softmax" (default, the reference's network): softmax(lin3(a2)); "linear": lin3(a2); "dueling" (Wang et al. 2016):
+    v + (A - mean(A)) with A = lin3(a2) and v = lin_v(a2), `lin_v = Linear(64, 1)` existing for this head only."""
+
+    def __init__(self, output_dim, conv_width=64, topk=0.5, initial_num_nodes=None, head="softmax"):
         super(NodeRemovalNet, self).__init__()
+        self.head = check_head(head)
         self.conv_width = conv_width
         self.topk = topk
         self.output_dim = output_dim
@@ -238,6 +252,8 @@ class NodeRemovalNet(nn.Module, _WeightAccessors):
         self.lin1 = torch.nn.Linear(2 * conv_width, 128)
         self.lin2 = torch.nn.Linear(128, 64)
         self.lin3 = torch.nn.Linear(64, output_dim)
+        if self.head == "dueling":   # (registered last: the last two entries of parameters() and of the state_dict)
+            self.lin_v = torch.nn.Linear(64, 1)
         torch.manual_seed(0)
         self.reset()
 
@@ -252,9 +268,18 @@ class NodeRemovalNet(nn.Module, _WeightAccessors):
             nn.init.xavier_normal_(conv.lin_r.weight, gain=0.9)
         for conv in (self.conv4, self.conv5, self.conv6):
             nn.init.xavier_normal_(conv.lin.weight, gain=0.9)
-        for lin in (self.lin1, self.lin2, self.lin3):
+        for lin in (self.lin1, self.lin2, self.lin3) + ((self.lin_v,) if self.head == "dueling" else ()):
             nn.init.xavier_normal_(lin.weight, gain=0.9)
             nn.init.normal_(lin.bias)
+
+    def _head_out(self, a2):
+        """The outputs of the graphs from their relu(lin2) rows."""
+        x = self.lin3(a2)
+        if self.head == "softmax":
+            return F.softmax(x, dim=1)  # pick which vertex to remove
+        if self.head == "dueling":
+            return self.lin_v(a2) + (x - x.mean(dim=1, keepdim=True))
+        return x
 
     def set_num_nodes(self, initial_num_nodes):
         """Re-creates conv1 with `initial_num_nodes` input features and default init (airfoilgcnn.py:78-80)."""
@@ -285,9 +310,7 @@ class NodeRemovalNet(nn.Module, _WeightAccessors):
         x = F.relu(self.lin1(x))
         x = F.dropout(x, p=0.0, training=self.training)
         x = F.relu(self.lin2(x))
-        x = self.lin3(x)
-        x = F.softmax(x, dim=1)  # pick which vertex to remove
-        return x
+        return self._head_out(x)
 
     def forward_fused(self, data):
         """Inference (no autograd) on the fused HIP kernels: one workgroup per graph, MFMA head."""
@@ -315,7 +338,7 @@ class NodeRemovalNet(nn.Module, _WeightAccessors):
             return x
         x = F.relu(self.lin1(x))
         x = F.relu(self.lin2(x))
-        return F.softmax(self.lin3(x), dim=1)
+        return self._head_out(x)
 
 
 def dense_batch(data_list, e_max: int, device=None):

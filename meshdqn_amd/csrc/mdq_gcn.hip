@@ -4,7 +4,7 @@
 // of LDS - CSR-by-target mean aggregation (SAGEConv), symmetric-normalised aggregation (GCNConv),
 // TopKPooling (tanh score, rank-by-counting top-k, edge filter + relabel), [max || mean] readouts -
 // and writes the 2C-wide graph embedding (sum of the per-level readouts).
-// Kernel 2 (mlp_head_kernel): the dense head lin1 -> relu -> lin2 -> relu -> lin3 (-> softmax),
+// Kernel 2 (mlp_head_kernel): the dense head lin1 -> relu -> lin2 -> relu -> lin3 (-> softmax | dueling aggregation),
 // batched over graphs on the matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 FMA chains).
 //
 // Restated semantics: airfoilgcnn.py:85-145 (NodeRemovalNet.forward), :170-209 (AirfoilGCNN.forward)
@@ -838,7 +838,8 @@ __device__ inline void head_layer(const float* in, int in_stride, int K, const f
 }
 
 template <int ROWS = 32, int NTH = WGH>
-__device__ __forceinline__ void head_store(const mdq_gcn_net& net, int B, int g0, const float* a3, int OUTP, float* out);
+__device__ __forceinline__ void head_store(const mdq_gcn_net& net, int B, int g0, const float* a3, int OUTP, const float* a2,
+                                           int a2s, float* out);
 
 __global__ __launch_bounds__(WGH) void mlp_head_kernel(mdq_gcn_net net, int B, const float* emb, float* out) {
   extern __shared__ __align__(16) float sm[];
@@ -861,7 +862,7 @@ __global__ __launch_bounds__(WGH) void mlp_head_kernel(mdq_gcn_net net, int B, c
   __syncthreads();
   head_layer(a2, 65, 64, net.lin3_w, net.lin3_b, OUT, a3, OUTP, false);
   __syncthreads();
-  head_store(net, B, g0, a3, OUTP, out);
+  head_store(net, B, g0, a3, OUTP, a2, 65, out);
 }
 
 // The same head for the reference's width (C = 128: 256 -> 128 -> 64 -> out_dim <= 256) with EVERY weight of a wave's
@@ -904,8 +905,14 @@ __device__ __forceinline__ void head_mma(const float* in, int in_stride, const f
   }
 }
 
+// `a2` (row stride `a2s`): the tile of relu(lin2) rows lin3 read - the operand of the dueling head's value stream.
+// Dueling rows: q[c] = v + (A[c] - mean A), v = lin_v_b + a2 . lin_v_w.  The wave that owns the row sums one product per
+// lane (64 = the width of a2) and one lane-strided slice of the advantages, each with a butterfly (every lane ends with the
+// same bits), and divides once by OUT - the same arithmetic in the three head kernels, whose a2 / a3 tiles are bitwise
+// equal.  OUT = 1: mean = A[0], the row is exactly v.
 template <int ROWS, int NTH>
-__device__ __forceinline__ void head_store(const mdq_gcn_net& net, int B, int g0, const float* a3, int OUTP, float* out) {
+__device__ __forceinline__ void head_store(const mdq_gcn_net& net, int B, int g0, const float* a3, int OUTP, const float* a2,
+                                           int a2s, float* out) {
   const int tid = threadIdx.x, OUT = net.out_dim;
   const int lane = tid & 63, wave = tid >> 6;
   for (int r = wave; r < ROWS; r += NTH / 64) {
@@ -919,6 +926,15 @@ __device__ __forceinline__ void head_store(const mdq_gcn_net& net, int B, int g0
       for (int c = lane; c < OUT; c += 64) s += expf(row[c] - mx);
       for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
       for (int c = lane; c < OUT; c += 64) out[(size_t)(g0 + r) * OUT + c] = expf(row[c] - mx) / s;
+    } else if (net.dueling) {
+      float v = a2[r * a2s + lane] * net.lin_v_w[lane];
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      v = net.lin_v_b[0] + v;
+      float s = 0.f;
+      for (int c = lane; c < OUT; c += 64) s += row[c];
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      const float mean = s / (float)OUT;
+      for (int c = lane; c < OUT; c += 64) out[(size_t)(g0 + r) * OUT + c] = v + (row[c] - mean);
     } else {
       for (int c = lane; c < OUT; c += 64) out[(size_t)(g0 + r) * OUT + c] = row[c];
     }
@@ -964,7 +980,7 @@ __global__ __launch_bounds__(WGH) void mlp_head_c128_kernel(mdq_gcn_net net, int
   if (wave < nblk3) head_mma<32>(a2, 65, w3a, b3a, OUT, wave, a3, OUTP, false);
   if (wave + 4 < nblk3) head_mma<32>(a2, 65, w3b, b3b, OUT, wave + 4, a3, OUTP, false);
   __syncthreads();
-  head_store(net, B, g0, a3, OUTP, out);
+  head_store(net, B, g0, a3, OUTP, a2, 65, out);
 }
 
 // The C = 128 head on tiles of 16 graphs: (B + 15) / 16 workgroups of 8 waves instead of (B + 31) / 32 of 4 (4 workgroups for
@@ -1047,7 +1063,7 @@ __global__ __launch_bounds__(WGH16) void mlp_head_c128_t16_kernel(mdq_gcn_net ne
   if (wave < nblk3) head16_mma<16>(a2, S2, w3a, b3a, OUT, wave, a3, OUTP, false);
   if (wave + 8 < nblk3) head16_mma<16>(a2, S2, w3b, b3b, OUT, wave + 8, a3, OUTP, false);
   __syncthreads();
-  head_store<16, WGH16>(net, B, g0, a3, OUTP, out);
+  head_store<16, WGH16>(net, B, g0, a3, OUTP, a2, S2, out);
 }
 
 }  // namespace mdq_gcn
@@ -1084,6 +1100,8 @@ static int gcn_forward_impl(const mdq_gcn_net* net, int32_t B, int32_t NMAX, int
   using namespace mdq_gcn;
   if (!net || B <= 0 || !x || !node_ptr || (!edge_ptr && !edge_cnt) || !emb || !out) return mdq_set_error("mdq_gcn_forward: bad arguments");
   const int C = net->C;
+  if (net->dueling && net->softmax) return mdq_set_error("mdq_gcn_forward: the dueling head excludes the softmax");
+  if (net->dueling && (!net->lin_v_w || !net->lin_v_b)) return mdq_set_error("mdq_gcn_forward: dueling head without lin_v_w / lin_v_b");
   if (C != 64 && C != 128 && C != 256 && C != 32) return mdq_set_error("mdq_gcn_forward: conv width must divide 256");
   if (net->fin0 > 32 && NMAX > NACC * (WGT / C)) return mdq_set_error("mdq_gcn_forward: graph too large for the input width");
   for (int l = 0; l < net->nlevels; ++l) {

@@ -214,7 +214,7 @@ __global__ __launch_bounds__(WGT) void gcn_train_kernel(mdq_gcn_net net, mdq_gcn
   float* dz2 = dz3 + OUTP;      // [64]
   float* dz1 = dz2 + 64;        // [128]
   float* scratch = dz1 + 128;   // [WGT]
-  float* scal = scratch + WGT;  // [4]: d loss / d q, index of q
+  float* scal = scratch + WGT;  // [4]: d loss / d q, index of q; dueling head: d loss / d v, 1 / OUT
   if (tid < C) {
     a0[tid] = rmax;
     a0[C + tid] = rmean;
@@ -228,8 +228,18 @@ __global__ __launch_bounds__(WGT) void gcn_train_kernel(mdq_gcn_net net, mdq_gcn
   __syncthreads();
   head_fwd(a2, 64, net.lin3_w, net.lin3_b, OUT, pr, scratch);
   TP_STAMP(8)
-  if (tid < 64) {   // wave 0: softmax, q, the loss term and d loss / d q
+  if (tid < 64) {   // wave 0: softmax | dueling aggregation, q, the loss term and d loss / d q
     const int lane = tid;
+    if (net.dueling) {   // q[c] = v + (A[c] - mean A), v = lin_v_b + a2 . lin_v_w: the arithmetic of the forward's head_store
+      float v = a2[lane] * net.lin_v_w[lane];
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      v = net.lin_v_b[0] + v;
+      float s = 0.f;
+      for (int c = lane; c < OUT; c += 64) s += pr[c];
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      const float mean = s / (float)OUT;
+      for (int c = lane; c < OUT; c += 64) pr[c] = v + (pr[c] - mean);
+    }
     if (net.softmax) {
       float mx = -INFINITY;
       for (int c = lane; c < OUT; c += 64) mx = fmaxf(mx, pr[c]);
@@ -291,6 +301,8 @@ __global__ __launch_bounds__(WGT) void gcn_train_kernel(mdq_gcn_net net, mdq_gcn
       ws[0] = term;
       scal[0] = dq;
       scal[1] = __int_as_float(jq);
+      scal[2] = dq;                   // d loss / d v: every q[c] carries v once, and only q[jq] has a gradient
+      scal[3] = 1.f / (float)OUT;     // d mean / d A[c]
     }
   }
   __syncthreads();
@@ -302,6 +314,8 @@ __global__ __launch_bounds__(WGT) void gcn_train_kernel(mdq_gcn_net net, mdq_gcn
     if (tid < OUT) {
       if (net.softmax)
         dz3[tid] = pr[tid] * ((tid == jq ? 1.f : 0.f) - pr[jq]) * dq;
+      else if (net.dueling)
+        dz3[tid] = dq * ((tid == jq ? 1.f : 0.f) - scal[3]);
       else
         dz3[tid] = tid == jq ? dq : 0.f;
     }
@@ -311,6 +325,12 @@ __global__ __launch_bounds__(WGT) void gcn_train_kernel(mdq_gcn_net net, mdq_gcn
   TP_STAMP(9)
   head_bwd_w(dz3, OUT, a2, 64, gp + G.lin3_w, gp + G.lin3_b);
   head_bwd_in(dz3, OUT, net.lin3_w, 64, dz2);
+  if (net.dueling && tid < 64) {   // the value stream: lin_v's gradients, and its share of d loss / d a2 before the relu mask
+    const float dv = scal[2];
+    gp[G.lin_v + tid] = dv * a2[tid];
+    if (tid == 0) gp[G.lin_v + 64] = dv;
+    dz2[tid] += dv * net.lin_v_w[tid];
+  }
   if (tid < 64) dz2[tid] = a2[tid] > 0.f ? dz2[tid] : 0.f;
   __syncthreads();
   head_bwd_w(dz2, 64, a1, 128, gp + G.lin2_w, gp + G.lin2_b);
@@ -516,6 +536,10 @@ extern "C" int mdq_gcn_train_step_weighted(const mdq_gcn_net* net, const mdq_gcn
       !d->nonfinal || !d->workspace || !d->partial || !d->grad || !d->loss)
     return mdq_set_error("mdq_gcn_train_step: bad arguments");
   const int C = net->C, NMAX = d->NMAX, EMAX = d->EMAX;
+  if (net->dueling && net->softmax) return mdq_set_error("mdq_gcn_train_step: the dueling head excludes the softmax");
+  if (net->dueling && (!net->lin_v_w || !net->lin_v_b)) return mdq_set_error("mdq_gcn_train_step: dueling head without lin_v_w / lin_v_b");
+  if (net->dueling && (d->layout.lin_v < 0 || d->layout.lin_v + 65 > d->layout.total))
+    return mdq_set_error("mdq_gcn_train_step: layout.lin_v outside the flat gradient");
   if (C != 64 && C != 128 && C != 256 && C != 32) return mdq_set_error("mdq_gcn_train_step: conv width must divide 256");
   if (net->out_dim > 256) return mdq_set_error("mdq_gcn_train_step: more than 256 head outputs");
   if (net->fin0 > 32 && NMAX > NACC * (WGT / C)) return mdq_set_error("mdq_gcn_train_step: graph too large for the input width");

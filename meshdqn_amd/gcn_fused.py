@@ -23,17 +23,20 @@ class GcnLevel(C.Structure):
 
 class GcnNet(C.Structure):
     _fields_ = [("nlevels", C.c_int32), ("C", C.c_int32), ("fin0", C.c_int32), ("out_dim", C.c_int32),
-                ("ratio", C.c_double), ("softmax", C.c_int32), ("_pad", C.c_int32),
+                ("ratio", C.c_double), ("softmax", C.c_int32), ("dueling", C.c_int32),
                 ("levels", GcnLevel * 6),
                 ("lin1_w", C.c_void_p), ("lin1_b", C.c_void_p), ("lin2_w", C.c_void_p), ("lin2_b", C.c_void_p),
-                ("lin3_w", C.c_void_p), ("lin3_b", C.c_void_p)]
+                ("lin3_w", C.c_void_p), ("lin3_b", C.c_void_p), ("lin_v_w", C.c_void_p), ("lin_v_b", C.c_void_p)]
 
 
 def _levels_of(net):
-    from .airfoilgcnn import AirfoilGCNN, NodeRemovalNet
+    """The conv / pool levels the forward runs, and whether a softmax follows lin3 (NodeRemovalNet: its `head` says;
+    the "linear" and "dueling" heads have none)."""
+    from .airfoilgcnn import AirfoilGCNN, NodeRemovalNet, check_head
     if isinstance(net, NodeRemovalNet):
         # conv3/pool3 and conv6/pool6 are skipped by the reference's forward (airfoilgcnn.py:106-110,124-128)
-        return [(net.conv1, net.pool1), (net.conv2, net.pool2), (net.conv4, net.pool4), (net.conv5, net.pool5)], True
+        return [(net.conv1, net.pool1), (net.conv2, net.pool2), (net.conv4, net.pool4), (net.conv5, net.pool5)], \
+            check_head(net.head) == "softmax"
     if isinstance(net, AirfoilGCNN):
         return [(net.conv1, net.pool1), (net.conv2, net.pool2), (net.conv3, net.pool3),
                 (net.conv4, net.pool4), (net.conv5, net.pool5), (net.conv6, net.pool6)], False
@@ -43,7 +46,7 @@ def _levels_of(net):
 class GcnGradLayout(C.Structure):
     _fields_ = [("w_l", C.c_int32 * 6), ("b", C.c_int32 * 6), ("w_r", C.c_int32 * 6), ("pool_w", C.c_int32 * 6),
                 ("lin1_w", C.c_int32), ("lin1_b", C.c_int32), ("lin2_w", C.c_int32), ("lin2_b", C.c_int32),
-                ("lin3_w", C.c_int32), ("lin3_b", C.c_int32), ("total", C.c_int32), ("_pad", C.c_int32)]
+                ("lin3_w", C.c_int32), ("lin3_b", C.c_int32), ("total", C.c_int32), ("lin_v", C.c_int32)]
 
 
 class GcnTrainDesc(C.Structure):
@@ -76,6 +79,7 @@ class FusedGcn:
         one-launch repack (mdq_gcn_pack) and the offsets of the parameters inside the flat gradient."""
         net = self.net
         levels, softmax = _levels_of(net)
+        dueling = getattr(net, "head", None) == "dueling"
         dev = net.lin1.weight.device
         if dev.type != "cuda":
             raise _lib.MeshDQNHipError("fused GCN kernels need the module on a GPU (no CPU fallback)")
@@ -109,6 +113,7 @@ class FusedGcn:
         d.out_dim = net.lin3.weight.shape[0]
         d.ratio = float(levels[0][1].ratio)
         d.softmax = 1 if softmax else 0
+        d.dueling = 1 if dueling else 0
         for l in range(6):
             lay.w_l[l] = lay.b[l] = lay.w_r[l] = lay.pool_w[l] = -1
         for l, (conv, pool) in enumerate(levels):
@@ -138,6 +143,13 @@ class FusedGcn:
         lay.lin1_w, lay.lin1_b = offs[id(net.lin1.weight)], offs[id(net.lin1.bias)]
         lay.lin2_w, lay.lin2_b = offs[id(net.lin2.weight)], offs[id(net.lin2.bias)]
         lay.lin3_w, lay.lin3_b = offs[id(net.lin3.weight)], offs[id(net.lin3.bias)]
+        if dueling:   # the value stream: two plain segments, one offset (the kernel finds the bias at lin_v + 64)
+            if tuple(net.lin_v.weight.shape) != (1, 64) or net.lin_v.bias is None:
+                raise ValueError("dueling head: lin_v must be Linear(64, 1) with a bias")
+            d.lin_v_w, d.lin_v_b = seg(net.lin_v.weight), seg(net.lin_v.bias)
+            lay.lin_v = offs[id(net.lin_v.weight)]
+            if offs[id(net.lin_v.bias)] != lay.lin_v + 64:
+                raise ValueError("dueling head: lin_v.weight and lin_v.bias must be adjacent in parameters() order")
         if net.lin1.weight.shape[0] != 128 or net.lin2.weight.shape[0] != 64:
             raise ValueError("head must be 2C -> 128 -> 64 -> out (as in the reference)")
         self.desc, self._keep, self._table, self.layout = d, keep, table, lay

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from . import streams as _st
-from .airfoilgcnn import NodeRemovalNet, dense_batch
+from .airfoilgcnn import NodeRemovalNet, check_head, dense_batch
 from .data import Batch
 # (besides what this module uses: every name other modules, the tools and the tests import from here)
 from .dist_context import DistContext, allgather_records, allgather_records_into, allgather_transitions  # noqa: F401
@@ -42,7 +42,8 @@ class DQNTrainer:
     def __init__(self, n_actions: int, num_inputs: int, ctx: Optional[DistContext] = None, lr=1e-5, weight_decay=1e-6,
                  batch_size=32, gamma=1.0, target_update=50, replay_capacity=10000, conv_width=128, topk=0.1,
                  seed=1370, dense: bool = True, e_max: int = 1536, prioritized: Optional[dict] = None, n_step: int = 1,
-                 target_net: Optional[dict] = None):
+                 target_net: Optional[dict] = None, head: str = "softmax"):
+        self.head = check_head(head)                       # the Q-head of both networks (a constructor option too)
         self.prioritized = self._check_prioritized(prioritized, batch_size)
         self.n_step = self._check_n_step(n_step)           # a constructor option like `prioritized`: not checkpointed
         self.target_net = self._check_target_net(target_net, target_update)     # ... and so is this one
@@ -52,8 +53,8 @@ class DQNTrainer:
         self.graphs = dev.type == "cuda"                   # replay forward + backward as a HIP graph when possible
         self._graphs, self._graph_error = {}, None
         torch.manual_seed(seed)  # identical initial replicas on every rank (airfoil_dqn.py:28-32)
-        self.policy_net_1 = NodeRemovalNet(n_actions + 1, conv_width=conv_width, topk=topk).float()
-        self.policy_net_2 = NodeRemovalNet(n_actions + 1, conv_width=conv_width, topk=topk).float()
+        self.policy_net_1 = NodeRemovalNet(n_actions + 1, conv_width=conv_width, topk=topk, head=self.head).float()
+        self.policy_net_2 = NodeRemovalNet(n_actions + 1, conv_width=conv_width, topk=topk, head=self.head).float()
         self.policy_net_1.set_num_nodes(num_inputs)
         self.policy_net_2.set_num_nodes(num_inputs)
         self.policy_net_1.to(dev)

@@ -1,6 +1,7 @@
 """A / B of the Q-head kernels (dev tool): `forward_arrays` of 128 graphs (180 nodes, ~400 edges each, the env step's shapes)
 with MDQ_HEAD_TILES=32 (mlp_head_c128_kernel, 32-graph tiles) against the default (mlp_head_c128_t16_kernel), alternately in
-one process; HIP events around every call, 200 calls per setting after a warm-up.  The embedding kernel is part of both."""
+one process; HIP events around every call, 200 calls per setting after a warm-up.  The embedding kernel is part of both.
+--q-head {softmax,linear,dueling}: the head of the network (default softmax)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -8,7 +9,8 @@ from meshdqn_amd.airfoilgcnn import NodeRemovalNet
 from meshdqn_amd.gcn_fused import FusedGcn
 B, N, E, F, CALLS = 128, 180, 400, 17, 200
 rng = np.random.default_rng(5)
-net = NodeRemovalNet(181, conv_width=128, topk=0.1); net.set_num_nodes(F); fused = FusedGcn(net.cuda())
+HEAD = sys.argv[sys.argv.index("--q-head") + 1] if "--q-head" in sys.argv else "softmax"
+net = NodeRemovalNet(181, conv_width=128, topk=0.1, head=HEAD); net.set_num_nodes(F); fused = FusedGcn(net.cuda())
 x = torch.from_numpy(rng.standard_normal((B * N, F))).float().cuda()
 node_ptr = torch.arange(B + 1, dtype=torch.int32, device="cuda") * N
 edge_ptr = torch.arange(B + 1, dtype=torch.int32, device="cuda") * E
@@ -35,4 +37,4 @@ for rnd in range(5):            # alternate the settings: 5 x 40 calls each
 print("outputs bitwise equal:", bool(np.array_equal(outs["32"].view(np.uint32), outs["16"].view(np.uint32))))
 for tiles in ("32", "16"):
     t = np.concatenate(res[tiles])
-    print(f"head tiles {tiles}: forward_arrays of {B} graphs, {t.size} calls: mean {t.mean():.2f} us, median {np.median(t):.2f} us, min {t.min():.2f} us")
+    print(f"q_head {HEAD}, head tiles {tiles}: forward_arrays of {B} graphs, {t.size} calls: mean {t.mean():.2f} us, median {np.median(t):.2f} us, min {t.min():.2f} us")

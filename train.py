@@ -68,6 +68,18 @@ def target_options(args, cfg: dict):
     return opt
 
 
+Q_HEADS = ("softmax", "linear", "dueling")
+
+
+def q_head_option(flag, cfg: dict) -> str:
+    """The `head` argument of `DQNTrainer` from --q-head and the optional top-level yaml key `q_head: dueling` (not a
+    reference key: its network's outputs are softmax probabilities).  The flag wins when both are given; neither: softmax."""
+    head = flag if flag is not None else cfg.get("q_head", "softmax")
+    if not isinstance(head, str) or head not in Q_HEADS:
+        raise SystemExit(f"q_head: {head!r} is none of " + ", ".join(Q_HEADS))
+    return head
+
+
 def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True, action="append",
@@ -117,6 +129,10 @@ def parser():
                     help="Polyak factor of the target refresh in (0, 1], target += T (online - target); default 1: a copy")
     ap.add_argument("--target-period", type=int, default=None, metavar="P",
                     help="gradient steps between two refreshes of the target network; default: agent_params.target_update")
+    ap.add_argument("--q-head", choices=Q_HEADS, default=None,
+                    help="what both Q-networks put out, in every loop: softmax (default, the reference's probabilities), linear "
+                         "(the raw lin3 outputs) or dueling (v + A - mean A with a value stream lin_v, Wang et al. 2016); also "
+                         "the top-level yaml key q_head:; checkpoints of different heads do not load into each other")
     ap.add_argument("--lift-weight", type=float, default=None, metavar="W",
                     help="weight of the lift in the reward, (drag_reward + W lift_reward) / (1 + W): the yaml key "
                          "agent_params.lift_weight (not a reference key: its reward reads the drag only); alone, the lift also "
@@ -193,7 +209,7 @@ def main():
                          batch_size=int(opt.get("batch_size", 32)), gamma=float(eps.get("gamma", 1.0)),
                          target_update=int(ap_.get("target_update", 50)),
                          prioritized=prioritized_options(args.prioritized_replay, cfg), n_step=n_step_option(args.n_step, cfg),
-                         target_net=target_options(args, cfg))
+                         target_net=target_options(args, cfg), head=q_head_option(args.q_head, cfg))
     # restart chain: restart n reads the checkpoint with n - 1 "restart_" prefixes and writes with n (every rank loads the
     # same files, so the replicas stay identical)
     restart_num, steps_done0 = 0, None
