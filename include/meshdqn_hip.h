@@ -736,6 +736,62 @@ typedef struct mdq_target_update_desc {
 } mdq_target_update_desc;
 MDQ_API int mdq_target_update(const mdq_target_update_desc* d, void* stream);
 
+/*
+ * Noisy-network exploration (Fortunato et al. 2018, factorised Gaussian noise on the dense head; no reference counterpart:
+ * its exploration is epsilon-greedy).  Appended within ABI 8.  The fused forward and the learning step read the PACKED copy
+ * of the parameters, so the noise is added while packing and neither of them changes.  All pointers device; no atomics.
+ *
+ * mdq_gcn_pack_noisy: mdq_gcn_pack with n = 1 .. MDQ_NOISY_MAX noisy layers, in ONE launch of the same grid.  A table
+ * segment that `nz` does not name is packed exactly as mdq_gcn_pack packs it.  Noisy layer L names its weight segment seg_w[L]
+ * (a transposed one: rows = out, cols = in) and its bias segment seg_b[L] (rows = out, cols = 1), sigma_w[L] float
+ * [out][in], sigma_b[L] float [out] and two OUTPUT vectors eps_in[L] float [in], eps_out[L] float [out].  It writes
+ *     dst_w[i * out + o] = mu_w[o][i] + sigma_w[o][i] * (eps_out[o] * eps_in[i])
+ *     dst_b[o]           = mu_b[o]    + sigma_b[o]    * eps_out[o]
+ * in float, in exactly these operations and this order, each rounded on its own (no fused multiply-add): a float32
+ * restatement from the eps vectors the launch wrote gives the same bits.
+ *
+ * The noise is counter-based, nothing comes from the host and no workgroup waits for another: entry j of side s (0 = in,
+ * 1 = out) of layer L is Philox4x32-10 (Salmon et al. 2011) with key (seed, stream) and counter (j, 2 L + s, draw_lo,
+ * draw_hi); of its output words r0, r1
+ *     u1 = ((r0 >> 8) + 1) * 2^-24   in (0, 1]        u2 = (r1 >> 8) * 2^-24   in [0, 1)
+ *     z  = sqrtf(-2 logf(u1)) * cospif(2 u2)          eps = copysignf(sqrtf(|z|), z)
+ * - the float functions are logf, sqrtf (correctly rounded) and cospif, whose argument 2 u2 is exact, so z keeps its
+ * relative accuracy where the cosine passes through zero.  Every workgroup recomputes the eps values its tile needs; the
+ * first workgroup of a layer's weight segment also stores the two vectors.  The same (seed, stream, draw) gives the same
+ * bits on every run, and |eps| <= sqrt(sqrt(48 ln 2)) < 2.41 always (u1 >= 2^-24).
+ *
+ * mdq_noisy_grad: the gradient of the sigmas from the gradient of the means the learning step wrote into the flat
+ * gradient `grad` (lay->total floats), one launch:
+ *     grad[sig_w[L] + o * in + i] = grad[mu_w[L] + o * in + i] * (eps_out[o] * eps_in[i])
+ *     grad[sig_b[L] + o]          = grad[mu_b[L] + o] * eps_out[o]
+ * with out = lay->out[L], in = lay->in[L], the same float product as the pack, read from the eps vectors of `nz` (of which
+ * it uses n and those pointers only).
+ *
+ * Refused before any launch (nonzero return, mdq_last_error names the entry point and the field): a NULL argument; n
+ * outside 1 .. 4; among the first n layers a NULL sigma or eps pointer; for the pack a bad table (n outside 1 .. 32), a
+ * segment index outside the table, a segment named twice, a weight segment with rows or cols < 1, a bias segment whose
+ * rows differ from the weight segment's or whose cols are not 1; for the gradient out or in < 1, a slice outside
+ * [0, total) and two slices (of any layers) that overlap.
+ */
+#define MDQ_NOISY_MAX 4
+typedef struct mdq_noisy_desc {
+  int32_t n, _pad;
+  uint32_t seed, stream;        /* the Philox key */
+  uint64_t draw;                /* counter words 2 (low half) and 3 */
+  int32_t seg_w[MDQ_NOISY_MAX], seg_b[MDQ_NOISY_MAX];
+  const float* sigma_w[MDQ_NOISY_MAX];
+  const float* sigma_b[MDQ_NOISY_MAX];
+  float* eps_in[MDQ_NOISY_MAX];
+  float* eps_out[MDQ_NOISY_MAX];
+} mdq_noisy_desc;
+typedef struct mdq_noisy_grad_layout {
+  int32_t total, _pad;
+  int32_t out[MDQ_NOISY_MAX], in[MDQ_NOISY_MAX];
+  int32_t mu_w[MDQ_NOISY_MAX], mu_b[MDQ_NOISY_MAX], sig_w[MDQ_NOISY_MAX], sig_b[MDQ_NOISY_MAX];
+} mdq_noisy_grad_layout;
+MDQ_API int mdq_gcn_pack_noisy(const mdq_gcn_pack_table* table, const mdq_noisy_desc* nz, void* stream);
+MDQ_API int mdq_noisy_grad(const mdq_noisy_desc* nz, const mdq_noisy_grad_layout* lay, float* grad, void* stream);
+
 /* Up to 8 buffer copies in one launch (no reference counterpart; the env step hands its meshes and the warm-start fields
  * to the flow engine with it): buffer t = rows[t] rows of row_bytes[t] bytes, consecutive rows src_stride_bytes[t] /
  * dst_stride_bytes[t] apart (all multiples of 4, pointers 4-byte aligned; device pointers, host arrays of them). */

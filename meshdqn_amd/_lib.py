@@ -173,6 +173,22 @@ class TargetUpdateDesc(C.Structure):
                 ("len", C.c_int32 * PACK_MAX), ("tau", C.c_double)]
 
 
+NOISY_MAX = 4      # MDQ_NOISY_MAX: noisy layers of one packed copy
+
+
+class NoisyDesc(C.Structure):
+    """Mirror of `mdq_noisy_desc` (appended within ABI 8)."""
+    _fields_ = [("n", C.c_int32), ("_pad", C.c_int32), ("seed", C.c_uint32), ("stream", C.c_uint32), ("draw", C.c_uint64),
+                ("seg_w", C.c_int32 * NOISY_MAX), ("seg_b", C.c_int32 * NOISY_MAX), ("sigma_w", C.c_void_p * NOISY_MAX),
+                ("sigma_b", C.c_void_p * NOISY_MAX), ("eps_in", C.c_void_p * NOISY_MAX), ("eps_out", C.c_void_p * NOISY_MAX)]
+
+
+class NoisyGradLayout(C.Structure):
+    """Mirror of `mdq_noisy_grad_layout` (appended within ABI 8)."""
+    _fields_ = [("total", C.c_int32), ("_pad", C.c_int32)] + [
+        (n, C.c_int32 * NOISY_MAX) for n in ("out", "in", "mu_w", "mu_b", "sig_w", "sig_b")]
+
+
 # every symbol include/meshdqn_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mdq_abi_version": (C.c_int, []),
@@ -268,6 +284,8 @@ SYMBOLS = {
     "mdq_adam_step": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mdq_double_q_select": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mdq_target_update": (C.c_int, [C.POINTER(TargetUpdateDesc), C.c_void_p]),
+    "mdq_gcn_pack_noisy": (C.c_int, [C.c_void_p, C.POINTER(NoisyDesc), C.c_void_p]),
+    "mdq_noisy_grad": (C.c_int, [C.POINTER(NoisyDesc), C.POINTER(NoisyGradLayout), C.c_void_p, C.c_void_p]),
     "mdq_spin": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
     "mdq_stream_create_cu_mask": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "mdq_stream_destroy": (C.c_int, [C.c_void_p]),

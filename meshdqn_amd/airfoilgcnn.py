@@ -225,14 +225,33 @@ def check_head(head):
     return head
 
 
+def check_noisy(noisy):
+    """None, or sigma0 of the noisy dense head as a finite float > 0."""
+    if noisy is None:
+        return None
+    if isinstance(noisy, bool) or not isinstance(noisy, (int, float, np.integer, np.floating)) or \
+            not (np.isfinite(noisy) and float(noisy) > 0.0):
+        raise ValueError(f"noisy must be None or a finite sigma0 > 0, not {noisy!r}")
+    return float(noisy)
+
+
 class NodeRemovalNet(nn.Module, _WeightAccessors):
     """`head` (not a reference feature) picks what the outputs of a graph are, with a2 = relu(lin2(relu(lin1(emb)))):
     "softmax" (default, the reference's network): softmax(lin3(a2)); "linear": lin3(a2); "dueling" (Wang et al. 2016):
-    v + (A - mean(A)) with A = lin3(a2) and v = lin_v(a2), `lin_v = Linear(64, 1)` existing for this head only."""
+    v + (A - mean(A)) with A = lin3(a2) and v = lin_v(a2), `lin_v = Linear(64, 1)` existing for this head only.
 
-    def __init__(self, output_dim, conv_width=64, topk=0.5, initial_num_nodes=None, head="softmax"):
+    `noisy` (not a reference feature either; None: nothing below exists): sigma0 of factorised Gaussian noise on the dense
+    head (Fortunato et al. 2018), whatever `head` is.  Layer L = lin1, lin2, lin3 (, lin_v) computes, once `set_noise` has
+    handed it vectors eps_in [in] and eps_out [out], F.linear(x, W + S * outer(eps_out, eps_in), b + s_b * eps_out).  All S
+    and s_b are slices of ONE flat parameter `noisy_sigma`, the last entry of `parameters()` (`noisy_layout()`), every entry
+    of a layer sigma0 / sqrt(in): constants, so the constructor draws the random numbers of the plain network and the mean
+    parameters have its bits.  Without noise set the network is its mean."""
+
+    def __init__(self, output_dim, conv_width=64, topk=0.5, initial_num_nodes=None, head="softmax", noisy=None):
         super(NodeRemovalNet, self).__init__()
         self.head = check_head(head)
+        self.noisy = check_noisy(noisy)
+        self._noise = None
         self.conv_width = conv_width
         self.topk = topk
         self.output_dim = output_dim
@@ -254,8 +273,59 @@ class NodeRemovalNet(nn.Module, _WeightAccessors):
         self.lin3 = torch.nn.Linear(64, output_dim)
         if self.head == "dueling":   # (registered last: the last two entries of parameters() and of the state_dict)
             self.lin_v = torch.nn.Linear(64, 1)
+        if self.noisy is not None:
+            sig = [torch.full((o * i + o,), self.noisy / math.sqrt(i)) for _, o, i, _, _ in self.noisy_layout()]
+            self.noisy_sigma = nn.Parameter(torch.cat(sig))
         torch.manual_seed(0)
         self.reset()
+
+    def noisy_layout(self):
+        """Per noisy layer (name, out, in, off_w, off_b): `noisy_sigma[off_w : off_w + out * in]` is the layer's S in torch
+        layout [out][in], `noisy_sigma[off_b : off_b + out]` its s_b; lin1, lin2, lin3 and, for the dueling head, lin_v."""
+        if self.noisy is None:
+            raise ValueError("noisy_layout: the network was built without noisy=sigma0")
+        out, off = [], 0
+        for name in ("lin1", "lin2", "lin3") + (("lin_v",) if self.head == "dueling" else ()):
+            o, i = getattr(self, name).weight.shape
+            out.append((name, o, i, off, off + o * i))
+            off += o * i + o
+        return out
+
+    def named_parameters(self, prefix="", recurse=True, remove_duplicate=True):
+        """torch's order (a module's own parameters in front of its children's) with `noisy_sigma` moved behind every other
+        parameter: the flat gradient, the Adam moments and the 173 493 entries in front keep their places."""
+        items = list(super().named_parameters(prefix=prefix, recurse=recurse, remove_duplicate=remove_duplicate))
+        own = (prefix + "." if prefix else "") + "noisy_sigma"
+        yield from (kv for kv in items if kv[0] != own)
+        yield from (kv for kv in items if kv[0] == own)
+
+    def set_noise(self, noise):
+        """None: the mean network.  {layer: (eps_in [in], eps_out [out])}: the autograd forwards compose those layers'
+        weights with the noise (a layer that is not named stays at its mean)."""
+        if noise is None:
+            self._noise = None
+            return
+        lay = {name: (o, i) for name, o, i, _, _ in self.noisy_layout()}
+        w = self.lin1.weight
+        held = {}
+        for name, (e_in, e_out) in noise.items():
+            if name not in lay:
+                raise ValueError(f"set_noise: {name!r} is no noisy layer of this network ({', '.join(lay)})")
+            e_in, e_out = (torch.as_tensor(e).to(w.device, w.dtype).reshape(-1) for e in (e_in, e_out))
+            if (e_out.numel(), e_in.numel()) != lay[name]:
+                raise ValueError(f"set_noise: {name} wants eps_in of {lay[name][1]} and eps_out of {lay[name][0]} entries")
+            held[name] = (e_in, e_out)
+        self._noise = held
+
+    def _dense(self, name, x):
+        """Layer `name` of the dense head: the module itself, or with noise set the composed weights."""
+        lin = getattr(self, name)
+        if self._noise is None or name not in self._noise:
+            return lin(x)
+        e_in, e_out = self._noise[name]
+        _, o, i, off_w, off_b = next(row for row in self.noisy_layout() if row[0] == name)
+        s_w, s_b = self.noisy_sigma[off_w:off_w + o * i].view(o, i), self.noisy_sigma[off_b:off_b + o]
+        return F.linear(x, lin.weight + s_w * torch.outer(e_out, e_in), lin.bias + s_b * e_out)
 
     def unused_parameters(self):
         return [p for m in (self.conv3, self.pool3, self.conv6, self.pool6) for p in m.parameters()]
@@ -274,11 +344,11 @@ class NodeRemovalNet(nn.Module, _WeightAccessors):
 
     def _head_out(self, a2):
         """The outputs of the graphs from their relu(lin2) rows."""
-        x = self.lin3(a2)
+        x = self._dense("lin3", a2)
         if self.head == "softmax":
             return F.softmax(x, dim=1)  # pick which vertex to remove
         if self.head == "dueling":
-            return self.lin_v(a2) + (x - x.mean(dim=1, keepdim=True))
+            return self._dense("lin_v", a2) + (x - x.mean(dim=1, keepdim=True))
         return x
 
     def set_num_nodes(self, initial_num_nodes):
@@ -290,7 +360,7 @@ class NodeRemovalNet(nn.Module, _WeightAccessors):
         self.removable = removable
 
     def forward(self, data, embedding=False):
-        x, edge_index, batch = data.x.float(), data.edge_index, data.batch
+        x, edge_index, batch = data.x.to(self.lin1.weight.dtype), data.edge_index, data.batch   # (float32 unless .double())
         x = F.relu(self.conv1(x, edge_index))
         x, edge_index, _, batch, _, _ = self.pool1(x, edge_index, None, batch)
         x1 = torch.cat([gmp(x, batch), gap(x, batch)], dim=1)
@@ -307,9 +377,9 @@ class NodeRemovalNet(nn.Module, _WeightAccessors):
         x = x1 + x2 + x4 + x5
         if embedding:
             return x
-        x = F.relu(self.lin1(x))
+        x = F.relu(self._dense("lin1", x))
         x = F.dropout(x, p=0.0, training=self.training)
-        x = F.relu(self.lin2(x))
+        x = F.relu(self._dense("lin2", x))
         return self._head_out(x)
 
     def forward_fused(self, data):
@@ -321,7 +391,7 @@ class NodeRemovalNet(nn.Module, _WeightAccessors):
         """Autograd path with static shapes: x (B,n,F) f32, src/dst (B,E) int64 local node ids, mask (B,E) 0/1 float
         (padded edges have mask 0 and any valid node id).  Same function as `forward` on the equivalent Batch."""
         A = _dense_adjacency(x.shape[1], src, dst, mask)
-        x = F.relu(_dense_sage(self.conv1, x.float(), A))
+        x = F.relu(_dense_sage(self.conv1, x.to(self.lin1.weight.dtype), A))
         x, A = _dense_topk(self.pool1, x, A)
         x1 = _dense_readout(x)
         x = F.relu(_dense_sage(self.conv2, x, A))
@@ -336,8 +406,8 @@ class NodeRemovalNet(nn.Module, _WeightAccessors):
         x = x1 + x2 + x4 + x5
         if embedding:
             return x
-        x = F.relu(self.lin1(x))
-        x = F.relu(self.lin2(x))
+        x = F.relu(self._dense("lin1", x))
+        x = F.relu(self._dense("lin2", x))
         return self._head_out(x)
 
 

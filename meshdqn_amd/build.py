@@ -43,6 +43,7 @@ UNITS = {
     "gcn": ("mdq_tu_gcn.hip", [], ["mdq_gcn.hip", "mdq_gcn_train.hip"]),
     "replay": ("mdq_replay.hip", [], []),
     "target": ("mdq_target.hip", [], []),
+    "noisy": ("mdq_noisy.hip", [], []),
     "mesh": ("mdq_mesh.hip", [], []),
     "smooth": ("mdq_tu_smooth.hip", [], ["mdq_smooth_shared.hip", "mdq_smooth_big.hip", "mdq_smooth.hip", "mdq_smooth_linear.hip"]),
     "topology": ("mdq_topology.hip", [], []),

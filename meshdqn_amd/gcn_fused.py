@@ -73,6 +73,57 @@ class FusedGcn:
         self._keep = []
         self.desc = None
         self._train_bufs = {}
+        # noisy networks: (seed, stream, draw) of the noise the packed copy carries, None: the mean network
+        self._noise = None
+        self.noisy_desc = self.noisy_layout = self.eps = None
+
+    def resample(self, seed: int, stream: int, draw: int):
+        """Pack the parameters WITH noise (`mdq_gcn_pack_noisy`, one launch on the current stream, instead of
+        `mdq_gcn_pack`): the dense head of the copy becomes mean + sigma * noise of Philox key (seed, stream), draw `draw`.
+        The copy keeps that noise through later repacks (new parameters, same noise) until the next `resample` or
+        `denoise`; `self.eps` holds {layer: (eps_in, eps_out)} device vectors the launch wrote, which `train_step` hands to
+        `mdq_noisy_grad`."""
+        if getattr(self.net, "noisy", None) is None:
+            raise ValueError("resample: the network was built without noisy=sigma0")
+        seed, stream, draw = int(seed), int(stream), int(draw)
+        if not (0 <= seed < 2 ** 32 and 0 <= stream < 2 ** 32 and 0 <= draw < 2 ** 64):
+            raise ValueError("resample: seed and stream are 32-bit, draw is a 64-bit unsigned number")
+        self._noise = (seed, stream, draw)
+        self._pack()
+
+    def denoise(self):
+        """The next pack (the next forward of this copy) is the mean network again."""
+        self._noise = None
+
+    def _build_noisy(self, table, segs, offs, keep, dev):
+        """Descriptor of the noisy pack and layout of the sigma gradients for the table just built (`segs`: parameter id ->
+        table segment, `offs`: parameter id -> offset in the flat gradient)."""
+        net = self.net
+        rows = net.noisy_layout()
+        if len(rows) > _lib.NOISY_MAX:
+            raise ValueError("too many noisy layers")
+        sig = net.noisy_sigma
+        if sig.dtype != torch.float32 or not sig.is_contiguous() or sig.device != dev:
+            raise ValueError("fused GCN kernels need noisy_sigma as a contiguous float32 parameter beside the others")
+        nz, lay = _lib.NoisyDesc(), _lib.NoisyGradLayout()
+        nz.n, lay.total = len(rows), self.layout.total
+        eps = torch.zeros(sum(o + i for _, o, i, _, _ in rows), dtype=torch.float32, device=dev)
+        keep.append(eps)
+        self.eps, at = {}, 0
+        for l, (name, o, i, off_w, off_b) in enumerate(rows):
+            lin = getattr(net, name)
+            nz.seg_w[l], nz.seg_b[l] = segs[id(lin.weight)], segs[id(lin.bias)]
+            if (table.rows[nz.seg_w[l]], table.cols[nz.seg_w[l]]) != (o, i):
+                raise ValueError(f"noisy layer {name}: its weight segment is not a transposed [{o}][{i}] one")
+            nz.sigma_w[l], nz.sigma_b[l] = sig.data_ptr() + 4 * off_w, sig.data_ptr() + 4 * off_b
+            e_in, e_out = eps[at:at + i], eps[at + i:at + i + o]
+            at += i + o
+            nz.eps_in[l], nz.eps_out[l] = e_in.data_ptr(), e_out.data_ptr()
+            self.eps[name] = (e_in, e_out)
+            lay.out[l], getattr(lay, "in")[l] = o, i             # (`in` is a keyword)
+            lay.mu_w[l], lay.mu_b[l] = offs[id(lin.weight)], offs[id(lin.bias)]
+            lay.sig_w[l], lay.sig_b[l] = offs[id(sig)] + off_w, offs[id(sig)] + off_b
+        self.noisy_desc, self.noisy_layout = nz, lay
 
     def _build_table(self):
         """Packed parameter buffers ([in][out] layout), the kernel descriptor pointing at them, the table of the
@@ -83,7 +134,7 @@ class FusedGcn:
         dev = net.lin1.weight.device
         if dev.type != "cuda":
             raise _lib.MeshDQNHipError("fused GCN kernels need the module on a GPU (no CPU fallback)")
-        keep, table = [], GcnPackTable()
+        keep, table, segs = [], GcnPackTable(), {}
         offs, pos = {}, 0
         for prm in net.parameters():
             offs[id(prm)] = pos
@@ -105,6 +156,7 @@ class FusedGcn:
             else:
                 table.rows[i], table.cols[i] = prm.numel(), 1
             table.n = i + 1
+            segs[id(prm)] = i
             return buf.data_ptr()
 
         d = GcnNet()
@@ -146,7 +198,8 @@ class FusedGcn:
         if dueling:   # the value stream: two plain segments, one offset (the kernel finds the bias at lin_v + 64)
             if tuple(net.lin_v.weight.shape) != (1, 64) or net.lin_v.bias is None:
                 raise ValueError("dueling head: lin_v must be Linear(64, 1) with a bias")
-            d.lin_v_w, d.lin_v_b = seg(net.lin_v.weight), seg(net.lin_v.bias)
+            # (a noisy layer's weight segment is a transposed one, rows = out; for this [1][64] weight the same 64 floats)
+            d.lin_v_w, d.lin_v_b = seg(net.lin_v.weight, getattr(net, "noisy", None) is not None), seg(net.lin_v.bias)
             lay.lin_v = offs[id(net.lin_v.weight)]
             if offs[id(net.lin_v.bias)] != lay.lin_v + 64:
                 raise ValueError("dueling head: lin_v.weight and lin_v.bias must be adjacent in parameters() order")
@@ -154,19 +207,28 @@ class FusedGcn:
             raise ValueError("head must be 2C -> 128 -> 64 -> out (as in the reference)")
         self.desc, self._keep, self._table, self.layout = d, keep, table, lay
         self._train_bufs = {}
+        if getattr(net, "noisy", None) is not None:
+            self._build_noisy(table, segs, offs, keep, dev)
 
     def _pack(self, stream=None):
-        """Bring the packed copy up to date: ONE launch (mdq_gcn_pack), and only after the parameters changed."""
+        """Bring the packed copy up to date: ONE launch (mdq_gcn_pack; mdq_gcn_pack_noisy for a copy that carries noise),
+        and only after the parameters or the noise state (`resample` / `denoise`) changed."""
         net = self.net
         # (`_mdq_version`: bumped by whoever writes the parameters with a kernel of its own, e.g. mdq_adam_step)
-        version = tuple(p._version for p in net.parameters()) + (id(net.conv1), getattr(net, "_mdq_version", 0))
+        version = tuple(p._version for p in net.parameters()) + (id(net.conv1), getattr(net, "_mdq_version", 0), self._noise)
         if version == self._version:
             return
         key = tuple(p.data_ptr() for p in net.parameters())
         if key != self._table_key:
             self._build_table()
             self._table_key = key
-        _lib.check(self.lib.mdq_gcn_pack(C.byref(self._table), _lib.stream_ptr(stream)), "mdq_gcn_pack")
+        if self._noise is None:
+            _lib.check(self.lib.mdq_gcn_pack(C.byref(self._table), _lib.stream_ptr(stream)), "mdq_gcn_pack")
+        else:
+            nz = self.noisy_desc
+            nz.seed, nz.stream, nz.draw = self._noise
+            _lib.check(self.lib.mdq_gcn_pack_noisy(C.byref(self._table), C.byref(nz), _lib.stream_ptr(stream)),
+                       "mdq_gcn_pack_noisy")
         self._version = version
 
     def train_step(self, x, node_ptr, esrc, edst, edge_ptr, nmax, emax, mode, q_other, action, reward, nonfinal, gamma,
@@ -174,7 +236,8 @@ class FusedGcn:
         """Forward + double-DQN Huber loss + backward of the module over a minibatch on the hand-written kernels
         (`mdq_gcn_train_step`, no autograd): returns (loss (1,) tensor, flat gradient over ALL parameters in
         `parameters()` order [, head outputs (B, out)]).  The returned tensors are persistent buffers that the next call
-        overwrites.  mode 0: this network evaluates the states, `q_other` the next states; mode 1 the other way
+        overwrites.  For a copy that carries noise (`resample`) the sigmas' slice is filled by `mdq_noisy_grad`, one more
+        launch behind the step; for the mean network it stays zero.  mode 0: this network evaluates the states, `q_other` the next states; mode 1 the other way
         round (the reference's `select` toggle, airfoil_dqn.py:240-310).  `loss_out`: a (1,) float32 device tensor to
         receive the loss instead of the internal one (e.g. a slot of a log ring: no copy, no synchronisation).
         `weight` / `td_out` ((B,) float32 device tensors, either may be None: `mdq_gcn_train_step_weighted`): importance
@@ -222,6 +285,10 @@ class FusedGcn:
             _lib.check(self.lib.mdq_gcn_train_step_weighted(
                 C.byref(d), C.byref(t), None if weight is None else weight.data_ptr(),
                 None if td_out is None else td_out.data_ptr(), _lib.stream_ptr(stream)), "mdq_gcn_train_step_weighted")
+        if self._noise is not None:
+            # the sigmas' slice (which the learning step leaves at zero) from the means' gradients and the eps of THIS copy's pack
+            _lib.check(self.lib.mdq_noisy_grad(C.byref(self.noisy_desc), C.byref(self.noisy_layout), bufs["grad"].data_ptr(),
+                                               _lib.stream_ptr(stream)), "mdq_noisy_grad")
         return (loss, bufs["grad"]) + ((bufs["out"],) if want_out else ())
 
     @torch.no_grad()

@@ -96,6 +96,14 @@ def _refuse_target_net(trainer, what: str):
                          "(DQNTrainer(target_net=...)) needs train_loop_device")
 
 
+def _refuse_noisy(trainer, what: str):
+    """Noisy networks get their noise from the pack launch of a device copy; the host paths run the torch modules, which
+    would be the mean networks without any exploration."""
+    if trainer.noisy is not None:
+        raise ValueError(f"{what} runs the torch modules, which carry no noise: a trainer with noisy networks "
+                         "(DQNTrainer(noisy=...)) needs train_loop_device")
+
+
 def _draw_epsilon(steps_done, n_actions: int, eps_start, eps_end, eps_decay):
     """Host random numbers of one batched step (both batched loops): epsilon per env, who explores, the random actions."""
     eps = eps_end + (eps_start - eps_end) * np.exp(-1.0 * steps_done / eps_decay)
@@ -134,6 +142,7 @@ def train_loop_per_worker(trainer: DQNTrainer, env_factory, num_episodes: int, m
     _refuse_prioritized(trainer, "train_loop_per_worker")
     _refuse_n_step(trainer, "train_loop_per_worker")
     _refuse_target_net(trainer, "train_loop_per_worker")
+    _refuse_noisy(trainer, "train_loop_per_worker")
     ctx = trainer.ctx
     if ctx.world > 1 and max_steps is None:
         raise ValueError("train_loop_per_worker with more than one rank needs max_steps (a step count common to all "
@@ -195,6 +204,7 @@ def train_loop_vec(trainer: DQNTrainer, venv, num_steps: int, optim_per_step: in
     _refuse_prioritized(trainer, "train_loop_vec")
     _refuse_n_step(trainer, "train_loop_vec")
     _refuse_target_net(trainer, "train_loop_vec")
+    _refuse_noisy(trainer, "train_loop_vec")
     ctx = trainer.ctx
     B, N = venv.B, venv.N
     fused = FusedGcn(trainer.policy_net_1)
@@ -328,7 +338,13 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
     the train-role copies of both networks are repacked on that stream, in order with the kernels that write the
     parameters; the acting copy belongs to policy_net_1 and follows it as before.  `target_trace=True` (kind "double" only)
     adds out["target"]: `sel` (int32) and `value` (float32), (minibatches, batch): the action the online network chose in
-    every next state and the target network's value of it, read back like the `per` trace."""
+    every next state and the target network's value of it, read back like the `per` trace.
+
+    With `DQNTrainer(noisy=...)` exploration is the networks' own: where the acting copy follows the parameters (below) it is
+    packed with fresh noise instead (`mdq_gcn_pack_noisy` in place of `mdq_gcn_pack`: no launch more), one draw per batched
+    step shared by the B environments; `explore` is all false, no epsilon is drawn (the host's numpy stream is not
+    touched, the logged epsilon is 0, the step counters still count) and the optimiser chain resamples its own copies
+    (`optimize_device`).  At the end the acting copy is told to drop its noise: `select_action` and `deploy` see the mean."""
     ctx = trainer.ctx
     dev = ctx.device
     per = trainer.prioritized
@@ -388,6 +404,10 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
         # random numbers of the chunk, drawn step by step in train_loop_vec's order
         explore, rand_act, eps_mean = np.zeros((K, B), bool), np.zeros((K, B), np.int32), []
         for k in range(K):
+            if trainer.noisy is not None:       # no epsilon-greedy: `explore` stays all false
+                steps_done += 1
+                eps_mean.append(0.0)
+                continue
             eps, explore[k], rand_act[k] = _draw_epsilon(steps_done, trainer.n_actions, eps_start, eps_end, eps_decay)
             eps_mean.append(float(eps.mean()))
         ro = venv.rollout_begin(K, explore, rand_act)
@@ -429,7 +449,10 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
             # the ACTING copy follows the parameters here and only here: behind the event of the last optimiser chain and
             # in front of the next one (which waits for `ev` below); rollout_step must not repack (pack=False): by then
             # the host has already bumped the version for an Adam kernel that is still in flight on the other stream
-            fused1._pack()
+            if trainer.noisy is None:
+                fused1._pack()
+            else:                               # ... with this step's noise: one draw for the B environments
+                trainer.resample("act1")
             base_cur = rep.group_base(t) + (ctx.rank * B if W != B else 0)     # this rank's B records of the step's group
             rep.step(st, base_cur, prev)
             ev = torch.cuda.Event()
@@ -514,6 +537,7 @@ def train_loop_device(trainer: DQNTrainer, venv, num_steps: int, optim_per_step:
         step_no += K
         if every and on_every is not None and (step_no // every) > ((step_no - K) // every):
             on_every(step_no, steps_done)
+    fused1.denoise()                # (a no-op for a copy that never carried noise)
     out = dict(rewards=np.array(rewards), dones=np.array(dones_hist), losses=list(trainer.losses), steps_done=steps_done,
                actions=np.array(actions_hist), reasons=np.array(reasons_hist))     # (reasons: reward.REASON_* per step)
     if per_trace:

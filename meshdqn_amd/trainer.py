@@ -34,7 +34,7 @@ from .gcn_fused import fused_of
 from .replay import (DeviceBatch, DeviceReplay, ReplayMemory, SharedDeviceReplay, StateRef, Transition,  # noqa: F401
                      gather_state_refs, pack_transitions, pack_transitions_device, state_refs, state_to_data_list,
                      unpack_transitions)
-from .train_loops import (TrainingLog, _refuse_target_net, epsilon_threshold, train_loop_device,  # noqa: F401
+from .train_loops import (TrainingLog, _refuse_noisy, _refuse_target_net, epsilon_threshold, train_loop_device,  # noqa: F401
                           train_loop_per_worker, train_loop_vec)
 
 
@@ -42,8 +42,9 @@ class DQNTrainer:
     def __init__(self, n_actions: int, num_inputs: int, ctx: Optional[DistContext] = None, lr=1e-5, weight_decay=1e-6,
                  batch_size=32, gamma=1.0, target_update=50, replay_capacity=10000, conv_width=128, topk=0.1,
                  seed=1370, dense: bool = True, e_max: int = 1536, prioritized: Optional[dict] = None, n_step: int = 1,
-                 target_net: Optional[dict] = None, head: str = "softmax"):
+                 target_net: Optional[dict] = None, head: str = "softmax", noisy: Optional[dict] = None):
         self.head = check_head(head)                       # the Q-head of both networks (a constructor option too)
+        self.noisy = self._check_noisy(noisy, seed)        # noisy dense heads of both networks (a constructor option too)
         self.prioritized = self._check_prioritized(prioritized, batch_size)
         self.n_step = self._check_n_step(n_step)           # a constructor option like `prioritized`: not checkpointed
         self.target_net = self._check_target_net(target_net, target_update)     # ... and so is this one
@@ -53,8 +54,9 @@ class DQNTrainer:
         self.graphs = dev.type == "cuda"                   # replay forward + backward as a HIP graph when possible
         self._graphs, self._graph_error = {}, None
         torch.manual_seed(seed)  # identical initial replicas on every rank (airfoil_dqn.py:28-32)
-        self.policy_net_1 = NodeRemovalNet(n_actions + 1, conv_width=conv_width, topk=topk, head=self.head).float()
-        self.policy_net_2 = NodeRemovalNet(n_actions + 1, conv_width=conv_width, topk=topk, head=self.head).float()
+        nkw = {} if self.noisy is None else dict(noisy=self.noisy["sigma0"])
+        self.policy_net_1 = NodeRemovalNet(n_actions + 1, conv_width=conv_width, topk=topk, head=self.head, **nkw).float()
+        self.policy_net_2 = NodeRemovalNet(n_actions + 1, conv_width=conv_width, topk=topk, head=self.head, **nkw).float()
         self.policy_net_1.set_num_nodes(num_inputs)
         self.policy_net_2.set_num_nodes(num_inputs)
         self.policy_net_1.to(dev)
@@ -80,6 +82,8 @@ class DQNTrainer:
         # the optimiser stream was calibrated against, flat Adam moments per network, minibatch buffers of `optimize_device`
         self._opt_stream = self._main_stream = self._opt_calibrated_for = self._adam = self._mb_bufs = None
         self._target_desc = None    # descriptor of `mdq_target_update` (policy_net_2 <- policy_net_1), built on first use
+        # noisy networks: the 64-bit draw counter of every packed copy that carries noise (checkpointed with the option on)
+        self.noise_draws = {copy: 0 for copy in self.NOISE_COPIES}
         self.opt_calibration_ms: List[float] = []
         random.seed(seed + self.ctx.rank)
         np.random.seed(seed + self.ctx.rank)
@@ -155,6 +159,40 @@ class DQNTrainer:
                 not (np.isfinite(tau) and 0.0 < float(tau) <= 1.0):
             raise ValueError(f"target_net: tau must lie in (0, 1], not {tau!r}")
         return dict(kind=kind, period=int(period), tau=float(tau))
+
+    # --- noisy networks (Fortunato et al. 2018; `train_loop_device` only: the noise is added by the pack launch) -----
+    NOISE_COPIES = ("act1", "train1", "train2")     # acting copy of net 1, train copies of net 1 and net 2: stream 4 rank + index
+
+    @staticmethod
+    def _check_noisy(noisy, seed) -> Optional[dict]:
+        """None (epsilon-greedy, the reference's exploration), or the complete option dict: both networks carry factorised
+        Gaussian noise of initial scale sigma0 / sqrt(in) on their dense heads (`NodeRemovalNet(noisy=sigma0)`), drawn on the
+        device from Philox key (seed, stream of the copy); `seed` defaults to the trainer's."""
+        if noisy is None:
+            return None
+        known = ("sigma0", "seed")
+        if not isinstance(noisy, dict):
+            raise ValueError("noisy: None or a dict with any of " + ", ".join(known))
+        unknown = sorted(set(noisy) - set(known), key=repr)
+        if unknown:
+            raise ValueError(f"noisy: unknown option(s) {unknown}; known: " + ", ".join(known))
+        sigma0 = noisy.get("sigma0", 0.5)
+        if isinstance(sigma0, bool) or not isinstance(sigma0, (int, float, np.integer, np.floating)) or \
+                not (np.isfinite(sigma0) and float(sigma0) > 0.0):
+            raise ValueError(f"noisy: sigma0 must be finite and > 0, not {sigma0!r}")
+        nseed = noisy.get("seed", seed)
+        if isinstance(nseed, bool) or not isinstance(nseed, (int, np.integer)) or not 0 <= int(nseed) < 2 ** 32:
+            raise ValueError(f"noisy: seed must be an integer in 0 .. 2^32 - 1, not {nseed!r}")
+        return dict(sigma0=float(sigma0), seed=int(nseed))
+
+    def resample(self, copy: str):
+        """New noise for packed copy `copy` (one of NOISE_COPIES) on the current stream: its next draw, from its own stream."""
+        k = self.NOISE_COPIES.index(copy)
+        net = self.policy_net_2 if copy == "train2" else self.policy_net_1
+        fused = self._fused_of(net, "act" if copy == "act1" else "train")
+        fused.resample(self.noisy["seed"], 4 * self.ctx.rank + k, self.noise_draws[copy])
+        self.noise_draws[copy] += 1
+        return fused
 
     def beta(self, g: Optional[int] = None) -> float:
         """Importance-weight exponent after g gradient applications (`num_grads`, which is checkpointed: a restart
@@ -329,6 +367,7 @@ class DQNTrainer:
         """One optimiser step (airfoil_dqn.py:315-340 + :184-200 + :286-310): local loss/backward, ONE flat
         all-reduce of the gradient over all ranks, identical Adam step on every rank."""
         _refuse_target_net(self, "optimize")
+        _refuse_noisy(self, "optimize")
         if transitions is None:
             mem = self.device_memory if self.device_memory is not None else self.memory
             if mem.size() < self.batch_size:
@@ -437,7 +476,7 @@ class DQNTrainer:
         mapping leaves pairs that overlap only partly, and the learning loop then runs at 2.6 instead of 1.95 ms per
         batched step.  Every candidate carries a stand-in chain (fused forward of one network + `mdq_gcn_train_step` of
         the other on a fixed random minibatch, with `target_net` kind "double" also the second forward and the select
-        launch: the kernels of `optimize_device`, no parameter is changed) through a few
+        launch: the kernels of `optimize_device`, with `noisy` also the two noisy packs and `mdq_noisy_grad`; no parameter is changed) through a few
         real env steps with the loop's own synchronisation; the fastest stays.  The environments are reset afterwards."""
         dev = self.ctx.device
         main = torch.cuda.current_stream(dev)
@@ -467,6 +506,7 @@ class DQNTrainer:
         f1, f2 = self._fused_of(self.policy_net_1, "train"), self._fused_of(self.policy_net_2, "train")
         f1._pack()
         f2._pack()
+        noisy, probe = self.noisy is not None, [0]
         double = self.target_net is not None and self.target_net["kind"] == "double"
         q_sel = torch.zeros((mb, self.n_actions + 1), dtype=torch.float32, device=dev) if double else None
         rng = np.random.default_rng(977)
@@ -481,6 +521,10 @@ class DQNTrainer:
                 ev.record(main)
                 with torch.cuda.stream(cand):
                     cand.wait_event(ev)
+                    if noisy:       # the chain that will run: both noisy packs (another draw forces the launch) and, from
+                        probe[0] += 1   # `train_step` of a copy that carries noise, `mdq_noisy_grad`; no counter moves
+                        f1.resample(self.noisy["seed"], 1, 2 ** 63 + probe[0])
+                        f2.resample(self.noisy["seed"], 2, 2 ** 63 + probe[0])
                     qo = f2.forward_arrays(x, node_ptr, esrc, edst, edge_ptr, N, EM)
                     if double:      # the chain that will run: the online network's forward and the select launch as well
                         q_on = f1.forward_arrays(x, node_ptr, esrc, edst, edge_ptr, N, EM)
@@ -506,6 +550,8 @@ class DQNTrainer:
         self._opt_stream = min(results, key=lambda r: r[0])[1]
         self._opt_calibrated_for = (main, venv._flow_stream)
         self.opt_calibration_ms = [r[0] for r in results]
+        f1.denoise()
+        f2.denoise()
         venv.reset_all()
         return self.opt_calibration_ms
 
@@ -532,7 +578,13 @@ class DQNTrainer:
         a row per graph whose maximum is Q_target(s', argmax_a Q_online(s', a)), the unchanged learning step with that as
         `q_other`, the all-reduce, `mdq_adam_step`, and every `period` gradient steps `mdq_target_update` (target <- online,
         `tau`) on the same stream.  Every rank runs the same update on identical replicas: no collective.  `sel_out` /
-        `value_out` (kind "double"): (batch,) int32 / float32 device tensors that receive the chosen action and that value."""
+        `value_out` (kind "double"): (batch,) int32 / float32 device tensors that receive the chosen action and that value.
+
+        A trainer with `noisy` first resamples the train copies of both networks (`mdq_gcn_pack_noisy` in place of their
+        repack): every forward and the learning step of this call see one draw per network - in the Double-DQN chain the
+        online network's forward on s' and its learning step share theirs -, `train_step` adds `mdq_noisy_grad` with the
+        eps of that draw in front of the all-reduce, and `mdq_adam_step` / `mdq_target_update` take `noisy_sigma` as one more
+        parameter tensor."""
         dev = self.ctx.device
         if self.n_step > 1 and head_step is None:
             raise ValueError("optimize_device: a trainer with n_step > 1 needs head_step (the batched step being written)")
@@ -544,6 +596,9 @@ class DQNTrainer:
         sel = True if tn is not None else self.select
         k = 0 if sel else 1
         net, other = ((self.policy_net_1, self.policy_net_2) if sel else (self.policy_net_2, self.policy_net_1))
+        if self.noisy is not None:      # one draw per network per optimiser step, in order with this stream's Adam launches
+            self.resample("train1")
+            self.resample("train2")
         mb, N, F, EM = len(idx), rep.N, rep.F, rep.e_max
         b = self._mb_bufs
         if b is None or b["key"] != (mb, N, F, EM):
@@ -632,12 +687,13 @@ class DQNTrainer:
         """`ParameterServer.write` (airfoil_dqn.py:214-218): PyG-keyed state dicts `{prefix}policy_net_{1,2}.pt`, plus
         `{prefix}trainer_state.pt` (both Adam states, both schedulers, gradient count, the double-DQN toggle and
         whatever the loop hands over in `extra`, e.g. its epsilon step counters) - what a restart needs beyond the
-        reference's two files."""
+        reference's two files.  A trainer with `noisy` adds the draw counters of its packed copies."""
         os.makedirs(save_dir, exist_ok=True)
         torch.save(self.policy_net_1.state_dict(), os.path.join(save_dir, f"{prefix}policy_net_1.pt"))
         torch.save(self.policy_net_2.state_dict(), os.path.join(save_dir, f"{prefix}policy_net_2.pt"))
         torch.save(dict(opts=[o.state_dict() for o in self.opts], scheds=[s_.state_dict() for s_ in self.scheds],
-                        num_grads=self.num_grads, select=self.select, extra=extra or {}),
+                        num_grads=self.num_grads, select=self.select, extra=extra or {},
+                        **({} if self.noisy is None else dict(noise_draws=dict(self.noise_draws)))),
                    os.path.join(save_dir, f"{prefix}trainer_state.pt"))
 
     def load(self, save_dir, prefix="", scheduler_steps: Optional[int] = None) -> dict:
@@ -670,6 +726,8 @@ class DQNTrainer:
             for s_, sd in zip(self.scheds, st["scheds"]):
                 s_.load_state_dict(sd)
             self.num_grads, self.select, extra = int(st["num_grads"]), bool(st["select"]), st.get("extra", {})
+            if self.noisy is not None:      # the noise continues where the checkpoint stopped (counters of a noisy run only)
+                self.noise_draws.update({c: int(v) for c, v in st.get("noise_draws", {}).items() if c in self.noise_draws})
         elif scheduler_steps:
             import warnings
             with warnings.catch_warnings():

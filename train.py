@@ -80,6 +80,24 @@ def q_head_option(flag, cfg: dict) -> str:
     return head
 
 
+def noisy_options(flag, cfg: dict):
+    """The `noisy` argument of `DQNTrainer` from --noisy-net [SIGMA0] and the optional top-level yaml block
+    `noisy_net: {sigma0: 0.5}` (not a reference section: its exploration is epsilon-greedy).  None: epsilon-greedy.  The
+    block alone switches the option on; the flag's number wins over the block's; the noise seed is the trainer's."""
+    block = cfg.get("noisy_net")
+    if block is not None and not isinstance(block, dict):
+        raise SystemExit(f"noisy_net: a block with sigma0, not {block!r}")
+    if block is None and flag is None:
+        return None
+    opt = dict(block or {})
+    unknown = sorted(set(opt) - {"sigma0"}, key=repr)
+    if unknown:
+        raise SystemExit(f"noisy_net: unknown key(s) {unknown} (known: sigma0)")
+    if flag is not None and flag is not True:
+        opt["sigma0"] = float(flag)
+    return opt
+
+
 def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True, action="append",
@@ -133,6 +151,11 @@ def parser():
                     help="what both Q-networks put out, in every loop: softmax (default, the reference's probabilities), linear "
                          "(the raw lin3 outputs) or dueling (v + A - mean A with a value stream lin_v, Wang et al. 2016); also "
                          "the top-level yaml key q_head:; checkpoints of different heads do not load into each other")
+    ap.add_argument("--noisy-net", nargs="?", type=float, const=True, default=None, metavar="SIGMA0",
+                    help="noisy networks in the device-resident loop instead of epsilon-greedy: factorised Gaussian noise of "
+                         "initial scale SIGMA0 / sqrt(inputs) (default 0.5) on the dense head of both Q-networks, drawn on the "
+                         "device while the parameters are packed, one draw per batched step; also the yaml block "
+                         "noisy_net: {sigma0: 0.5}; checkpoints with and without it do not load into each other")
     ap.add_argument("--lift-weight", type=float, default=None, metavar="W",
                     help="weight of the lift in the reward, (drag_reward + W lift_reward) / (1 + W): the yaml key "
                          "agent_params.lift_weight (not a reference key: its reward reads the drag only); alone, the lift also "
@@ -209,7 +232,8 @@ def main():
                          batch_size=int(opt.get("batch_size", 32)), gamma=float(eps.get("gamma", 1.0)),
                          target_update=int(ap_.get("target_update", 50)),
                          prioritized=prioritized_options(args.prioritized_replay, cfg), n_step=n_step_option(args.n_step, cfg),
-                         target_net=target_options(args, cfg), head=q_head_option(args.q_head, cfg))
+                         target_net=target_options(args, cfg), head=q_head_option(args.q_head, cfg),
+                         noisy=noisy_options(args.noisy_net, cfg))
     # restart chain: restart n reads the checkpoint with n - 1 "restart_" prefixes and writes with n (every rank loads the
     # same files, so the replicas stay identical)
     restart_num, steps_done0 = 0, None
@@ -248,6 +272,8 @@ def main():
         raise SystemExit("n-step returns need the device-resident loop (a GPU, the device mesh engine, no --host-loop)")
     if trainer.target_net is not None and not device_loop:
         raise SystemExit("a target network needs the device-resident loop (a GPU, the device mesh engine, no --host-loop)")
+    if trainer.noisy is not None and not device_loop:
+        raise SystemExit("noisy networks need the device-resident loop (a GPU, the device mesh engine, no --host-loop)")
     loop = train_loop_device if device_loop else train_loop_vec
     kw, every, on_every = {}, args.save_every, checkpoint
     if args.digest:
