@@ -489,6 +489,7 @@ def test_dueling_double_chain_equals_the_learning_step_by_hand(run_default):
 
 
 def test_loop_dueling_prioritized_n_step_is_reproducible(base_env):
+    """(Reproducibility only: the combined chain is held to an fp64 reference in tests/test_optimizer_chain_gpu.py.)"""
     a, ta = _run(base_env, prioritized=PER, n_step=3, head="dueling")
     b, tb = _run(base_env, prioritized=PER, n_step=3, head="dueling")
     _same_run(a, ta, b, tb)

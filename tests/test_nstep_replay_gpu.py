@@ -370,6 +370,7 @@ def test_loop_on_a_ring_that_wraps(base_env):
 
 
 def test_loop_with_prioritized_replay(base_env, run_three_steps_prioritized):
+    """(The prioritized trace of such a run is replayed in full, and the chain held to fp64, in tests/test_optimizer_chain_gpu.py.)"""
     out, tr = run_three_steps_prioritized
     assert np.isfinite(out["per"]["td"]).all() and np.isfinite(out["losses"]).all()
     assert np.array_equal(out["per"]["idx"], out["nstep"]["idx"])     # the drawn records are the ones the walks start from

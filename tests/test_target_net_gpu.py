@@ -480,6 +480,7 @@ def test_loop_period_one_ends_with_the_target_equal_to_the_online_network(base_e
 
 
 def test_loop_with_prioritized_replay_and_n_step(base_env):
+    """(Reproducibility only: the combined chain is held to an fp64 reference in tests/test_optimizer_chain_gpu.py.)"""
     a, ta = _run_target(base_env, DOUBLE, prioritized=PER, n_step=3)
     b, tb = _run_target(base_env, DOUBLE, prioritized=PER, n_step=3)
     _same_run(a, ta, b, tb)
